@@ -2,6 +2,7 @@
 """bench.py — time-steps/s of the k-space first-order loop on MI355X (BASELINE.json metric).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--size n] [--no-cpu] [--no-512] [--weak | --strong]
+                  [--dump-outputs DIR]
 
 N=1 workload: BASELINE config 3 — 256^3 heterogeneous (c0, rho0, BonA, alpha_coeff as arrays), power-law absorption +
 nonlinear term, p0 source, p_raw + p_max sampled on one xy plane (the manual's benchmark setup).
@@ -164,6 +165,51 @@ def pmc_traffic_for_this_build():
         if d.get("kernel_source_hash") == cur:
             return f, d
     return None, None
+
+
+DUMP_FIELDS = ("p", "ux", "uy", "uz", "rhox", "rhoy", "rhoz")  # the state a step leaves behind
+DUMP_POINTS = 1 << 20  # per field: a larger grid is sampled at this many points (7 x 4 MiB + the two sensor rows)
+DUMP_SEED = 0x0D0D
+
+
+def _stream_so_far(sim, name):
+    """(values, sampled steps) of an output stream in the middle of a run, as the solver holds it: a raw series with
+    the row still in flight flushed first, an aggregate (p_max) copied from its device accumulator"""
+    import numpy as np
+    from kwave_amd.solver import _check
+    n, steps = C.c_uint64(), C.c_uint64()
+    _check(sim.L.kwh_stream_checkpoint(sim._h, name.encode(), None, 0, C.byref(n), C.byref(steps)))
+    a = np.empty(n.value, dtype=np.float32)
+    _check(sim.L.kwh_stream_checkpoint(sim._h, name.encode(), a.ctypes.data, a.size, C.byref(n), C.byref(steps)))
+    return a, steps.value
+
+
+def dump_outputs(sim, out_dir):
+    """What the timed path computed in its last step, as float32 .npy files in out_dir: the state fields (the whole
+    grid up to DUMP_POINTS voxels; beyond that the same seeded sample for every field: one voxel drawn from each of
+    DUMP_POINTS equal runs of linear indices) and the sensor outputs the solver hands back: the p_raw series' row of
+    that step (p_raw_last) and the running p_max.  The inputs are seeded, so two builds run with the same arguments
+    can be compared file for file."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    sim.sync()
+    n = sim.nx * sim.ny * sim.nz
+    idx = None
+    if n > DUMP_POINTS:
+        run = n // DUMP_POINTS
+        idx = np.arange(DUMP_POINTS, dtype=np.int64) * run + np.random.default_rng(DUMP_SEED).integers(0, run, DUMP_POINTS)
+    files = {}
+    for name in DUMP_FIELDS:
+        a = sim.field(name).reshape(-1)
+        files[name if idx is None else name + "_sample"] = a if idx is None else a[idx]
+    raw, rows = _stream_so_far(sim, "p")
+    if rows != sim.t:  # sampling starts at step 0: one row per step
+        raise RuntimeError(f"p_raw holds {rows} rows after {sim.t} steps")
+    files["p_raw_last"] = raw.reshape(rows, -1)[-1]
+    files["p_max"], _ = _stream_so_far(sim, "p_max")
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return sorted(files)
 
 
 WEAK_DIMS = {1: (256, 256, 256), 2: (256, 256, 512), 4: (256, 512, 512), 8: (512, 512, 512)}  # 256^3 voxels per GPU
@@ -396,7 +442,12 @@ def main():
                     help="N>1 data path: the device library's own RCCL exchange, or torch.distributed as a callback")
     ap.add_argument("--slab-selftest", action="store_true",
                     help="one rank through the N>1 code path (slab kernels + RCCL all-to-all with itself): rehearsal on a 1-GPU box")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N=1: write the state and the sensor outputs (p_raw row, p_max) after the last timed step to "
+                         "DIR/<name>.npy (float32, under 64 MB in all)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or args.slab_selftest or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("--dump-outputs is only supported with --gpus 1")
 
     if args.slab_selftest:
         for k, v in (("MASTER_ADDR", "127.0.0.1"), ("MASTER_PORT", "29533"), ("RANK", "0"), ("WORLD_SIZE", "1"), ("LOCAL_RANK", "0")):
@@ -428,7 +479,10 @@ def main():
     sim.sync()
     ms = sim.time_steps(K)  # HIP events on the solver's stream around exactly K steps; synchronises on the stop event
     sim.sync()
+    if sim.t != W + K:
+        raise RuntimeError(f"the solver stopped at time index {sim.t}, not after {W} + {K} steps")
     steps_per_s = K / (ms * 1e-3)
+    dumped = dump_outputs(sim, args.dump_outputs) if args.dump_outputs else None
 
     # --- per entry point timing (live, same process, same workload) ---
     hip = capi.load()
@@ -500,6 +554,8 @@ def main():
            "roofline": roofline}
     if c4_one is not None:
         out["config"]["c4_512"] = c4_one
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "files": [f + ".npy" for f in dumped], "time_index": W + K}
     if not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(pr, n)
     print(json.dumps(out))

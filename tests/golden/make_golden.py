@@ -5,6 +5,9 @@
                      oracle/Makefile into oracle/_ref/libcompress_ref.so (never copied): the four bases for three
                      (period, mos, harmonics) triples, findPeriod on sampled sines, 40-bit codec round trips.
                      These pin oracle/kwave_oracle.c's restatement of the compression basis (config 5).
+  compress_ref_edges.npz  the same compiled reference's 40-bit encodings of edge values (zeros, 21 decades of
+                     magnitude) and of the decoded codec outputs above, so that the codec checks need no compiled
+                     reference where the tests run.
   oracle_cases.npz   outputs of the CPU oracle (sensor series + final-field checksums) for small seeded problems:
                      regression pins for the oracle itself and reference data for the GPU path on the GPU box, where
                      neither /root/reference nor a long oracle run is available.
@@ -84,6 +87,33 @@ def make_compress():
     print("wrote compress_ref.npz", {k: v.shape for k, v in out.items() if k.startswith("cfg0")})
 
 
+def make_compress_edges():
+    """compress_ref_edges.npz: the reference's 40-bit encodings of 2000 values spread over 21 decades (every 50th
+    pair zero) and its re-encodings of compress_ref.npz's decoded codec outputs (encode(decode(packed)))."""
+    orc.build(force=False)
+    if not os.path.exists(orc.REF_LIB_PATH):
+        raise SystemExit("oracle/_ref/libcompress_ref.so missing: run `make -C oracle ref` where the reference sources are")
+    L = C.CDLL(orc.REF_LIB_PATH)
+    L.cref_to40b.argtypes = [C.c_float, C.c_float, C.c_void_p, C.c_int]
+    g = np.load(os.path.join(HERE, "compress_ref.npz"))
+    rng = np.random.default_rng(7)
+    vals = (rng.standard_normal((2000, 2)) * 10.0 ** rng.uniform(-12, 9, size=(2000, 2))).astype(np.float32)
+    vals[::50] = 0.0
+    out = {"edges_in": vals}
+    for e in (138, 114):
+        packed = np.zeros((len(vals), 5), dtype=np.uint8)
+        for j in range(len(vals)):
+            L.cref_to40b(float(vals[j, 0]), float(vals[j, 1]), packed[j].ctypes.data, e)
+        out[f"edges{e}_packed"] = packed
+        vout = g[f"codec{e}_out"]
+        again = np.zeros((len(vout), 5), dtype=np.uint8)
+        for j in range(len(vout)):
+            L.cref_to40b(float(vout[j, 0]), float(vout[j, 1]), again[j].ctypes.data, e)
+        out[f"codec{e}_repacked"] = again
+    np.savez_compressed(os.path.join(HERE, "compress_ref_edges.npz"), **out)
+    print("wrote compress_ref_edges.npz", {k: v.shape for k, v in out.items()})
+
+
 def make_oracle_cases():
     out = {}
     for name, case in CASES.items():
@@ -105,5 +135,11 @@ def make_oracle_cases():
 
 
 if __name__ == "__main__":
-    make_compress()
-    make_oracle_cases()
+    # make_golden.py [compress] [edges] [oracle]: the named fixtures only (default: all of them)
+    which = sys.argv[1:] or ["compress", "edges", "oracle"]
+    if "compress" in which:
+        make_compress()
+    if "edges" in which:
+        make_compress_edges()
+    if "oracle" in which:
+        make_oracle_cases()
