@@ -303,10 +303,11 @@ KW_API kw_status kw_compute_velocity_shift(kw_ctx* ctx, int axis, float* spectru
  * Fused spectral pipeline (MI355X fast path; csrc/kw_fused.hip).  Each entry computes one whole stage of the step —
  * FFTs, spectral multiply and the real-space update — with hand-written FFT passes, so the gradients and spectra never
  * make an HBM round trip as separate arrays.  Same arithmetic as the kernels cited; supported when each of Nx, Ny, Nz
- * is one of 16 32 48 64 72 80 96 100 108 120 128 144 160 192 200 216 240 256 288 300 320 324 384 400 432 480 500 512
- * 576 600 640 648 768 1024 (kw_fused_supported says;
- * other grids use the rocFFT entry points above).  kappa / nabla / sourceKappa must first be imported into the
- * pipeline's padded row layout.
+ * is one of 16 32 48 64 72 80 96 100 108 112 120 128 140 144 160 168 180 192 196 200 216 224 240 252 256 280 288 300
+ * 320 324 336 360 384 392 400 420 432 448 480 500 504 512 540 560 576 600 640 648 672 700 720 756 768 784 800 840 864
+ * 896 900 960 1024 (2-D: Nx and Ny; with Nx one of 672 700 720 756 784 800 840 864 900 960 the Ny * Nz rows must also
+ * be a multiple of 16 — kw_fused_supported says; other grids use the rocFFT entry points above).  kappa / nabla /
+ * sourceKappa must first be imported into the pipeline's padded row layout.
  * ---------------------------------------------------------------------------------------------------------------- */
 /* Multi-GPU (new with this build; the reference is single-GPU, Readme.md:12-13): Z-slab decomposition with one
  * all-to-all transpose per 3-D FFT.  A context in slab mode holds nz = nz_global/nranks planes of every real array

@@ -43,6 +43,123 @@ def complete_2d(pr: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
     return out
 
 
+def kspace_real_operators(nx, ny, nz, dx, dy, dz, c_ref, dt, alpha_power=None) -> Dict[str, np.ndarray]:
+    """The reduced real k-space operators [nz][ny][nx/2+1] (KSpaceFirstOrderSolver.cpp:2404-2643): kappa, sourceKappa
+    and, given alpha_power, nabla1 / nabla2 (0 at k = 0)."""
+    fx = 0.5 - np.abs(0.5 - np.arange(nx // 2 + 1) / nx)
+    fy = 0.5 - np.abs(0.5 - np.arange(ny) / ny)
+    fz = 0.5 - np.abs(0.5 - np.arange(nz) / nz)
+    kk = np.sqrt((fz ** 2 / dz ** 2).reshape(-1, 1, 1) + (fy ** 2 / dy ** 2).reshape(1, -1, 1)
+                 + (fx ** 2 / dx ** 2).reshape(1, 1, -1))
+    arg = c_ref * dt * math.pi * kk
+    out = {}
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out["kappa"] = np.where(arg == 0.0, 1.0, np.sin(arg) / arg)
+    out["source_kappa"] = np.cos(arg)
+    if alpha_power is not None:
+        k2pi = 2.0 * math.pi * kk
+        with np.errstate(divide="ignore"):
+            n1 = np.power(k2pi, alpha_power - 2.0)
+            n2 = np.power(k2pi, alpha_power - 1.0)
+        n1[np.isinf(n1)] = 0.0
+        n2[np.isinf(n2)] = 0.0
+        out["nabla1"], out["nabla2"] = n1, n2
+    return out
+
+
+def fft_r2c(a: np.ndarray) -> np.ndarray:
+    """Forward R2C transform of a [nz][ny][nx] real array: [nz][ny][nx/2+1] complex."""
+    return np.fft.rfftn(a, axes=(0, 1, 2))
+
+
+def fft_c2r(c: np.ndarray, shape) -> np.ndarray:
+    """Unnormalised inverse (cuFFT C2R): the 1/N lives in the consumers."""
+    return np.fft.irfftn(c, s=tuple(shape), axes=(0, 1, 2)) * float(np.prod(shape))
+
+
+# ---- the stages of one step, as pure float64 functions: one per fused entry point of include/kwave_hip.h -------------
+# Arguments broadcast against [nz][ny][nx]: fields are arrays of that shape; media are arrays or scalars; the derivative
+# operators are complex vectors shaped (1, 1, nx/2+1), (1, ny, 1), (nz, 1, 1); kappa / nabla / sourceKappa are real
+# [nz][ny][nx/2+1].  Each returns new arrays and changes none of its arguments.
+
+def stage_velocity(p, u, dtrho, pml_sg, kappa, dd_pos):
+    """A1-A4 (kw_fused_velocity): u_i <- pml_sg_i (pml_sg_i u_i - dt/rho0_sg_i Fi(dd_i+ kappa F(p)) / N)."""
+    shape = np.shape(p)
+    d = 1.0 / float(np.prod(shape))
+    e = fft_r2c(p) * kappa
+    return [(u[a] * pml_sg[a] - d * fft_c2r(e * dd_pos[a], shape) * dtrho[a]) * pml_sg[a] for a in range(3)]
+
+
+def stage_initial_velocity(p, dtrho, kappa, dd_pos):
+    """A12 second half (kw_fused_initial_velocity): u_i = dt/rho0_sg_i Fi(dd_i+ kappa F(p)) / (2 N)."""
+    shape = np.shape(p)
+    d = 1.0 / float(np.prod(shape))
+    e = fft_r2c(p) * kappa
+    return [fft_c2r(e * dd_pos[a], shape) * dtrho[a] * d * 0.5 for a in range(3)]
+
+
+def stage_velocity_gradient(u, kappa, dd_neg, dudn=None):
+    """A6-A8 (kw_fused_velocity_gradient): du_i = Fi(dd_i- kappa F(u_i)) / N, times dudn_i on a non-uniform grid
+    (SolverCudaKernels.cu:1285-1301; the fused entry point leaves that scaling to the caller)."""
+    shape = np.shape(u[0])
+    kd = kappa / float(np.prod(shape))
+    du = [fft_c2r(fft_r2c(u[a]) * kd * dd_neg[a], shape) for a in range(3)]
+    if dudn is not None:
+        du = [du[a] * dudn[a] for a in range(3)]
+    return du
+
+
+def density_update(rho, du, pml, rho0, dt, nonlinear):
+    """A9: rho_i <- pml_i (pml_i rho_i - s du_i), s = dt (2 sum(rho) + rho0) nonlinear, dt rho0 linear."""
+    s = (2.0 * (rho[0] + rho[1] + rho[2]) + rho0) * dt if nonlinear else dt * rho0
+    return [pml[a] * (pml[a] * rho[a] - s * du[a]) for a in range(3)]
+
+
+def pressure_terms(rho, du, rho0, bona, nonlinear):
+    """computePressureTerms{Linear,Nonlinear}: (density sum S, first term of the pressure sum, rho0 sum(du)); the first
+    term is S linear, S + BonA S^2 / (2 rho0) nonlinear."""
+    S = rho[0] + rho[1] + rho[2]
+    first = (bona * S * S / (2.0 * rho0) + S) if nonlinear else S
+    return S, first, rho0 * (du[0] + du[1] + du[2])
+
+
+def equation_of_state(rho, c2, rho0, bona, nonlinear):
+    """A11 lossless (sumPressure{Nonlinear,Linear}Lossless): p = c2 (S + BonA S^2 / (2 rho0)) | c2 S."""
+    S = rho[0] + rho[1] + rho[2]
+    return c2 * (S + bona * S * S / (2.0 * rho0)) if nonlinear else c2 * S
+
+
+def stage_density(u, rho, pml, rho0, dt, kappa, dd_neg, nonlinear, terms=0, bona=0.0, c2=None):
+    """A6-A9 and the pressure terms of A11 (kw_fused_density).  Returns {"du", "rho", "t"}: "t" is what the entry point
+    writes to t0..t2 — terms 1: [sum rho, rho0 sum du]; 2: [sum rho, nonlinear term, rho0 sum du]; 3: [p] (lossless
+    equation of state; c2 an input)."""
+    du = stage_velocity_gradient(u, kappa, dd_neg)
+    rho_n = density_update(rho, du, pml, rho0, dt, nonlinear)
+    t = []
+    if terms in (1, 2):
+        S, first, vgt = pressure_terms(rho_n, du, rho0, bona, terms == 2)
+        t = [S, vgt] if terms == 1 else [S, first, vgt]
+    elif terms == 3:
+        t = [equation_of_state(rho_n, c2, rho0, bona, nonlinear)]
+    return {"du": du, "rho": rho_n, "t": t}
+
+
+def stage_absorption_pressure(first, vel_grad_term, density_sum, nabla1, nabla2, c2, tau, eta):
+    """A11 absorbing, after the terms (kw_fused_absorption_pressure):
+    p = c2 (first + (tau Fi(nabla1 F(rho0 sum du)) - eta Fi(nabla2 F(sum rho))) / N)."""
+    shape = np.shape(density_sum)
+    d = 1.0 / float(np.prod(shape))
+    tau_term = fft_c2r(fft_r2c(vel_grad_term) * nabla1, shape)
+    eta_term = fft_c2r(fft_r2c(density_sum) * nabla2, shape)
+    return c2 * (first + d * (tau_term * tau - eta_term * eta))
+
+
+def stage_scale_source(s, source_kappa):
+    """FFT part of scaleSource (kw_fused_scale_source): Fi(sourceKappa F(s)) / N."""
+    shape = np.shape(s)
+    return fft_c2r(fft_r2c(s) * source_kappa, shape) / float(np.prod(shape))
+
+
 class NumpySim:
     def __init__(self, pr: Dict[str, np.ndarray]):
         pr = complete_2d(pr)
@@ -79,24 +196,12 @@ class NumpySim:
                        f8("pml_z_sgz").reshape(-1, 1, 1)]
         # generators (KSpaceFirstOrderSolver.cpp:2404-2643)
         dx, dy, dz, c_ref = (_sc(pr[k]) for k in ("dx", "dy", "dz", "c_ref"))
-        fx = 0.5 - np.abs(0.5 - np.arange(nx // 2 + 1) / nx)
-        fy = 0.5 - np.abs(0.5 - np.arange(ny) / ny)
-        fz = 0.5 - np.abs(0.5 - np.arange(nz) / nz)
-        kk = np.sqrt((fz ** 2 / dz ** 2).reshape(-1, 1, 1) + (fy ** 2 / dy ** 2).reshape(1, -1, 1)
-                     + (fx ** 2 / dx ** 2).reshape(1, 1, -1))
-        arg = c_ref * self.dt * math.pi * kk
-        with np.errstate(divide="ignore", invalid="ignore"):
-            self.kappa = np.where(arg == 0.0, 1.0, np.sin(arg) / arg)
-        self.source_kappa = np.cos(arg)
+        gen = kspace_real_operators(nx, ny, nz, dx, dy, dz, c_ref, self.dt,
+                                    _sc(pr["alpha_power"]) if self.absorbing else None)
+        self.kappa, self.source_kappa = gen["kappa"], gen["source_kappa"]
         if self.absorbing:
             y = _sc(pr["alpha_power"])
-            k2pi = 2.0 * math.pi * kk
-            with np.errstate(divide="ignore"):
-                n1 = np.power(k2pi, y - 2.0)
-                n2 = np.power(k2pi, y - 1.0)
-            n1[np.isinf(n1)] = 0.0
-            n2[np.isinf(n2)] = 0.0
-            self.nabla1, self.nabla2 = n1, n2
+            self.nabla1, self.nabla2 = gen["nabla1"], gen["nabla2"]
             a_np = 100.0 * (1.0e-6 / (2.0 * math.pi)) ** y / (20.0 * math.log10(math.e))
             alpha = f8("alpha_coeff") if pr["alpha_coeff"].size > 1 else _sc(pr["alpha_coeff"])
             a2 = 2.0 * a_np * alpha
@@ -112,11 +217,10 @@ class NumpySim:
 
     # helpers
     def F(self, a):
-        return np.fft.rfftn(a, axes=(0, 1, 2))
+        return fft_r2c(a)
 
     def Fi(self, c):
-        # unnormalised inverse (cuFFT C2R), the 1/N lives in the consumers
-        return np.fft.irfftn(c, s=self.shape, axes=(0, 1, 2)) * self.N
+        return fft_c2r(c, self.shape)
 
     def _src_values(self, inp, n, many):
         inp = np.asarray(inp, dtype=np.float64).reshape(-1)
@@ -125,16 +229,13 @@ class NumpySim:
     def _scaled(self, inp, idx, many):
         T = np.zeros(self.N)
         T[idx] = self._src_values(inp, idx.size, many)
-        S = self.F(T.reshape(self.shape)) * self.source_kappa / self.N
-        return self.Fi(S)
+        return stage_scale_source(T.reshape(self.shape), self.source_kappa)
 
     def step(self):
-        pr, d = self.pr, 1.0 / self.N
+        pr = self.pr
+        dd_pos = (self.ddx_pos, self.ddy_pos, self.ddz_pos)
         # A1-A4
-        e = self.F(self.p) * self.kappa
-        g = [self.Fi(e * self.ddx_pos), self.Fi(e * self.ddy_pos), self.Fi(e * self.ddz_pos)]
-        for a in range(3):
-            self.u[a] = (self.u[a] * self.pml_sg[a] - d * g[a] * self.dtrho[a]) * self.pml_sg[a]
+        self.u = stage_velocity(self.p, self.u, self.dtrho, self.pml_sg, self.kappa, dd_pos)
         # A5
         names = ("ux", "uy", "uz")
         if any(int(_sc(pr.get(f"{nm}_source_flag", 0))) for nm in names) or int(_sc(pr.get("transducer_source_flag", 0))):
@@ -157,18 +258,9 @@ class NumpySim:
                 sig = np.asarray(pr["transducer_source_input"], dtype=np.float64).reshape(-1)
                 np.add.at(self.u[0].reshape(-1), idx, sig[dm + self.t])
         # A6-A8
-        kd = self.kappa * d
-        self.du[0] = self.Fi(self.F(self.u[0]) * kd * self.ddx_neg)
-        self.du[1] = self.Fi(self.F(self.u[1]) * kd * self.ddy_neg)
-        self.du[2] = self.Fi(self.F(self.u[2]) * kd * self.ddz_neg)
-        if self.dudn is not None:  # SolverCudaKernels.cu:1285-1301
-            self.du = [self.du[a] * self.dudn[a] for a in range(3)]
+        self.du = stage_velocity_gradient(self.u, self.kappa, (self.ddx_neg, self.ddy_neg, self.ddz_neg), self.dudn)
         # A9
-        if self.nonlinear:
-            s = (2.0 * (self.rho[0] + self.rho[1] + self.rho[2]) + self.rho0) * self.dt
-        else:
-            s = self.dt * self.rho0
-        self.rho = [self.pml[a] * (self.pml[a] * self.rho[a] - s * self.du[a]) for a in range(3)]
+        self.rho = density_update(self.rho, self.du, self.pml, self.rho0, self.dt, self.nonlinear)
         # A10
         if int(_sc(pr.get("p_source_flag", 0))) > self.t:
             idx = np.asarray(pr["p_source_index"], dtype=np.int64).reshape(-1) - 1
@@ -187,27 +279,18 @@ class NumpySim:
                     else:
                         np.add.at(flat, idx, v)
         # A11
-        S = self.rho[0] + self.rho[1] + self.rho[2]
         if not self.absorbing:
-            if self.nonlinear:
-                self.p = self.c2 * (S + self.bona * S * S / (2.0 * self.rho0))
-            else:
-                self.p = self.c2 * S
+            self.p = equation_of_state(self.rho, self.c2, self.rho0, self.bona, self.nonlinear)
         else:
-            D = self.du[0] + self.du[1] + self.du[2]
-            tau_term = self.Fi(self.F(self.rho0 * D) * self.nabla1)
-            eta_term = self.Fi(self.F(S) * self.nabla2)
-            base = (self.bona * S * S / (2.0 * self.rho0) + S) if self.nonlinear else S
-            self.p = self.c2 * (base + d * (tau_term * self.tau - eta_term * self.eta))
+            S, first, vgt = pressure_terms(self.rho, self.du, self.rho0, self.bona, self.nonlinear)
+            self.p = stage_absorption_pressure(first, vgt, S, self.nabla1, self.nabla2, self.c2, self.tau, self.eta)
         # A12
         if self.t == 0 and int(_sc(pr.get("p0_source_flag", 0))) == 1:
             p0 = np.asarray(pr["p0_source_input"], dtype=np.float64)
             self.p = p0.copy()
             ndim = 2 if self.nz == 1 else 3  # SolverCudaKernels.cu:873-876 dimScalingFactor
             self.rho = [p0 / (ndim * self.c2) if a < ndim else np.zeros_like(p0) for a in range(3)]
-            e = self.F(self.p) * self.kappa
-            g = [self.Fi(e * self.ddx_pos), self.Fi(e * self.ddy_pos), self.Fi(e * self.ddz_pos)]
-            self.u = [g[a] * self.dtrho[a] * d * 0.5 for a in range(3)]
+            self.u = stage_initial_velocity(self.p, self.dtrho, self.kappa, dd_pos)
         self.t += 1
 
 

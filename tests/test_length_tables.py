@@ -1,6 +1,6 @@
 """Consistency of the fast path's line-length tables (CPU only: parses the sources): every length of KW_FUSED_LENGTHS has a
-factor pair with both factors register-DFT sizes, the tuning tables name only listed lengths, and README / DESIGN quote the
-same list."""
+factor pair with both factors register-DFT sizes, the tuning tables name only listed lengths, and README / DESIGN / the
+public header quote the same list."""
 import os
 import re
 
@@ -54,3 +54,9 @@ def test_tuning_tables_and_documents_name_listed_lengths_only():
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     block = re.search(r"each of Nx, Ny, Nz ∈ \{([\d,\s]+)\}", design).group(1)
     assert [int(x) for x in block.replace(",", " ").split()] == sorted(listed)
+    header = open(os.path.join(ROOT, "include", "kwave_hip.h")).read()
+    block = re.search(r"supported when each of Nx, Ny, Nz\n \* is one of ([\d\s*]+?)\(2-D", header).group(1)
+    assert [int(x) for x in block.replace("*", " ").split()] == sorted(listed)
+    no_tail_listed = {int(x) for x in re.findall(r"case (\d+):", no_tail)}
+    block = re.search(r"with Nx one of ([\d\s*]+?) the Ny \* Nz rows", header).group(1)
+    assert [int(x) for x in block.replace("*", " ").split()] == sorted(no_tail_listed)
