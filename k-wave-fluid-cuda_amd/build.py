@@ -20,7 +20,14 @@ INCLUDE = os.path.join(ROOT, "include")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 HIPCC = os.path.join(ROCM, "bin", "hipcc")
 
-FUSED_TUS = (7, 8, 0, 2, 1, 5, 3, 6, 4)  # passes over kw_fused.hip, slowest first
+# the code objects that take longest to compile, started first (the fused pipeline's kernel sets: one per line length;
+# measured from scratch, 8 jobs side by side: 185 s down to 65 s in this order, every other object at most 11 s)
+SLOWEST_FIRST = ("kw_fused_xinv_other.hip", "kw_fused_main.hip", "kw_fused_xinv_density_plain_tail.hip",
+                 "kw_fused_xinv_density_chain_tail.hip", "kw_fused_xinv_other_tail.hip", "kw_fused_xinv_density_plain_long.hip",
+                 "kw_fused_xinv_density_chain_long.hip", "kw_fused_xinv_density_chain_short.hip",
+                 "kw_fused_xinv_density_plain_short.hip")
+# the fused pipeline's device code, which each of its code objects (kw_fused_*.hip) includes: no code object itself
+INCLUDED_ONLY = ("kw_fused.hip",)
 HIP_LIB = os.path.join(LIB_DIR, "libkwave_hip.so")
 HOST_LIB = os.path.join(LIB_DIR, "libkwave_host.so")
 
@@ -40,18 +47,24 @@ def _run(cmd):
     return r.stdout
 
 
+def _hip_sources():
+    """the csrc/*.hip that are code objects, slowest to compile first"""
+    rank = {name: i for i, name in enumerate(SLOWEST_FIRST)}
+    srcs = [s for s in glob.glob(os.path.join(CSRC, "*.hip")) if os.path.basename(s) not in INCLUDED_ONLY]
+    return sorted(srcs, key=lambda s: (rank.get(os.path.basename(s), len(rank)), s))
+
+
 def build_hip(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(LIB_DIR, exist_ok=True)
-    srcs = sorted(glob.glob(os.path.join(CSRC, "*.hip")))
-    deps = srcs + glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(INCLUDE, "*.h"))
-    if force or _newer(HIP_LIB, deps):
+    srcs = _hip_sources()
+    headers = glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(INCLUDE, "*.h")) + \
+        [os.path.join(CSRC, name) for name in INCLUDED_ONLY]
+    if force or _newer(HIP_LIB, srcs + headers):
         objs, jobs = [], []
-        # kw_fused.hip is compiled in five passes (its x-inverse epilogue kernels in four of them, see the file's header)
-        units = [(s, tu) for s in srcs for tu in (FUSED_TUS if os.path.basename(s) == "kw_fused.hip" else (None,))]
-        for s, tu in units:
-            o = os.path.join(LIB_DIR, os.path.basename(s) + (".o" if not tu else f".tu{tu}.o"))
-            if force or _newer(o, [s] + [d for d in deps if d.endswith(".h")]):
-                extra = os.environ.get("KW_HIPCC_EXTRA", "").split() + ([f"-DKW_FUSED_TU={tu}"] if tu else [])
+        for s in srcs:
+            o = os.path.join(LIB_DIR, os.path.basename(s) + ".o")
+            if force or _newer(o, [s] + headers):
+                extra = os.environ.get("KW_HIPCC_EXTRA", "").split()
                 # -fno-slp-vectorize: packed-f32 pairing buys nothing here (same instruction count, more moves; measured +0.6 %)
                 cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
                        "-fno-slp-vectorize"] + extra + [
@@ -60,7 +73,7 @@ def build_hip(force: bool = False, verbose: bool = False) -> str:
                     cmd.insert(1, "-Rpass-analysis=kernel-resource-usage")
                 jobs.append(cmd)
             objs.append(o)
-        # the translation units compile side by side (kw_fused.hip alone takes minutes: one kernel set per line length)
+        # the translation units compile side by side (the fused pipeline's take minutes: one kernel set per line length)
         with concurrent.futures.ThreadPoolExecutor(max_workers=max(1, min(8, len(jobs)))) as pool:
             for out in pool.map(_run, jobs):
                 if verbose:
@@ -75,15 +88,13 @@ def build_hip_variant(name: str, extra_flags, only_length: int = 256) -> str:
     box): the fused pipeline restricted to one line length (compiles in seconds) plus extra compiler flags."""
     out_dir = os.path.join(ROOT, "ab", name)
     os.makedirs(out_dir, exist_ok=True)
-    srcs = sorted(glob.glob(os.path.join(CSRC, "*.hip")))
-    units = [(s, tu) for s in srcs for tu in (FUSED_TUS if os.path.basename(s) == "kw_fused.hip" else (None,))]
     jobs, objs = [], []
-    for s, tu in units:
-        o = os.path.join(out_dir, os.path.basename(s) + (".o" if not tu else f".tu{tu}.o"))
+    for s in _hip_sources():
+        o = os.path.join(out_dir, os.path.basename(s) + ".o")
         cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-fno-slp-vectorize"]
         cmd += list(extra_flags) + ([f"-DKW_FUSED_ONLY={only_length}"] if only_length else [])
-        cmd += ([f"-DKW_FUSED_TU={tu}"] if tu else []) + ["-I" + INCLUDE, "-I" + CSRC, "-I" + os.path.join(ROOT, "include"),
-                                                          "-I" + os.path.join(ROCM, "include"), "-c", s, "-o", o]
+        cmd += ["-I" + INCLUDE, "-I" + CSRC, "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROCM, "include"),
+                "-c", s, "-o", o]
         jobs.append(cmd)
         objs.append(o)
     with concurrent.futures.ThreadPoolExecutor(max_workers=8) as pool:

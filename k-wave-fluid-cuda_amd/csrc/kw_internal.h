@@ -55,7 +55,7 @@ struct kw_ctx
   kw_fft_plan  r2c_1d[3], c2r_1d[3];
   void*        fft_work       = nullptr; // one shared work buffer, sized for the largest plan
   size_t       fft_work_bytes = 0;
-  // fused spectral pipeline (kw_fused.hip): private padded spectral scratch + per-axis twiddle tables
+  // fused spectral pipeline (kw_fused*.hip): private padded spectral scratch + per-axis twiddle tables
   struct fused_plan
   {
     bool     ready = false;

@@ -1,29 +1,31 @@
 #!/usr/bin/env python3
-"""Per-kernel instruction mix of kw_fused.hip (gfx950), from hipcc -S.  Offline: no GPU needed.
+"""Per-kernel instruction mix of the fused pipeline's code objects (csrc/kw_fused_*.hip, gfx950), from hipcc -S.  Offline:
+no GPU needed.
 
   python tools/isa_stats.py [extra hipcc flags...]     e.g.  -DKW_PK=1
 """
 import collections
+import glob
 import os
 import re
 import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "k-wave-fluid-cuda_amd", "csrc", "kw_fused.hip")
+CSRC = os.path.join(ROOT, "k-wave-fluid-cuda_amd", "csrc")
 
 
 def main():
     extra = sys.argv[1:]
     out = os.environ.get("KW_ISA_OUT", "/tmp/kw_fused_isa.s")
-    # the file is built in five passes (KW_FUSED_TU = 0 ... 4: see its header); all are listed
+    # every code object of the pipeline (see kw_fused.hip); all are listed
     procs, outs = [], []
-    for tu in (0, 1, 2, 3, 4):
-        o = f"{out}.tu{tu}"
+    for src in sorted(glob.glob(os.path.join(CSRC, "kw_fused_*.hip"))):
+        o = f"{out}.{os.path.basename(src)}"
         outs.append(o)
         procs.append(subprocess.Popen(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize",
                                        "--cuda-device-only", "-S", "-I" + os.path.join(ROOT, "include"),
-                                       "-I" + os.path.dirname(SRC), SRC, "-o", o, f"-DKW_FUSED_TU={tu}"] + extra))
+                                       "-I" + CSRC, src, "-o", o] + extra))
     for pr in procs:
         if pr.wait() != 0:
             raise SystemExit("hipcc failed")

@@ -2,6 +2,7 @@
 """Registers / LDS / occupancy of the fused kernels at one line length, from the compiler's own remarks
 (-Rpass-analysis=kernel-resource-usage) on a KW_FUSED_ONLY build:  python tools/kernel_resources.py 500"""
 import concurrent.futures
+import glob
 import os
 import re
 import subprocess
@@ -12,12 +13,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "k-wave-fluid-cuda_amd", "csrc")
 
 
-def compile_tu(args):
-    length, tu, tmp, extra = args
+def compile_one(args):
+    length, src, tmp, extra = args
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
            "-fno-slp-vectorize", f"-DKW_FUSED_ONLY={length}", "-Rpass-analysis=kernel-resource-usage", "-I" + CSRC,
-           "-I" + os.path.join(ROOT, "include"), "-I/opt/rocm/include", "-c", os.path.join(CSRC, "kw_fused.hip"), "-o",
-           os.path.join(tmp, f"f{tu}.o")] + ([f"-DKW_FUSED_TU={tu}"] if tu else []) + extra
+           "-I" + os.path.join(ROOT, "include"), "-I/opt/rocm/include", "-c", src, "-o",
+           os.path.join(tmp, os.path.basename(src) + ".o")] + extra
     return subprocess.run(cmd, capture_output=True, text=True).stderr
 
 
@@ -25,7 +26,8 @@ def main():
     length = int(sys.argv[1]) if len(sys.argv) > 1 else 256
     extra = sys.argv[2:]
     with tempfile.TemporaryDirectory() as tmp, concurrent.futures.ThreadPoolExecutor(8) as pool:
-        texts = list(pool.map(compile_tu, [(length, tu, tmp, extra) for tu in (0, 1, 2, 3, 4, 5, 6, 7, 8)]))
+        srcs = sorted(glob.glob(os.path.join(CSRC, "kw_fused_*.hip")))  # the fused pipeline's code objects
+        texts = list(pool.map(compile_one, [(length, src, tmp, extra) for src in srcs]))
     pat = re.compile(r"Function Name: (\S+).*?VGPRs: (\d+).*?AGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+).*?"
                      r"Occupancy \[waves/SIMD\]: (\d+).*?LDS Size \[bytes/block\]: (\d+)", re.S)
     for txt in texts:
