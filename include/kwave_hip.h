@@ -255,7 +255,8 @@ KW_API kw_status kw_compute_pressure_gradient(kw_ctx* ctx, float* fft_x, float* 
 KW_API kw_status kw_compute_velocity_gradient(kw_ctx* ctx, float* fft_x, float* fft_y, float* fft_z,
                                               const float* kappa, const float* ddx_k_shift_neg,
                                               const float* ddy_k_shift_neg, const float* ddz_k_shift_neg);
-/* computeVelocityGradientShiftNonuniform (.cuh:293, .cu:1285-1320): du?d? *= d?ud?n[coord] on a non-uniform grid */
+/* computeVelocityGradientShiftNonuniform (.cuh:293, .cu:1285-1320): du?d? *= d?ud?n[coord] on a non-uniform grid;
+ * KW_ERR_INVALID when Ny > 65535 */
 KW_API kw_status kw_compute_velocity_gradient_shift_nonuniform(kw_ctx* ctx, float* duxdx, float* duydy, float* duzdz,
                                                                const float* dxudxn, const float* dyudyn,
                                                                const float* dzudzn);

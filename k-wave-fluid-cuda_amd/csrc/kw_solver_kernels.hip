@@ -931,7 +931,9 @@ kw_status kw_compute_velocity_gradient_shift_nonuniform(kw_ctx* ctx, float* dux,
   KW_PROF(ctx, "compute_velocity_gradient_shift_nonuniform");
   KW_REQUIRE(dux && duy && duz && nx && ny && nz);
   const kw_constants& c = ctx->c;
-  KW_REQUIRE(static_cast<uint64_t>(c.ny) * c.nz <= 65535u * 65535u);
+  // the chunked launch below needs at least one whole z-plane of rows (ny <= 65535) per launch: a taller plane would
+  // give zstep == 0, i.e. launches with no rows
+  KW_REQUIRE(c.ny <= 65535u);
   // rows on grid.y would overflow 65535 for big grids: fold rows into grid.x/y = (x blocks, rows) only when they fit
   const uint32_t rows = c.ny * c.nz;
   if (rows <= 65535u)

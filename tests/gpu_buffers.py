@@ -1,0 +1,59 @@
+"""Device buffers and constants shared by the kernel-level GPU tests (a plain module, imported by name from tests/).
+
+Guarded: a device array between GUARD-byte bands of 0xFF bytes (NaN as float32).  A kernel that writes outside the
+array fails the guard check on read(); one that reads outside it turns its result into NaN.  `offset` moves the
+array's start by that many bytes past the 256-byte aligned interior, to hand a kernel a misaligned pointer.
+"""
+import numpy as np
+
+GUARD = 4096
+
+# scalar media of the Constants (arbitrary, O(1)); the operators are generated with dx = dy = dz = 1, c_ref = 1
+DT, RHO0, C2, BONA, TAU, ETA = 0.7, 1.3, 2.1, 0.6, 0.8, 0.45
+DT_RHO0_SG = (0.9, 1.1, 0.75)
+
+
+def set_constants(dev, nx, ny, nz, **extra):
+    """kw_set_constants for an nx x ny x nz grid with the scalar media above; `extra` sets further fields (sources)"""
+    from kwave_amd import capi
+    k = capi.Constants()
+    k.nx, k.ny, k.nz, k.n_elements = nx, ny, nz, nx * ny * nz
+    k.nx_complex, k.ny_complex, k.nz_complex = nx // 2 + 1, ny, nz
+    k.n_elements_complex = (nx // 2 + 1) * ny * nz
+    k.fft_divider = 1.0 / (nx * ny * nz)
+    k.fft_divider_x, k.fft_divider_y, k.fft_divider_z = 1.0 / nx, 1.0 / ny, 1.0 / nz
+    k.dt, k.dt_by_2, k.c2, k.rho0, k.dt_rho0 = DT, DT / 2, C2, RHO0, DT * RHO0
+    k.dt_rho0_sgx, k.dt_rho0_sgy, k.dt_rho0_sgz = DT_RHO0_SG
+    k.b_on_a, k.absorb_tau, k.absorb_eta = BONA, TAU, ETA
+    for name, v in extra.items():
+        setattr(k, name, v)
+    dev.set_constants(k)
+    return k
+
+
+class Guarded:
+    """A device array between GUARD-byte bands of 0xFF bytes; .ptr is the 256-byte aligned interior plus `offset`."""
+
+    def __init__(self, dev, host, offset=0, dtype=np.float32):
+        host = np.ascontiguousarray(host, dtype=dtype)
+        self.dev, self.shape, self.dtype, self.n, self.offset = dev, host.shape, host.dtype, host.nbytes, offset
+        self.total = GUARD + (offset + self.n + 255) // 256 * 256 + GUARD
+        self.buf = dev.empty(self.total, np.uint8)
+        self.buf.fill_bytes(0xFF)
+        self.ptr = self.buf.ptr + GUARD + offset
+        self.write(host)
+
+    def write(self, host):
+        host = np.ascontiguousarray(host, dtype=self.dtype)
+        assert host.nbytes == self.n
+        from kwave_amd import capi
+        capi.check(self.dev.L.kw_memcpy_h2d(self.dev.ctx, self.ptr, host.ctypes.data, self.n))
+
+    def read(self):
+        raw = self.buf.download()
+        lo, hi = raw[:GUARD + self.offset], raw[GUARD + self.offset + self.n:]
+        assert np.all(lo == 0xFF) and np.all(hi == 0xFF), "guard band overwritten"
+        return raw[GUARD + self.offset:GUARD + self.offset + self.n].view(self.dtype).reshape(self.shape).copy()
+
+    def free(self):
+        self.buf.free()

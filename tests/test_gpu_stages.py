@@ -32,6 +32,7 @@ from conftest import ROOT
 
 sys.path.insert(0, ROOT)
 from oracle import kwave_np as knp  # noqa: E402
+from gpu_buffers import BONA, C2, DT, DT_RHO0_SG, ETA, RHO0, TAU, Guarded, set_constants  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -39,14 +40,10 @@ TOL_WHOLE = 2.2e-6
 TOL_LINE = 5e-6
 TOL_UPPER = 2.1e-6
 
-GUARD = 4096
 CHAIN_U, P_IN_SCRATCH = 1, 2           # kw_fused_velocity flags
 U_IN_SCRATCH, CHAIN_TERMS = 1, 2       # kw_fused_density / kw_fused_velocity_gradient flags
 TERMS_IN_SCRATCH, CHAIN_P = 1, 2       # kw_fused_absorption_pressure flags
 
-# scalar media of the Constants (arbitrary, O(1)); the operators are generated with dx = dy = dz = 1, c_ref = 1
-DT, RHO0, C2, BONA, TAU, ETA = 0.7, 1.3, 2.1, 0.6, 0.8, 0.45
-DT_RHO0_SG = (0.9, 1.1, 0.75)
 ALPHA_POWER = 1.5
 
 
@@ -65,46 +62,6 @@ AXIS_GRIDS = list(dict.fromkeys([(n, 16, 16) for n in LENGTHS] + [(16, n, 16) fo
 TWO_D_NY = 108  # no multiple of 16, 20, 24 or 32: every x tile size ends in a masked tile
 TWO_D_GRIDS = [(n, TWO_D_NY, 1) for n in LENGTHS if n not in NO_TAIL]
 MIXED_GRIDS = [(140, 252, 48), (864, 16, 48), (100, 196, 72)]
-
-
-# ---- device helpers ---------------------------------------------------------------------------------------------------
-def set_constants(dev, nx, ny, nz):
-    from kwave_amd import capi
-    k = capi.Constants()
-    k.nx, k.ny, k.nz, k.n_elements = nx, ny, nz, nx * ny * nz
-    k.nx_complex, k.ny_complex, k.nz_complex = nx // 2 + 1, ny, nz
-    k.n_elements_complex = (nx // 2 + 1) * ny * nz
-    k.fft_divider = 1.0 / (nx * ny * nz)
-    k.fft_divider_x, k.fft_divider_y, k.fft_divider_z = 1.0 / nx, 1.0 / ny, 1.0 / nz
-    k.dt, k.dt_by_2, k.c2, k.rho0, k.dt_rho0 = DT, DT / 2, C2, RHO0, DT * RHO0
-    k.dt_rho0_sgx, k.dt_rho0_sgy, k.dt_rho0_sgz = DT_RHO0_SG
-    k.b_on_a, k.absorb_tau, k.absorb_eta = BONA, TAU, ETA
-    dev.set_constants(k)
-
-
-class Guarded:
-    """A float32 device array between GUARD-byte bands of 0xFF bytes; .ptr is the 256-byte aligned interior."""
-
-    def __init__(self, dev, host):
-        host = np.ascontiguousarray(host, dtype=np.float32)
-        self.dev, self.shape, self.n = dev, host.shape, host.nbytes
-        self.total = GUARD + (self.n + 255) // 256 * 256 + GUARD
-        self.buf = dev.empty(self.total, np.uint8)
-        self.buf.fill_bytes(0xFF)
-        self.ptr = self.buf.ptr + GUARD
-        self.write(host)
-
-    def write(self, host):
-        host = np.ascontiguousarray(host, dtype=np.float32)
-        assert host.nbytes == self.n
-        from kwave_amd import capi
-        capi.check(self.dev.L.kw_memcpy_h2d(self.dev.ctx, self.ptr, host.ctypes.data, self.n))
-
-    def read(self):
-        raw = self.buf.download()
-        lo, hi = raw[:GUARD], raw[GUARD + self.n:]
-        assert np.all(lo == 0xFF) and np.all(hi == 0xFF), "guard band overwritten"
-        return raw[GUARD:GUARD + self.n].view(np.float32).reshape(self.shape).copy()
 
 
 def _g(x):
