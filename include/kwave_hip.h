@@ -515,6 +515,33 @@ KW_API kw_status kw_q_term_sum(kw_ctx* ctx, float* out, const float* a, const fl
 /* postProcessingRms (.cuh:103-105, .cu:359-378) */
 KW_API kw_status kw_post_processing_rms(kw_ctx* ctx, float* sampling_buffer, float scaling_coeff, uint64_t n_samples);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Weighted transducer arrays (new with this build): an array element of k-Wave's kWaveArray is a set of grid points
+ * with band-limited interpolation weights.  Both directions are a sparse matrix in CSR form: ptr[0..rows] are 0-based
+ * uint32 row offsets into entries[], and an entry is a 0-based column with its weight, read as one 8-byte load.  Both
+ * kernels only gather, so every output value is a fixed function of the CSR and the input: the same bits on every run.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct kw_csr_entry
+{
+  uint32_t col;    /* weighted source: element (0 .. n_elements-1); weighted sensor: linear grid index */
+  float    weight;
+} kw_csr_entry;
+#define KW_ELEMENT_CHUNK 1024u /* entries per block of kw_sample_elements */
+/* Weighted pressure source: the per-point series row of time step t,
+ *   row[k] = sum over the entries j of row k, in CSR order, of weight_j * element_input[t * n_elements + col_j]
+ * accumulated with fp32 fma from 0.  One thread per point.  ptr has n_points + 1 entries. */
+KW_API kw_status kw_element_source_row(kw_ctx* ctx, float* row, const float* element_input, const uint32_t* ptr,
+                                       const kw_csr_entry* entries, uint32_t n_points, uint32_t n_elements,
+                                       uint64_t time_index);
+/* Weighted pressure sensor: out[e] = sum over the entries j of row e of weight_j * p[col_j], for e < n_elements.
+ * Row e is cut into ceil(len_e / KW_ELEMENT_CHUNK) chunks; chunk_ptr[0..n_elements] are the 0-based prefix sums of those
+ * counts (computed once by the caller, n_chunks = chunk_ptr[n_elements]) and partials holds n_chunks floats of workspace.
+ * One block per chunk: per-lane fma partial sums, then a fixed wave64 + LDS tree; a second launch adds an element's chunk
+ * partials in chunk order.  No atomics.  An empty row gives 0. */
+KW_API kw_status kw_sample_elements(kw_ctx* ctx, float* out, const float* p, const uint32_t* ptr,
+                                    const kw_csr_entry* entries, uint32_t n_elements, uint64_t nnz,
+                                    const uint32_t* chunk_ptr, uint32_t n_chunks, float* partials);
+
 #ifdef __cplusplus
 }
 #endif

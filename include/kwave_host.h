@@ -32,6 +32,15 @@ typedef struct kwh_dataset
   uint64_t    nx, ny, nz; /* (x,y,z) sizes = HDF5 dims reversed; complex datasets have the doubled x size halved here */
 } kwh_dataset;
 
+/* Weighted pressure source (new with this build; k-Wave's kWaveArray): instead of p_source_input, the datasets
+ *   p_source_element_input  float  (1, p_source_flag, E)  one signal per element
+ *   p_source_element_ptr    uint64 (1, 1, Npts + 1)       0-based CSR offsets, row k = point k of p_source_index
+ *   p_source_element_index  uint64 (1, 1, nnz)            1-based element number of each entry
+ *   p_source_element_weight float  (1, 1, nnz)            weight of each entry
+ * make point k receive v_k(t) = sum_j weight_j * signal[t][element_j] (fp32 fma in CSR order); p_source_mode then applies
+ * as to a p_source_many = 1 source with series row t = v(t).  p_source_input must be absent and p_source_many, if
+ * given, 1.  kwh_create checks every CSR (offsets, counts, element and grid index ranges) and names the dataset. */
+
 /* what the reference takes from the command line for the loop (CommandLineParameters.cpp:264-292) */
 typedef struct kwh_options
 {
@@ -82,6 +91,11 @@ typedef struct kwh_options
   const char* rccl_library;   /* optional library name / path for the RCCL binding (kw_comm_init_with); NULL = default */
   float    p2p_emulate_link_gbs;   /* > 0 with comm_p2p: link model instead of peers (kw_comm_p2p_emulate; schedule studies */
   float    p2p_emulate_latency_us; /*   with ONE rank of slab_ranks on a one-GPU machine, tools/emulate_rank.py) */
+  int32_t  p_elements;        /* --p_elements: weighted sensor, stream "p_elements" of (Nt - s) rows of E values,
+                                 p_elements[t][e] = sum_j sensor_element_weight[j] * p[sensor_element_index[j]] over row e
+                                 of the CSR (sensor_element_ptr: E + 1 0-based offsets; sensor_element_index: 1-based
+                                 linear grid indices).  Independent of sensor_mask_*.  Without the three datasets,
+                                 kwh_create fails. */
 } kwh_options;
 /* gathers `bytes` bytes of every rank, in rank order, into all (nranks * bytes); the same result on every rank; 0 = ok.
  * Any transport the launcher has will do: MPI_Allgather, torch.distributed.all_gather on a gloo group, files. */

@@ -171,7 +171,27 @@ _SIG: Dict[str, list] = {
     "kw_intensity_avg": [_P, _P, _P, _P, _U64, _U64],
     "kw_q_term_sum": [_P, _P, _P, _P, _P, _U64],
     "kw_divide": [_P, _P, C.c_float, _U64],
+    "kw_element_source_row": [_P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _U64],
+    "kw_sample_elements": [_P, _P, _P, _P, _P, C.c_uint32, _U64, _P, C.c_uint32, _P],
 }
+
+ELEMENT_CHUNK = 1024  # KW_ELEMENT_CHUNK
+
+
+def csr_entries(cols, weights) -> np.ndarray:
+    """kw_csr_entry[] (uint32 column, float32 weight) as a uint32 array of 2 * nnz words."""
+    e = np.empty((len(cols), 2), dtype=np.uint32)
+    e[:, 0] = np.asarray(cols, dtype=np.uint32)
+    e[:, 1] = np.ascontiguousarray(weights, dtype=np.float32).view(np.uint32)
+    return e.reshape(-1)
+
+
+def element_chunk_ptr(ptr) -> np.ndarray:
+    """chunk_ptr of kw_sample_elements: prefix sums of ceil(row length / KW_ELEMENT_CHUNK), uint32."""
+    lengths = np.diff(np.asarray(ptr, dtype=np.int64))
+    out = np.zeros(len(lengths) + 1, dtype=np.uint32)
+    out[1:] = np.cumsum((lengths + ELEMENT_CHUNK - 1) // ELEMENT_CHUNK)
+    return out
 
 
 def load() -> C.CDLL:

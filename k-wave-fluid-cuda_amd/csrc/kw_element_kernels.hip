@@ -1,0 +1,117 @@
+// kw_element_kernels.hip — weighted transducer arrays (kwave_hip.h, "Weighted transducer arrays"): the element signals
+// expanded to per-point source values, and the sampled pressure reduced to one value per element.  Both are gathers over
+// a CSR matrix whose entries are (uint32 column, float weight) pairs, so each entry is one 8-byte load and no output is
+// written by more than one thread: the summation order is fixed by the CSR alone.
+#include "kw_internal.h"
+
+namespace {
+
+constexpr uint32_t kBlock = 256;                          // 4 waves
+constexpr uint32_t kChunk = KW_ELEMENT_CHUNK;             // entries per block of the sensor reduction
+static_assert(kChunk % kBlock == 0, "a chunk is a whole number of block-wide passes");
+
+} // namespace
+
+// one thread per source point: its row of the CSR in order, fp32 fma from 0
+__global__ __launch_bounds__(256) void k_element_source_row(float* __restrict__ row, const float* __restrict__ signal_t,
+                                                            const uint32_t* __restrict__ ptr,
+                                                            const uint2* __restrict__ entries, uint32_t n_points)
+{
+  for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < n_points; k += gridDim.x * blockDim.x)
+  {
+    const uint32_t end = ptr[k + 1];
+    float acc = 0.0f;
+    for (uint32_t j = ptr[k]; j < end; j++)
+    {
+      const uint2 e = entries[j];
+      acc = __fmaf_rn(__uint_as_float(e.y), signal_t[e.x], acc);
+    }
+    row[k] = acc;
+  }
+}
+
+// one block per (element, chunk): lane l of the block sums entries begin + l, begin + l + 256, ... with fp32 fma, then a
+// butterfly over the 64 lanes of each wave and the four wave sums in a fixed pairing give the chunk's partial sum
+__global__ __launch_bounds__(256) void k_sample_elements(float* __restrict__ partials, const float* __restrict__ p,
+                                                         const uint32_t* __restrict__ ptr, const uint2* __restrict__ entries,
+                                                         const uint32_t* __restrict__ chunk_ptr, uint32_t n_elements)
+{
+  const uint32_t b = blockIdx.x;
+  // the element whose chunks include b: the largest e with chunk_ptr[e] <= b (rows without chunks are skipped over)
+  uint32_t lo = 0, hi = n_elements;
+  while (hi - lo > 1)
+  {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (chunk_ptr[mid] <= b) lo = mid;
+    else hi = mid;
+  }
+  const uint32_t row_end = ptr[lo + 1];
+  const uint32_t begin   = ptr[lo] + (b - chunk_ptr[lo]) * kChunk;
+  const uint32_t end     = (begin >= row_end) ? begin : ((row_end - begin > kChunk) ? begin + kChunk : row_end);
+  float acc = 0.0f;
+  for (uint32_t j = begin + threadIdx.x; j < end; j += kBlock)
+  {
+    const uint2 e = entries[j];
+    acc = __fmaf_rn(__uint_as_float(e.y), p[e.x], acc);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  __shared__ float wave_sum[kBlock / 64];
+  if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[b] = (wave_sum[0] + wave_sum[1]) + (wave_sum[2] + wave_sum[3]);
+}
+
+// one thread per element: its chunk partials in chunk order (0 for an empty row)
+__global__ __launch_bounds__(256) void k_sample_elements_sum(float* __restrict__ out, const float* __restrict__ partials,
+                                                             const uint32_t* __restrict__ chunk_ptr, uint32_t n_elements)
+{
+  const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n_elements) return;
+  const uint32_t end = chunk_ptr[e + 1];
+  float acc = 0.0f;
+  for (uint32_t c = chunk_ptr[e]; c < end; c++) acc += partials[c];
+  out[e] = acc;
+}
+
+extern "C" {
+
+kw_status kw_element_source_row(kw_ctx* ctx, float* row, const float* element_input, const uint32_t* ptr,
+                                const kw_csr_entry* entries, uint32_t n_points, uint32_t n_elements, uint64_t time_index)
+{
+  KW_CHECK_CTX(ctx);
+  KW_PROF(ctx, "element_source_row");
+  if (n_points == 0) return KW_OK;
+  KW_REQUIRE(row && element_input && ptr && entries && n_elements > 0);
+  static_assert(sizeof(kw_csr_entry) == sizeof(uint2), "an entry is one 8-byte load");
+  uint32_t grid = (n_points + kBlock - 1) / kBlock;
+  const uint32_t cap = static_cast<uint32_t>(ctx->cu_count) * 8;
+  if (grid > cap) grid = cap;
+  hipLaunchKernelGGL(k_element_source_row, dim3(grid), dim3(kBlock), 0, ctx->stream, row,
+                     element_input + time_index * n_elements, ptr, reinterpret_cast<const uint2*>(entries), n_points);
+  KW_LAUNCH_CHECK();
+  return KW_OK;
+}
+
+kw_status kw_sample_elements(kw_ctx* ctx, float* out, const float* p, const uint32_t* ptr, const kw_csr_entry* entries,
+                             uint32_t n_elements, uint64_t nnz, const uint32_t* chunk_ptr, uint32_t n_chunks,
+                             float* partials)
+{
+  KW_CHECK_CTX(ctx);
+  KW_PROF(ctx, "sample_elements");
+  if (n_elements == 0) return KW_OK;
+  KW_REQUIRE(out && ptr && chunk_ptr && nnz <= 0xFFFFFFFFull);
+  KW_REQUIRE(n_chunks == 0 || (p && entries && partials));
+  if (n_chunks > 0)
+  {
+    hipLaunchKernelGGL(k_sample_elements, dim3(n_chunks), dim3(kBlock), 0, ctx->stream, partials, p, ptr,
+                       reinterpret_cast<const uint2*>(entries), chunk_ptr, n_elements);
+    KW_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(k_sample_elements_sum, dim3((n_elements + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, out,
+                     partials, chunk_ptr, n_elements);
+  KW_LAUNCH_CHECK();
+  return KW_OK;
+}
+
+} // extern "C"

@@ -124,7 +124,10 @@ INPUT_DATASETS = (
     "x_shift_neg_r", "y_shift_neg_r", "z_shift_neg_r", "pml_x", "pml_x_sgx", "pml_y", "pml_y_sgy", "pml_z", "pml_z_sgz",
     "dxudxn", "dyudyn", "dzudzn", "dxudxn_sgx", "dyudyn_sgy", "dzudzn_sgz",
     "p0_source_input", "p_source_index", "p_source_input", "u_source_index", "ux_source_input", "uy_source_input",
-    "uz_source_input", "transducer_source_input", "delay_mask", "sensor_mask_index", "sensor_mask_corners")
+    "uz_source_input", "transducer_source_input", "delay_mask", "sensor_mask_index", "sensor_mask_corners",
+    # weighted transducer arrays (new with this build): element signals and CSR weight matrices
+    "p_source_element_input", "p_source_element_ptr", "p_source_element_index", "p_source_element_weight",
+    "sensor_element_ptr", "sensor_element_index", "sensor_element_weight")
 
 
 def dataset_exists(path: str, name: str) -> bool:

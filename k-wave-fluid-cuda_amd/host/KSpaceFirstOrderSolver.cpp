@@ -40,6 +40,7 @@ void KSpaceFirstOrderSolver::allocateMemory()
 void KSpaceFirstOrderSolver::freeMemory()
 {
   releaseFusedPipeline();
+  mSourceElements.release();
   mOutputStreamContainer.freeStreams();
   mMatrixContainer.freeMatrices();
   HipFftComplexMatrix::destroyAllPlansAndStaticData();
@@ -50,6 +51,10 @@ void KSpaceFirstOrderSolver::loadInputData(const InputProvider& input)
 {
   PhaseTimer timer(mPhaseTime[0]);
   mMatrixContainer.loadDataFromInputFile(input);
+  if (mParameters.getPressureSourceElementFlag())
+    mSourceElements.upload(index(MI::kPressureSourceElementPtr).getHostData(), mParameters.getPressureSourceIndexSize(),
+                           index(MI::kPressureSourceElementIndex).getHostData(),
+                           real(MI::kPressureSourceElementWeight).getHostData(), mParameters.getPressureSourceElementNnz(), false);
   mOutputStreamContainer.createStreams();
 }
 
@@ -717,7 +722,7 @@ void KSpaceFirstOrderSolver::addVelocitySource()
     else
     {
       RealMatrix& scaledSource = getTemp1RealND();
-      scaleSource(scaledSource, real(c.input), index(MI::kVelocitySourceIndex), mParameters.getVelocitySourceMany());
+      scaleSource(scaledSource, real(c.input), index(MI::kVelocitySourceIndex), mParameters.getVelocitySourceMany(), timeIndex);
       SolverHipKernels::addVelocityScaledSource(real(c.u), scaledSource);
     }
   }
@@ -727,24 +732,36 @@ template<SD sd> void KSpaceFirstOrderSolver::addPressureSource()
 { // :2310-2332
   if (mParameters.getPressureSourceFlag() > mParameters.getTimeIndex())
   {
+    // weighted source: this step's row v(t) = W s(t) goes into the one-row series buffer, which the kernels below then
+    // read as row 0 of a p_source_many = 1 source
+    size_t seriesRow = mParameters.getTimeIndex();
+    if (mParameters.getPressureSourceElementFlag())
+    {
+      kwCheck(kw_element_source_row(mParameters.getHipParameters().getContext(), real(MI::kPressureSourceInput).getDeviceData(),
+                                    real(MI::kPressureSourceElementInput).getDeviceData(), mSourceElements.ptr(),
+                                    mSourceElements.entries(), static_cast<uint32_t>(mParameters.getPressureSourceIndexSize()),
+                                    static_cast<uint32_t>(mParameters.getPressureSourceElementCount()), seriesRow));
+      seriesRow = 0;
+    }
     if (mParameters.getPressureSourceMode() != Parameters::SourceMode::kAdditive)
     {
-      SolverHipKernels::addPressureSource<sd>(mMatrixContainer);
+      SolverHipKernels::addPressureSource<sd>(mMatrixContainer, seriesRow);
     }
     else
     {
       RealMatrix& scaledSource = getTemp1RealND();
-      scaleSource(scaledSource, real(MI::kPressureSourceInput), index(MI::kPressureSourceIndex), mParameters.getPressureSourceMany());
+      scaleSource(scaledSource, real(MI::kPressureSourceInput), index(MI::kPressureSourceIndex), mParameters.getPressureSourceMany(),
+                  seriesRow);
       SolverHipKernels::addPressureScaledSource<sd>(mMatrixContainer, scaledSource);
     }
   }
 }
 
 void KSpaceFirstOrderSolver::scaleSource(RealMatrix& scaledSource, const RealMatrix& sourceInput,
-                                         const IndexMatrix& sourceIndex, const size_t manyFlag)
+                                         const IndexMatrix& sourceIndex, const size_t manyFlag, size_t seriesRow)
 { // :2339-2352
   scaledSource.zeroDeviceMatrix();
-  SolverHipKernels::insertSourceIntoScalingMatrix(scaledSource, sourceInput, sourceIndex, manyFlag);
+  SolverHipKernels::insertSourceIntoScalingMatrix(scaledSource, sourceInput, sourceIndex, manyFlag, seriesRow);
   if (mFused)
   {
     kwCheck(kw_fused_scale_source(mParameters.getHipParameters().getContext(), scaledSource.getDeviceData(), mSourceKappaPadded));

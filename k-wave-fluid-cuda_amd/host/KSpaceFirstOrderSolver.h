@@ -8,6 +8,7 @@
 // arithmetic order) instead of one launch per reference kernel.
 #ifndef KW_HOST_KSPACE_FIRST_ORDER_SOLVER_H
 #define KW_HOST_KSPACE_FIRST_ORDER_SOLVER_H
+#include "ElementArrays.h"
 #include "MatrixContainer.h"
 #include "OutputStreams.h"
 #include "Parameters.h"
@@ -58,7 +59,8 @@ class KSpaceFirstOrderSolver
   template<SD simulationDimension> void computePressureLinear();
   void addVelocitySource();
   template<SD simulationDimension> void addPressureSource();
-  void scaleSource(RealMatrix& scaledSource, const RealMatrix& sourceInput, const IndexMatrix& sourceIndex, const size_t manyFlag);
+  void scaleSource(RealMatrix& scaledSource, const RealMatrix& sourceInput, const IndexMatrix& sourceIndex, const size_t manyFlag,
+                   size_t seriesRow);
   template<SD simulationDimension> void addInitialPressureSource();
   template<SD simulationDimension> void computeShiftedVelocity();
   // post-processing of the stored series (KSpaceFirstOrderSolver.cpp:1231-1534, :1783-2080)
@@ -113,5 +115,6 @@ class KSpaceFirstOrderSolver
   float*                mNabla1Padded = nullptr;
   float*                mNabla2Padded = nullptr;
   float*                mSourceKappaPadded = nullptr;
+  ElementCsr            mSourceElements; // weighted pressure source: point <- element weights (Parameters::getPressureSourceElementFlag)
 };
 #endif

@@ -2,6 +2,8 @@
 // *content*; here it is a schema table (kSchema below) walked by init().
 #include "MatrixContainer.h"
 
+#include <algorithm>
+
 #include "MatrixNames.h"
 #include "Parameters.h"
 
@@ -67,6 +69,9 @@ bool uySource(const P& p) { return p.getVelocityYSourceFlag() != 0; }
 bool uzSource(const P& p) { return p.getVelocityZSourceFlag() != 0; }
 bool anyVelocityIndex(const P& p) { return transducer(p) || uxSource(p) || uySource(p) || uzSource(p); }
 bool pSource(const P& p) { return p.getPressureSourceFlag() != 0; }
+bool pSourceWeighted(const P& p) { return pSource(p) && p.getPressureSourceElementFlag(); }
+bool pSourceExpanded(const P& p) { return pSource(p) && !p.getPressureSourceElementFlag(); }
+bool sensorElements(const P& p) { return p.getStorePressureElementsFlag(); }
 bool kSpaceCorrectedSource(const P& p)
 {
   return ((p.getVelocitySourceMode() == P::SourceMode::kAdditive) || (p.getPressureSourceMode() == P::SourceMode::kAdditive)) &&
@@ -83,6 +88,13 @@ DimensionSizes dimsVelocityIndex(const P& p) { return DimensionSizes(1, 1, p.get
 DimensionSizes dimsTransducerInput(const P& p) { return DimensionSizes(1, 1, p.getTransducerSourceInputSize()); }
 DimensionSizes dimsPressureIndex(const P& p) { return DimensionSizes(1, 1, p.getPressureSourceIndexSize()); }
 DimensionSizes dimsPressureInput(const P& p) { return seriesOf(p.getPressureSourceMany(), p.getPressureSourceIndexSize(), p.getPressureSourceFlag()); }
+// weighted source: the device holds Nt_src x E element signals and one row of Npts values that the source kernels read
+DimensionSizes dimsPressureElementInput(const P& p) { return DimensionSizes(p.getPressureSourceElementCount(), p.getPressureSourceFlag(), 1); }
+DimensionSizes dimsPressureRow(const P& p) { return DimensionSizes(std::max<size_t>(p.getPressureSourceIndexSize(), 1), 1, 1); }
+DimensionSizes dimsPressureElementPtr(const P& p) { return DimensionSizes(1, 1, p.getPressureSourceIndexSize() + 1); }
+DimensionSizes dimsPressureElementEntries(const P& p) { return DimensionSizes(1, 1, p.getPressureSourceElementNnz()); }
+DimensionSizes dimsSensorElementPtr(const P& p) { return DimensionSizes(1, 1, p.getSensorElementCount() + 1); }
+DimensionSizes dimsSensorElementEntries(const P& p) { return DimensionSizes(1, 1, p.getSensorElementNnz()); }
 DimensionSizes dimsUxInput(const P& p) { return seriesOf(p.getVelocitySourceMany(), p.getVelocitySourceIndexSize(), p.getVelocityXSourceFlag()); }
 DimensionSizes dimsUyInput(const P& p) { return seriesOf(p.getVelocitySourceMany(), p.getVelocitySourceIndexSize(), p.getVelocityYSourceFlag()); }
 DimensionSizes dimsUzInput(const P& p) { return seriesOf(p.getVelocitySourceMany(), p.getVelocitySourceIndexSize(), p.getVelocityZSourceFlag()); }
@@ -168,7 +180,15 @@ const Row kSchema[] = {
   { MI::kVelocitySourceIndex, MT::kIndex, Extent::kByRule, dimsVelocityIndex, kFromFile, kVelocitySourceIndexName, anyVelocityIndex },
   { MI::kDelayMask, MT::kIndex, Extent::kByRule, dimsVelocityIndex, kFromFile, kDelayMaskName, transducer },
   { MI::kTransducerSourceInput, MT::kReal, Extent::kByRule, dimsTransducerInput, kFromFile, kTransducerSourceInputName, transducer },
-  { MI::kPressureSourceInput, MT::kReal, Extent::kByRule, dimsPressureInput, kFromFile, kPressureSourceInputName, pSource },
+  { MI::kPressureSourceInput, MT::kReal, Extent::kByRule, dimsPressureInput, kFromFile, kPressureSourceInputName, pSourceExpanded },
+  { MI::kPressureSourceInput, MT::kReal, Extent::kByRule, dimsPressureRow, 0, "p_source_row", pSourceWeighted },
+  { MI::kPressureSourceElementInput, MT::kReal, Extent::kByRule, dimsPressureElementInput, kFromFile, kPressureSourceElementInputName, pSourceWeighted },
+  { MI::kPressureSourceElementPtr, MT::kIndex, Extent::kByRule, dimsPressureElementPtr, kFromFile, kPressureSourceElementPtrName, pSourceWeighted },
+  { MI::kPressureSourceElementIndex, MT::kIndex, Extent::kByRule, dimsPressureElementEntries, kFromFile, kPressureSourceElementIndexName, pSourceWeighted },
+  { MI::kPressureSourceElementWeight, MT::kReal, Extent::kByRule, dimsPressureElementEntries, kFromFile, kPressureSourceElementWeightName, pSourceWeighted },
+  { MI::kSensorElementPtr, MT::kIndex, Extent::kByRule, dimsSensorElementPtr, kFromFile, kSensorElementPtrName, sensorElements },
+  { MI::kSensorElementIndex, MT::kIndex, Extent::kByRule, dimsSensorElementEntries, kFromFile, kSensorElementIndexName, sensorElements },
+  { MI::kSensorElementWeight, MT::kReal, Extent::kByRule, dimsSensorElementEntries, kFromFile, kSensorElementWeightName, sensorElements },
   { MI::kPressureSourceIndex, MT::kIndex, Extent::kByRule, dimsPressureIndex, kFromFile, kPressureSourceIndexName, pSource },
   { MI::kVelocityXSourceInput, MT::kReal, Extent::kByRule, dimsUxInput, kFromFile, kVelocityXSourceInputName, uxSource },
   { MI::kVelocityYSourceInput, MT::kReal, Extent::kByRule, dimsUyInput, kFromFile, kVelocityYSourceInputName, uySource },

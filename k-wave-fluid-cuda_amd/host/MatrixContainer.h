@@ -37,7 +37,11 @@ class MatrixContainer
     kTransducerSourceInput, kVelocityXSourceInput, kVelocityYSourceInput, kVelocityZSourceInput, kPressureSourceIndex,
     kVelocitySourceIndex, kDelayMask, kUxShifted, kUyShifted, kUzShifted, kXShiftNegR, kYShiftNegR, kZShiftNegR,
     kTemp1RealND, kTemp2RealND, kTemp3RealND, kTempHipFftX, kTempHipFftY, kTempHipFftZ, kTempHipFftShift,
-    kDxudxn, kDyudyn, kDzudzn, kDxudxnSgx, kDyudynSgy, kDzudznSgz
+    kDxudxn, kDyudyn, kDzudzn, kDxudxnSgx, kDyudynSgy, kDzudznSgz,
+    // weighted transducer arrays: element signals + CSR of the source, CSR of the sensor (read from the input; the
+    // device copies the kernels use are packed by ElementCsr, ElementArrays.h)
+    kPressureSourceElementInput, kPressureSourceElementPtr, kPressureSourceElementIndex, kPressureSourceElementWeight,
+    kSensorElementPtr, kSensorElementIndex, kSensorElementWeight
   };
 
   MatrixContainer() = default;

@@ -35,7 +35,14 @@ MatrixName kInitialPressureSourceInputName = "p0_source_input";
 MatrixName kTransducerSourceInputName = "transducer_source_input", kDelayMaskName = "delay_mask";
 MatrixName kSensorMaskTypeName = "sensor_mask_type", kSensorMaskIndexName = "sensor_mask_index",
            kSensorMaskCornersName = "sensor_mask_corners";
+// weighted transducer arrays (new with this build): CSR weight matrices, 0-based uint64 row offsets, 1-based columns
+MatrixName kPressureSourceElementInputName = "p_source_element_input", kPressureSourceElementPtrName = "p_source_element_ptr",
+           kPressureSourceElementIndexName = "p_source_element_index",
+           kPressureSourceElementWeightName = "p_source_element_weight";
+MatrixName kSensorElementPtrName = "sensor_element_ptr", kSensorElementIndexName = "sensor_element_index",
+           kSensorElementWeightName = "sensor_element_weight";
 // output / state names
+MatrixName kPElementsName = "p_elements";
 MatrixName kPName = "p", kPRmsName = "p_rms", kPMaxName = "p_max", kPMinName = "p_min", kPMaxAllName = "p_max_all",
            kPMinAllName = "p_min_all", kPressureFinalName = "p_final";
 MatrixName kUxName = "ux", kUyName = "uy", kUzName = "uz";

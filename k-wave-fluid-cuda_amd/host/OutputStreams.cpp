@@ -442,6 +442,31 @@ void CuboidOutputStream::flushRaw()
   mFlushedSteps++;
 }
 
+// ---- ElementOutputStream --------------------------------------------------------------------------------------------
+void ElementOutputStream::create()
+{
+  mSize = mPtr.size() - 1;
+  allocateMemory();
+  // the CSR as loaded from the input (1-based grid indices); Parameters::init has checked it against the grid
+  mCsr.upload(mPtr.getHostData(), mSize, mIndex.getHostData(), mWeight.getHostData(), mIndex.size(), true);
+}
+void ElementOutputStream::sample()
+{
+  const int b = mSampledSteps & 1;
+  kwCheck(kw_sample_elements(ctx(), mDeviceRaw[b], mSourceMatrix.getDeviceData(), mCsr.ptr(), mCsr.entries(),
+                             static_cast<uint32_t>(mSize), mCsr.nnz(), mCsr.chunkPtr(), mCsr.chunks(), mCsr.partials()));
+  rawSampleTail(ctx(), mDeviceRaw[b], mPinned[b], mEvent[b], mSize);
+  mSampledSteps++;
+}
+void ElementOutputStream::flushRaw()
+{
+  if (mFlushedSteps >= mSampledSteps) return;
+  const int b = mFlushedSteps & 1;
+  kwCheck(kw_event_synchronize(ctx(), mEvent[b]));
+  storeRow(mPinned[b]);
+  mFlushedSteps++;
+}
+
 // ---- WholeDomainOutputStream ----------------------------------------------------------------------------------------
 void WholeDomainOutputStream::create()
 {
@@ -574,6 +599,11 @@ void OutputStreamContainer::init(MatrixContainer& mc)
         mContainer[OI::kQTermC] = new PostProcessedOutputStream("Q_term_c", mc.getMatrix<RealMatrix>(MI::kP), RO::kQTermC, mask, false);
     }
   }
+  if (params.getStorePressureElementsFlag())
+    mContainer[OI::kPressureElements] = new ElementOutputStream(kPElementsName, mc.getMatrix<RealMatrix>(MI::kP),
+                                                                mc.getMatrix<IndexMatrix>(MI::kSensorElementPtr),
+                                                                mc.getMatrix<IndexMatrix>(MI::kSensorElementIndex),
+                                                                mc.getMatrix<RealMatrix>(MI::kSensorElementWeight));
   if (params.getStoreVelocityMaxAllFlag())
   {
     mContainer[OI::kVelocityXMaxAll] = new WholeDomainOutputStream(kUxName + "_max_all", mc.getMatrix<RealMatrix>(MI::kUxSgx), RO::kMax);

@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "ElementArrays.h"
 #include "MatrixContainer.h"
 
 /// Replaces namespace OutputStreamsCudaKernels (OutputStreams/OutputStreamsCudaKernels.cuh:47-106)
@@ -215,6 +216,24 @@ class CuboidOutputStream : public BaseOutputStream
   const IndexMatrix& mSensorMask;
 };
 
+/// --p_elements: one value per element of a weighted sensor (sensor_element_*), out[e] = sum_j w_j p[index_j], raw series
+/// on the same overlapped pinned path as p.  Independent of the sensor mask.  New with this build.
+class ElementOutputStream : public BaseOutputStream
+{
+ public:
+  ElementOutputStream(const std::string& name, const RealMatrix& source, const IndexMatrix& ptr, const IndexMatrix& index,
+                      const RealMatrix& weight)
+    : BaseOutputStream(name, source, ReduceOperator::kNone), mPtr(ptr), mIndex(index), mWeight(weight) {}
+  void create() override;
+  void sample() override;
+  void flushRaw() override;
+ private:
+  const IndexMatrix& mPtr;
+  const IndexMatrix& mIndex;
+  const RealMatrix&  mWeight;
+  ElementCsr         mCsr;
+};
+
 class WholeDomainOutputStream : public BaseOutputStream
 {
  public:
@@ -238,7 +257,8 @@ class OutputStreamContainer
     kPressureC, kVelocityXNonStaggeredC, kVelocityYNonStaggeredC, kVelocityZNonStaggeredC,
     kIntensityXAvgC, kIntensityYAvgC, kIntensityZAvgC,
     kIntensityXAvg, kIntensityYAvg, kIntensityZAvg, kQTerm, kQTermC,
-    kVelocityXC, kVelocityYC, kVelocityZC
+    kVelocityXC, kVelocityYC, kVelocityZC,
+    kPressureElements
   };
   ~OutputStreamContainer() { freeStreams(); }
   void init(MatrixContainer& matrixContainer); // OutputStreamContainer.cpp:70-325

@@ -144,7 +144,8 @@ void Parameters::init(const InputProvider& in, const Options& options)
   }
   if (mPressureSourceFlag != 0)
   {
-    in.readScalarValue(kPressureSourceManyName, mPressureSourceMany);
+    if (in.datasetExists(kPressureSourceElementInputName)) mPressureSourceMany = 1; // weighted: one row per step
+    else in.readScalarValue(kPressureSourceManyName, mPressureSourceMany);
     size_t m = 0;
     in.readScalarValue(kPressureSourceModeName, m);
     mPressureSourceMode      = toMode(m, "pressure");
@@ -196,6 +197,7 @@ void Parameters::init(const InputProvider& in, const Options& options)
     }
     CompressHelper::getInstance().init(mOptions.period, mOptions.mos, mOptions.harmonics, true);
   }
+  readElementArrays(in);
   mRho0ScalarFlag = in.getDatasetDimensionSizes(kRho0Name) == scalarSizes;
   if (mRho0ScalarFlag)
   {
@@ -203,6 +205,84 @@ void Parameters::init(const InputProvider& in, const Options& options)
     in.readScalarValue(kRho0SgxName, mRho0SgxScalar);
     in.readScalarValue(kRho0SgyName, mRho0SgyScalar);
     in.readScalarValue(kRho0SgzName, mRho0SgzScalar);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Weighted transducer arrays: the CSR datasets are checked here, before anything is allocated on the device, because a
+// bad offset or column would be an out-of-bounds gather in kw_element_source_row / kw_sample_elements.  The device holds
+// offsets and columns as 32-bit values (kw_csr_entry), which bounds the entry count and, for the sensor, the grid.
+void Parameters::readElementArrays(const InputProvider& in)
+{
+  mPressureSourceElementCount = mPressureSourceElementNnz = 0;
+  mSensorElementCount = mSensorElementNnz = 0;
+  const size_t gridPoints = mFullDimensionSizes.nElements();
+  constexpr size_t kMax32 = 0xFFFFFFFFull;
+  // ptr: rows + 1 non-decreasing 0-based offsets ending at nnz; columns: 1-based, 1 .. limit
+  auto checkCsr = [&](const std::string& ptrName, size_t rows, const std::string& colName, const std::string& weightName,
+                      size_t limit, const char* what) {
+    for (const std::string* n : {&ptrName, &colName, &weightName})
+      if (!in.datasetExists(*n)) throw std::invalid_argument(*n + ": dataset is missing (" + what + ")");
+    const size_t nnz = in.getDatasetSize(colName);
+    if (in.getDatasetSize(ptrName) != rows + 1)
+      throw std::invalid_argument(ptrName + ": has " + std::to_string(in.getDatasetSize(ptrName)) + " entries, expected " +
+                                  std::to_string(rows + 1));
+    if (in.getDatasetSize(weightName) != nnz)
+      throw std::invalid_argument(weightName + ": has " + std::to_string(in.getDatasetSize(weightName)) + " entries, but " +
+                                  colName + " has " + std::to_string(nnz));
+    if (nnz > kMax32) throw std::invalid_argument(colName + ": more than 2^32 - 1 entries");
+    std::vector<size_t> ptr(rows + 1), col(nnz);
+    in.readIndex(ptrName, ptr.data(), ptr.size());
+    if (ptr[0] != 0) throw std::invalid_argument(ptrName + ": the first offset must be 0");
+    for (size_t r = 0; r < rows; r++)
+      if (ptr[r + 1] < ptr[r]) throw std::invalid_argument(ptrName + ": offsets are not monotone at row " + std::to_string(r));
+    if (ptr[rows] != nnz)
+      throw std::invalid_argument(ptrName + ": last offset " + std::to_string(ptr[rows]) + " differs from the " +
+                                  std::to_string(nnz) + " entries of " + colName);
+    if (nnz > 0) in.readIndex(colName, col.data(), col.size());
+    for (size_t j = 0; j < nnz; j++)
+      if (col[j] < 1 || col[j] > limit)
+        throw std::invalid_argument(colName + ": entry " + std::to_string(j) + " = " + std::to_string(col[j]) +
+                                    " lies outside 1.." + std::to_string(limit));
+    return nnz;
+  };
+
+  const bool sourceWeighted = in.datasetExists(kPressureSourceElementInputName);
+  if (sourceWeighted && mPressureSourceFlag == 0)
+    throw std::invalid_argument(kPressureSourceElementInputName + ": present, but p_source_flag is 0");
+  if (sourceWeighted)
+  {
+    if (in.datasetExists(kPressureSourceInputName))
+      throw std::invalid_argument("p_source_input and " + kPressureSourceElementInputName + " cannot both be present");
+    if (in.datasetExists(kPressureSourceManyName))
+    {
+      size_t many = 0;
+      in.readScalarValue(kPressureSourceManyName, many);
+      if (many != 1) throw std::invalid_argument(kPressureSourceManyName + ": must be 1 with " + kPressureSourceElementInputName);
+    }
+    const DimensionSizes dims = in.getDatasetDimensionSizes(kPressureSourceElementInputName); // (E, Nt_src, 1)
+    const size_t elements = dims.nx;
+    if (elements == 0 || dims.nElements() != elements * mPressureSourceFlag)
+      throw std::invalid_argument(kPressureSourceElementInputName + ": expected (1, p_source_flag = " +
+                                  std::to_string(mPressureSourceFlag) + ", E) with E >= 1");
+    if (mPressureSourceIndexSize > kMax32) throw std::invalid_argument(kPressureSourceIndexName + ": more than 2^32 - 1 points");
+    mPressureSourceElementNnz = checkCsr(kPressureSourceElementPtrName, mPressureSourceIndexSize, kPressureSourceElementIndexName,
+                                         kPressureSourceElementWeightName, elements, "weighted pressure source");
+    mPressureSourceElementCount = elements;
+  }
+  if (mOptions.storePressureElements)
+  {
+    if (!in.datasetExists(kSensorElementPtrName) || !in.datasetExists(kSensorElementIndexName) ||
+        !in.datasetExists(kSensorElementWeightName))
+      throw std::invalid_argument("--p_elements needs the datasets " + kSensorElementPtrName + ", " + kSensorElementIndexName +
+                                  " and " + kSensorElementWeightName);
+    if (gridPoints > kMax32)
+      throw std::invalid_argument(kSensorElementIndexName + ": the weighted sensor needs a grid of fewer than 2^32 points");
+    const size_t rows = in.getDatasetSize(kSensorElementPtrName);
+    if (rows < 2) throw std::invalid_argument(kSensorElementPtrName + ": needs E + 1 >= 2 entries");
+    mSensorElementNnz   = checkCsr(kSensorElementPtrName, rows - 1, kSensorElementIndexName, kSensorElementWeightName,
+                                   gridPoints, "weighted sensor");
+    mSensorElementCount = rows - 1;
   }
 }
 

@@ -57,6 +57,7 @@ class Parameters
     bool   storePressureC = false, storeVelocityNonStaggeredC = false, storeIntensityAvgC = false;
     bool   storeIntensityAvg = false, storeQTerm = false, storeQTermC = false; // --I_avg, --Q_term, --Q_term_c
     bool   storeVelocityC = false; // --u_c
+    bool   storePressureElements = false; // --p_elements: weighted sensor (sensor_element_*), one series per element
     bool   complex40bit = false;       // --40-bit_complex
     bool   onlyPostProcessing = false; // --post: post-processing of an existing output file, no time loop
     float  frequency = 0.0f;       // --frequency [Hz], alternative to --period
@@ -182,6 +183,14 @@ class Parameters
   SourceMode getPressureSourceMode() const { return mPressureSourceMode; }
   size_t     getPressureSourceMany() const { return mPressureSourceMany; }
   SourceMode getVelocitySourceMode() const { return mVelocitySourceMode; }
+  /// weighted pressure source (p_source_element_input present): p_source_index points get v(t) = W s(t) from E element
+  /// signals; the series seen by the source kernels is one row of Npts values (p_source_many is 1)
+  bool   getPressureSourceElementFlag() const { return mPressureSourceElementCount != 0; }
+  size_t getPressureSourceElementCount() const { return mPressureSourceElementCount; }
+  size_t getPressureSourceElementNnz() const { return mPressureSourceElementNnz; }
+  /// weighted sensor (--p_elements): E rows of sensor_element_* over the grid
+  size_t getSensorElementCount() const { return mSensorElementCount; }
+  size_t getSensorElementNnz() const { return mSensorElementNnz; }
   size_t     getVelocitySourceMany() const { return mVelocitySourceMany; }
 
   SensorMaskType getSensorMaskType() const { return mSensorMaskType; }
@@ -212,6 +221,7 @@ class Parameters
   bool getStoreQTermFlag() const { return mOptions.storeQTerm; }
   bool getStoreQTermCFlag() const { return mOptions.storeQTermC; }
   bool getStoreVelocityCFlag() const { return mOptions.storeVelocityC; }
+  bool getStorePressureElementsFlag() const { return mOptions.storePressureElements; }
   bool getOnlyPostProcessingFlag() const { return mOptions.onlyPostProcessing; }
   bool get40bitCompressionFlag() const { return mOptions.complex40bit; }
   bool getNoCompressionOverlapFlag() const { return mOptions.noCompressionOverlap; }
@@ -255,5 +265,8 @@ class Parameters
   size_t mPressureSourceMany = 0, mVelocitySourceMany = 0;
   SensorMaskType mSensorMaskType = SensorMaskType::kIndex;
   size_t mSensorMaskIndexSize = 0, mSensorMaskCornersSize = 0;
+  size_t mPressureSourceElementCount = 0, mPressureSourceElementNnz = 0;
+  size_t mSensorElementCount = 0, mSensorElementNnz = 0;
+  void   readElementArrays(const InputProvider& in);
 };
 #endif

@@ -41,19 +41,19 @@ void addVelocitySource(RealMatrix& velocity, const RealMatrix& input, const Inde
   kwCheck(kw_add_velocity_source(ctx(), velocity.getDeviceData(), input.getDeviceData(),
                                  (const uint64_t*)index.getDeviceData(), Parameters::getInstance().getTimeIndex()));
 }
-template<SD sd> void addPressureSource(const MatrixContainer& c)
+template<SD sd> void addPressureSource(const MatrixContainer& c, size_t seriesRow)
 {
   kwCheck(kw_add_pressure_source(ctx(), real(c, MI::kRhoX), real(c, MI::kRhoY), real(c, MI::kRhoZ),
                                  real(c, MI::kPressureSourceInput),
                                  (const uint64_t*)c.getMatrix<IndexMatrix>(MI::kPressureSourceIndex).getDeviceData(),
-                                 Parameters::getInstance().getTimeIndex()));
+                                 seriesRow));
 }
 void insertSourceIntoScalingMatrix(RealMatrix& scaled, const RealMatrix& input, const IndexMatrix& index,
-                                   const size_t manyFlag)
+                                   const size_t manyFlag, size_t seriesRow)
 {
   kwCheck(kw_insert_source_into_scaling_matrix(ctx(), scaled.getDeviceData(), input.getDeviceData(),
                                                (const uint64_t*)index.getDeviceData(), index.size(), manyFlag != 0,
-                                               Parameters::getInstance().getTimeIndex()));
+                                               seriesRow));
 }
 void computeSourceGradient(HipFftComplexMatrix& spectrum, const RealMatrix& sourceKappa)
 {
@@ -180,7 +180,7 @@ void computeVelocityShiftInZ(HipFftComplexMatrix& t, const ComplexMatrix& s)
 // explicit instances (3-D)
 template void computeVelocityHeterogeneous<SD::k3D>(const MatrixContainer&);
 template void computeVelocityHomogeneousUniform<SD::k3D>(const MatrixContainer&);
-template void addPressureSource<SD::k3D>(const MatrixContainer&);
+template void addPressureSource<SD::k3D>(const MatrixContainer&, size_t);
 template void addPressureScaledSource<SD::k3D>(const MatrixContainer&, const RealMatrix&);
 template void addInitialPressureSource<SD::k3D>(const MatrixContainer&);
 template void computeInitialVelocityHeterogeneous<SD::k3D>(const MatrixContainer&);

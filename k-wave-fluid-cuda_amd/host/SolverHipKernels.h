@@ -18,9 +18,10 @@ template<SD simulationDimension = SD::k3D> void computeVelocityHeterogeneous(con
 template<SD simulationDimension = SD::k3D> void computeVelocityHomogeneousUniform(const MatrixContainer& container);
 void addTransducerSource(const MatrixContainer& container);
 void addVelocitySource(RealMatrix& velocity, const RealMatrix& velocitySourceInput, const IndexMatrix& velocitySourceIndex);
-template<SD simulationDimension = SD::k3D> void addPressureSource(const MatrixContainer& container);
+/// seriesRow: row of p_source_input to read (the time index; 0 for the one-row buffer of a weighted source)
+template<SD simulationDimension = SD::k3D> void addPressureSource(const MatrixContainer& container, size_t seriesRow);
 void insertSourceIntoScalingMatrix(RealMatrix& scaledSource, const RealMatrix& sourceInput,
-                                   const IndexMatrix& sourceIndex, const size_t manyFlag);
+                                   const IndexMatrix& sourceIndex, const size_t manyFlag, size_t seriesRow);
 void computeSourceGradient(HipFftComplexMatrix& sourceSpectrum, const RealMatrix& sourceKappa);
 void addVelocityScaledSource(RealMatrix& velocity, const RealMatrix& scaledSource);
 template<SD simulationDimension = SD::k3D>

@@ -61,7 +61,7 @@ void kwh_open_output(kwh_solver* s, const std::string& path, unsigned compressio
     // rows of the dataset: every sampled step, or every finished frame (IndexOutputStream.cpp:108-117)
     const size_t rows = cs ? std::max<size_t>(steps / CompressHelper::getInstance().getOSize(), 1) : steps;
     std::vector<Hdf5SeriesWriter::Part> parts;
-    if (cornersMask && cs == nullptr)
+    if (cornersMask && cs == nullptr && dynamic_cast<ElementOutputStream*>(st) == nullptr) // p_elements: one row of E values
     {
       const IndexMatrix& corners = mc.getMatrix<IndexMatrix>(MatrixContainer::MatrixIdx::kSensorMaskCorners);
       writer->drain();
@@ -177,7 +177,8 @@ static void writeStreamData(kwh_solver* s, Hdf5File& out, BaseOutputStream* st, 
 {
   const DimensionSizes dims = Parameters::getInstance().getGlobalDimensionSizes();
   MatrixContainer& mcs = s->solver->getMatrixContainer();
-  if (mcs.has(MatrixContainer::MatrixIdx::kSensorMaskCorners) && dynamic_cast<WholeDomainOutputStream*>(st) == nullptr)
+  if (mcs.has(MatrixContainer::MatrixIdx::kSensorMaskCorners) && dynamic_cast<WholeDomainOutputStream*>(st) == nullptr &&
+      dynamic_cast<ElementOutputStream*>(st) == nullptr)
   {
     const IndexMatrix& corners = mcs.getMatrix<IndexMatrix>(MatrixContainer::MatrixIdx::kSensorMaskCorners);
     if (!out.datasetExists(name)) out.createGroup(name);

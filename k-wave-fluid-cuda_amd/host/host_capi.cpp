@@ -53,6 +53,7 @@ Parameters::Options kwh_convert_options(const kwh_options* o)
   if (o->rccl_library != nullptr) opt.rcclLibrary = o->rccl_library;
   opt.p2pEmulateLinkGbs   = o->p2p_emulate_link_gbs;
   opt.p2pEmulateLatencyUs = o->p2p_emulate_latency_us;
+  opt.storePressureElements = o->p_elements != 0;
   return opt;
 }
 
