@@ -297,6 +297,24 @@ KW_API kw_status kw_sum_pressure_nonlinear_lossless(kw_ctx* ctx, float* p, const
 /* sumPressureLinearLossless (.cuh:444, .cu:2224-2275) */
 KW_API kw_status kw_sum_pressure_linear_lossless(kw_ctx* ctx, float* p, const float* rho_x, const float* rho_y,
                                                  const float* rho_z, const float* c2);
+/* Stokes absorption (new with this build; k-Wave's medium.alpha_mode = 'stokes', absorbing_flag = 2): for alpha_power == 2
+ * the power-law operators degenerate (nabla1 = |k|^0 = 1, eta ~ tan(pi) = 0) and the absorbing equation of state is
+ * element-wise.  With rhoSum = (rho_x + rho_y) + rho_z and duSum = (duxdx + duydy) + duzdz, every fp32 product and sum
+ * rounded on its own (no fma contraction), in this order:
+ *   absorb = tau * (rho0 * duSum)
+ *   first  = rhoSum                                               (linear)
+ *          = (((b_on_a * rhoSum) * rhoSum) / (2 * rho0)) + rhoSum   (nonlinear: the nonlinear term of .cu:1588-1601)
+ *   p      = c2 * (first + absorb)
+ * tau = absorb_tau of the power law at alpha_power = 2 (-2 * alpha_Np * c0).  c2 / b_on_a / rho0 / tau NULL -> scalars.
+ * kw_fused_density(terms == 4) evaluates the same expression (same bits) inside the density epilogue. */
+KW_API kw_status kw_sum_pressure_stokes_nonlinear(kw_ctx* ctx, float* p, const float* rho_x, const float* rho_y,
+                                                  const float* rho_z, const float* duxdx, const float* duydy,
+                                                  const float* duzdz, const float* c2, const float* b_on_a,
+                                                  const float* rho0, const float* absorb_tau);
+KW_API kw_status kw_sum_pressure_stokes_linear(kw_ctx* ctx, float* p, const float* rho_x, const float* rho_y,
+                                               const float* rho_z, const float* duxdx, const float* duydy,
+                                               const float* duzdz, const float* c2, const float* rho0,
+                                               const float* absorb_tau);
 /* computeVelocityShiftInX/Y/Z (.cuh:482-499, .cu:2617-2710); spectrum in the layout of kw_fft_r2c_1d(axis) */
 KW_API kw_status kw_compute_velocity_shift(kw_ctx* ctx, int axis, float* spectrum, const float* shift_neg_r);
 
@@ -428,7 +446,10 @@ KW_API kw_status kw_fused_initial_velocity(kw_ctx* ctx, const float* p, float* u
  * t1 = rho0 * sum du; terms==2: t0 = sum rho, t1 = nonlinear term, t2 = rho0 * sum du.
  * terms==3 (lossless media): the equation of state itself, sumPressure{Nonlinear,Linear}Lossless (.cu:2067-2084,
  * 2224-2236): t0 = p (output), t1 = c2 array or NULL for the scalar (INPUT, not written), t2 unused; with
- * KW_FUSED_CHAIN_TERMS the spectrum of the new p is left for kw_fused_velocity(KW_FUSED_P_IN_SCRATCH). */
+ * KW_FUSED_CHAIN_TERMS the spectrum of the new p is left for kw_fused_velocity(KW_FUSED_P_IN_SCRATCH).
+ * terms==4 (Stokes absorption, alpha_power == 2): as terms==3 with the absorbing term of kw_sum_pressure_stokes_* (same
+ * association order, same bits) on the gradients of this step: t0 = p (output), t1 = c2 array or NULL, t2 = absorb_tau
+ * array or NULL (both INPUTS, not written; NULL -> the scalar of kw_constants); chains the spectrum of p like terms==3. */
 KW_API kw_status kw_fused_density(kw_ctx* ctx, int nonlinear, const float* ux_sgx, const float* uy_sgy,
                                   const float* uz_sgz, float* rho_x, float* rho_y, float* rho_z, const float* pml_x,
                                   const float* pml_y, const float* pml_z, const float* rho0,

@@ -24,8 +24,9 @@ HIPCC = os.path.join(ROCM, "bin", "hipcc")
 # measured from scratch, 8 jobs side by side: 185 s down to 65 s in this order, every other object at most 11 s)
 SLOWEST_FIRST = ("kw_fused_xinv_other.hip", "kw_fused_main.hip", "kw_fused_xinv_density_plain_tail.hip",
                  "kw_fused_xinv_density_chain_tail.hip", "kw_fused_xinv_other_tail.hip", "kw_fused_xinv_density_plain_long.hip",
-                 "kw_fused_xinv_density_chain_long.hip", "kw_fused_xinv_density_chain_short.hip",
-                 "kw_fused_xinv_density_plain_short.hip")
+                 "kw_fused_xinv_density_chain_long.hip", "kw_fused_xinv_density_stokes_tail.hip",
+                 "kw_fused_xinv_density_chain_short.hip", "kw_fused_xinv_density_plain_short.hip",
+                 "kw_fused_xinv_density_stokes_long.hip", "kw_fused_xinv_density_stokes_short.hip")
 # the fused pipeline's device code, which each of its code objects (kw_fused_*.hip) includes: no code object itself
 INCLUDED_ONLY = ("kw_fused.hip",)
 HIP_LIB = os.path.join(LIB_DIR, "libkwave_hip.so")

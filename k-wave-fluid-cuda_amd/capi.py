@@ -125,6 +125,8 @@ _SIG: Dict[str, list] = {
     "kw_sum_pressure_terms_linear": [_P] + [_P] * 7,
     "kw_sum_pressure_nonlinear_lossless": [_P] + [_P] * 7,
     "kw_sum_pressure_linear_lossless": [_P] + [_P] * 5,
+    "kw_sum_pressure_stokes_nonlinear": [_P] + [_P] * 11,
+    "kw_sum_pressure_stokes_linear": [_P] + [_P] * 10,
     "kw_compute_velocity_shift": [_P, C.c_int, _P, _P],
     "kw_measure_copy_bandwidth": [_P, C.c_size_t, C.c_int, C.POINTER(C.c_double)],
     "kw_comm_unique_id": [_P, C.c_size_t],

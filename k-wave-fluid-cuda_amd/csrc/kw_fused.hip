@@ -117,7 +117,8 @@ struct XinvArgs
   float*        aux[3]; // du stores / -
   float*        t[3];  // pressure-term outputs
   int           nonlinear;
-  int           terms; // 0 none, 1 linear (t0 = sum rho, t1 = rho0*sum du), 2 nonlinear (t0, t1 = nonlinear term, t2)
+  int           terms; // 0 none, 1 linear (t0 = sum rho, t1 = rho0*sum du), 2 nonlinear (t0, t1 = nonlinear term, t2),
+                       // 3 lossless pressure (t0 = p, m0[2] = c2), 4 Stokes pressure (as 3, and t[2] = absorb_tau array or NULL: INPUT)
   uint32_t      comp0; // first component of this launch (per-array launches)
   float2*       fout[3]; // CHAIN: where the forward x-transform of the epilogue's result goes (scratch rows)
   uint32_t      tile0;   // first 2*NL-row tile of this launch (chunked plane-local passes)
@@ -144,6 +145,11 @@ kw_status xinv_density_chain_tail(int terms, kw_ctx* ctx, int ncomp, const XinvA
 kw_status xinv_density_plain_short(int terms, kw_ctx* ctx, int ncomp, const XinvArgs& a, uint32_t tile0, uint32_t ntiles);
 kw_status xinv_density_plain_long(int terms, kw_ctx* ctx, int ncomp, const XinvArgs& a, uint32_t tile0, uint32_t ntiles);
 kw_status xinv_density_plain_tail(int terms, kw_ctx* ctx, int ncomp, const XinvArgs& a, uint32_t tile0, uint32_t ntiles);
+// the Stokes pressure epilogue (terms == 4), plain and chained, in code objects of its own (kw_fused_xinv_density_stokes_*.hip)
+kw_status xinv_density_stokes_short(int chain, kw_ctx* ctx, int ncomp, const XinvArgs& a, uint32_t tile0, uint32_t ntiles);
+kw_status xinv_density_stokes_long(int chain, kw_ctx* ctx, int ncomp, const XinvArgs& a, uint32_t tile0, uint32_t ntiles);
+kw_status xinv_density_stokes_tail(int chain, kw_ctx* ctx, int ncomp, const XinvArgs& a, uint32_t tile0, uint32_t ntiles);
+kw_status xinv_density_stokes_plane(int chain, kw_ctx* ctx, int ncomp, const XinvArgs& a, uint32_t plane0, uint32_t nplanes);
 kw_status xinv_other(int epi, int chain, kw_ctx* ctx, int ncomp, const XinvArgs& a, uint32_t tile0, uint32_t ntiles);
 kw_status xinv_other_tail(int epi, int chain, kw_ctx* ctx, int ncomp, const XinvArgs& a, uint32_t tile0, uint32_t ntiles);
 // whole-plane tiles (small grids, see k_xinv); with density-chain-short and other
@@ -1344,8 +1350,9 @@ __global__ __launch_bounds__((Geo<L, PLANE ? L / 2 : nl_x(L)>::THREADS), (EPI ==
   float4 pmlx4 = make_float4(1.f, 1.f, 1.f, 1.f);
   if (XFIX && ((EPI == EPI_VELOCITY && comp == 0) || EPI == EPI_DENSITY)) pmlx4 = ld4(a.m1[0] + xfix);
   const bool hetRho0 = (EPI == EPI_DENSITY) && (a.m0[0] != nullptr);
-  const bool hetBonA = (EPI == EPI_DENSITY) && (terms == 2 || (terms == 3 && a.nonlinear)) && (a.m0[1] != nullptr);
-  const bool hetC2   = (EPI == EPI_DENSITY) && (terms == 3) && (a.m0[2] != nullptr);
+  const bool hetBonA = (EPI == EPI_DENSITY) && (terms == 2 || ((terms == 3 || terms == 4) && a.nonlinear)) && (a.m0[1] != nullptr);
+  const bool hetC2   = (EPI == EPI_DENSITY) && (terms == 3 || terms == 4) && (a.m0[2] != nullptr);
+  const bool hetTau  = (EPI == EPI_DENSITY) && (terms == 4) && (a.t[2] != nullptr);
 #pragma unroll
   for (int q0 = 0; q0 < NQ; q0 += GQ)
   {
@@ -1379,7 +1386,7 @@ __global__ __launch_bounds__((Geo<L, PLANE ? L / 2 : nl_x(L)>::THREADS), (EPI ==
         op2[g] = ld4(a.out[2] + i);
         if (hetRho0) op3[g] = ld4(a.m0[0] + i);
         if (hetBonA) op4[g] = ld4(a.m0[1] + i);
-        if (hetC2) op5[g] = ld4(a.m0[2] + i);
+        if (hetC2 && terms == 3) op5[g] = ld4(a.m0[2] + i);
         sy[g] = a.m1[1][y];
         sz[g] = a.m1[2][z];
       }
@@ -1526,6 +1533,28 @@ __global__ __launch_bounds__((Geo<L, PLANE ? L / 2 : nl_x(L)>::THREADS), (EPI ==
           if (row_ok) st4(a.t[0] + i, pn);
           if constexpr (CHAIN) { if (e_ok) *reinterpret_cast<float4*>(&ldsr[(e / Q4) * RP + x]) = pn; }
         }
+        else if (terms == 4)
+        { // Stokes absorption (alpha_power == 2) on the updated densities and the gradients of this step: kw_stokes_pressure
+          // (kw_internal.h), the arithmetic of kw_sum_pressure_stokes_*; the new p is stored and chained like the lossless one
+          const float4 b4   = hetBonA ? op4[g] : make_float4(k.b_on_a, k.b_on_a, k.b_on_a, k.b_on_a);
+          // c2 and tau are requested here, once the density update has released the registers of the old densities, not
+          // with the operand group above: the epilogue then needs no more registers than the lossless one
+          // (a masked row reads nothing: its p is 0 and is neither stored nor chained past the grid's last row)
+          const bool   in_grid = !TAIL || r < a.nrows;
+          const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+          const float4 c24  = hetC2 ? (in_grid ? ld4(a.m0[2] + i) : zero4) : make_float4(k.c2, k.c2, k.c2, k.c2);
+          const float4 tau4 = hetTau ? (in_grid ? ld4(a.t[2] + i) : zero4) : make_float4(k.absorb_tau, k.absorb_tau, k.absorb_tau, k.absorb_tau);
+          float4 pn;
+#pragma unroll
+          for (int t = 0; t < 4; t++)
+          {
+            const float rhoSum = f4get(nrx, t) + f4get(nry, t) + f4get(nrz, t);
+            const float duSum  = f4get(dux, t) + f4get(duy, t) + f4get(duz, t);
+            f4put(pn, t, kw_stokes_pressure(a.nonlinear != 0, f4get(c24, t), f4get(tau4, t), f4get(r04, t), f4get(b4, t), rhoSum, duSum));
+          }
+          if (row_ok) st4(a.t[0] + i, pn);
+          if constexpr (CHAIN) { if (e_ok) *reinterpret_cast<float4*>(&ldsr[(e / Q4) * RP + x]) = pn; }
+        }
         else if (terms == 1)
         { // :1733-1741
           float4 o0, o1;
@@ -1566,7 +1595,7 @@ __global__ __launch_bounds__((Geo<L, PLANE ? L / 2 : nl_x(L)>::THREADS), (EPI ==
 #pragma unroll
     for (int jf = 0; jf < NF; jf++)
     {
-      if (EPI == EPI_DENSITY && jf == 1 && terms == 3) break; // lossless: only p is chained
+      if (EPI == EPI_DENSITY && jf == 1 && (terms == 3 || terms == 4)) break; // lossless / Stokes: only p is chained
       if (!(FW0_IN_LDS && jf == 0))
       {
 #pragma unroll
@@ -1746,7 +1775,8 @@ kw_status launch_xinv_impl(kw_ctx* ctx, int ncomp, XinvArgs a, uint32_t tile0, u
 }
 
 // the bodies of the x-inverse entry points (kw_fused_xinv_*.hip): density epilogues by their number of pressure terms
-// (chained: 1 ... 3, plain: 0 ... 3), the other epilogues by epilogue and chaining
+// (chained: 1 ... 3, plain: 0 ... 3; the Stokes pressure epilogue, 4, has entry points of its own), the other epilogues
+// by epilogue and chaining
 template<bool CHAIN, bool TAIL, int LINES, bool PLANE = false>
 kw_status launch_xinv_density(int terms, kw_ctx* ctx, int ncomp, const XinvArgs& a, uint32_t tile0, uint32_t ntiles)
 {
@@ -1759,6 +1789,13 @@ kw_status launch_xinv_density(int terms, kw_ctx* ctx, int ncomp, const XinvArgs&
   }
   kw_set_error("fused pipeline: no density epilogue for chain = %d, terms = %d", CHAIN ? 1 : 0, terms);
   return KW_ERR_INVALID;
+}
+
+template<bool TAIL, int LINES, bool PLANE = false>
+kw_status launch_xinv_density_stokes(int chain, kw_ctx* ctx, int ncomp, const XinvArgs& a, uint32_t tile0, uint32_t ntiles)
+{
+  return chain ? launch_xinv_impl<EPI_DENSITY, true, 4, TAIL, LINES, PLANE>(ctx, ncomp, a, tile0, ntiles)
+               : launch_xinv_impl<EPI_DENSITY, false, 4, TAIL, LINES, PLANE>(ctx, ncomp, a, tile0, ntiles);
 }
 
 template<bool TAIL, bool PLANE = false>

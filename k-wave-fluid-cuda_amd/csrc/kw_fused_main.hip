@@ -243,8 +243,9 @@ kw_status launch_xinv(kw_ctx* ctx, int ncomp, XinvArgs a, uint32_t z0 = 0, uint3
   a.side_off = ctx->fused.side_off;
   a.nrows = c.ny * c.nz;
   if (plane) // one block per z-plane; the kernel does the plane's y transforms as well
-    return EPI == EPI_DENSITY ? xinv_density_plane(CHAIN ? 1 : 0, TERMS, ctx, ncomp, a, z0, nzc ? nzc : c.nz)
-                              : xinv_other_plane(EPI, CHAIN ? 1 : 0, ctx, ncomp, a, z0, nzc ? nzc : c.nz);
+    return EPI != EPI_DENSITY ? xinv_other_plane(EPI, CHAIN ? 1 : 0, ctx, ncomp, a, z0, nzc ? nzc : c.nz)
+           : TERMS == 4       ? xinv_density_stokes_plane(CHAIN ? 1 : 0, ctx, ncomp, a, z0, nzc ? nzc : c.nz)
+                              : xinv_density_plane(CHAIN ? 1 : 0, TERMS, ctx, ncomp, a, z0, nzc ? nzc : c.nz);
   const uint32_t rows_per_tile = 2u * static_cast<uint32_t>(nl_x(c.nx));
   const uint32_t rows = c.ny * (nzc ? nzc : c.nz), full = rows / rows_per_tile;
   const uint32_t tile0 = z0 * c.ny / rows_per_tile; // chunked launches start on tile boundaries (plane_local_tail)
@@ -252,12 +253,14 @@ kw_status launch_xinv(kw_ctx* ctx, int ncomp, XinvArgs a, uint32_t z0 = 0, uint3
   if (full > 0)
   {
     if (EPI != EPI_DENSITY) KW_TRY(xinv_other(EPI, CHAIN ? 1 : 0, ctx, ncomp, a, tile0, full));
+    else if (TERMS == 4) KW_TRY((long_lines ? xinv_density_stokes_long : xinv_density_stokes_short)(CHAIN ? 1 : 0, ctx, ncomp, a, tile0, full));
     else if (CHAIN) KW_TRY((long_lines ? xinv_density_chain_long : xinv_density_chain_short)(TERMS, ctx, ncomp, a, tile0, full));
     else KW_TRY((long_lines ? xinv_density_plain_long : xinv_density_plain_short)(TERMS, ctx, ncomp, a, tile0, full));
   }
   if (rows % rows_per_tile != 0)
   {
     if (EPI != EPI_DENSITY) KW_TRY(xinv_other_tail(EPI, CHAIN ? 1 : 0, ctx, ncomp, a, tile0 + full, 1));
+    else if (TERMS == 4) KW_TRY(xinv_density_stokes_tail(CHAIN ? 1 : 0, ctx, ncomp, a, tile0 + full, 1));
     else KW_TRY((CHAIN ? xinv_density_chain_tail : xinv_density_plain_tail)(TERMS, ctx, ncomp, a, tile0 + full, 1));
   }
   return KW_OK;
@@ -1027,9 +1030,9 @@ kw_status kw_fused_density(kw_ctx* ctx, int nonlinear, const float* ux, const fl
   KW_REQUIRE(!chain_terms || terms != 0);
   KW_REQUIRE(ux && uy && uz && rx && ry && rz && pmlx && pmly && pmlz && kappa_padded && ddx && ddy && ddz);
   KW_REQUIRE((duxdx == nullptr) == (duydy == nullptr) && (duxdx == nullptr) == (duzdz == nullptr));
-  KW_REQUIRE(terms >= 0 && terms <= 3);
-  KW_REQUIRE(terms == 0 || terms == 3 || (t0 && t1 && (terms == 1 || t2)));
-  KW_REQUIRE(terms != 3 || t0 != nullptr);
+  KW_REQUIRE(terms >= 0 && terms <= 4);
+  KW_REQUIRE(terms == 0 || terms >= 3 || (t0 && t1 && (terms == 1 || t2)));
+  KW_REQUIRE(terms < 3 || t0 != nullptr);
   float2** S = ctx->fused.s;
   const float* in3[3] = { ux, uy, uz };
   ZArgs z{};
@@ -1058,7 +1061,8 @@ kw_status kw_fused_density(kw_ctx* ctx, int nonlinear, const float* ux, const fl
   for (int i = 0; i < 3; i++) { x.in[i] = S[i]; x.out[i] = rho[i]; x.m1[i] = pml[i]; x.aux[i] = du[i]; x.t[i] = t[i]; }
   x.m0[0]     = rho0;
   x.m0[1]     = bona;
-  x.m0[2]     = (terms == 3) ? t1 : nullptr; // lossless pressure: t0 = p (out), t1 = c2 array or NULL (in)
+  x.m0[2]     = (terms >= 3) ? t1 : nullptr; // lossless / Stokes pressure: t0 = p (out), t1 = c2 array or NULL (in),
+                                             // Stokes: t2 = absorb_tau array or NULL (in; travels as x.t[2], never written)
   x.nonlinear = nonlinear;
   x.terms     = terms;
   x.fout[0]   = S[0]; // chained: x-spectrum of rho0 * sum(du)
@@ -1068,12 +1072,12 @@ kw_status kw_fused_density(kw_ctx* ctx, int nonlinear, const float* ux, const fl
   do {                                                                                                                 \
     if (tail_chunked)                                                                                                  \
     {                                                                                                                  \
-      if (chain_terms) KW_TRY((plane_local_tail<EPI_DENSITY, true, (T) == 0 ? 1 : (T)>(ctx, 3, 1, x, (T) == 3 ? 1 : 2))); \
+      if (chain_terms) KW_TRY((plane_local_tail<EPI_DENSITY, true, (T) == 0 ? 1 : (T)>(ctx, 3, 1, x, (T) >= 3 ? 1 : 2))); \
       else KW_TRY((plane_local_tail<EPI_DENSITY, false, (T)>(ctx, 3, 1, x, 0)));                                       \
     }                                                                                                                  \
     else if (ctx->fused.pipelined)                                                                                     \
     {                                                                                                                  \
-      if (chain_terms) KW_TRY((pslab_tail<EPI_DENSITY, true, (T) == 0 ? 1 : (T)>(ctx, 3, 1, x, (T) == 3 ? 1 : 2)));    \
+      if (chain_terms) KW_TRY((pslab_tail<EPI_DENSITY, true, (T) == 0 ? 1 : (T)>(ctx, 3, 1, x, (T) >= 3 ? 1 : 2)));    \
       else KW_TRY((pslab_tail<EPI_DENSITY, false, (T)>(ctx, 3, 1, x, 0)));                                             \
     }                                                                                                                  \
     else if (chain_terms) KW_TRY((launch_xinv<EPI_DENSITY, true, (T) == 0 ? 1 : (T)>(ctx, 1, x)));                      \
@@ -1084,7 +1088,8 @@ kw_status kw_fused_density(kw_ctx* ctx, int nonlinear, const float* ux, const fl
     case 0: DENSITY_TAIL(0); break; // (chain_terms requires terms != 0: checked above)
     case 1: DENSITY_TAIL(1); break;
     case 2: DENSITY_TAIL(2); break;
-    default: DENSITY_TAIL(3); break;
+    case 3: DENSITY_TAIL(3); break;
+    default: DENSITY_TAIL(4); break;
   }
 #undef DENSITY_TAIL
   return KW_OK;

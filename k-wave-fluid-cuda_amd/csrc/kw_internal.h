@@ -174,6 +174,22 @@ void kw_set_error(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
     if (st_ != KW_OK) return st_;                                                                                      \
   } while (0)
 
+// Stokes absorption (absorbing_flag == 2, alpha_power == 2): the equation of state that the density epilogue of the fused
+// pipeline (terms == 4) and kw_sum_pressure_stokes_* both evaluate, in one fp32 association order (kwave_hip.h) and
+// without contraction into fma, so that every kernel form gives the same bits:
+//   absorb = tau * (rho0 * duSum);  first = rhoSum  |  ((bOnA * rhoSum) * rhoSum) / (2 * rho0) + rhoSum;  p = c2 * (first + absorb)
+#ifdef __HIPCC__
+__device__ __forceinline__ float kw_stokes_pressure(bool nonlinear, float c2, float tau, float rho0, float bOnA, float rhoSum,
+                                                    float duSum)
+{
+#pragma clang fp contract(off)
+  const float absorb = tau * (rho0 * duSum);
+  float first = rhoSum;
+  if (nonlinear) first = (((bOnA * rhoSum) * rhoSum) / (2.0f * rho0)) + rhoSum;
+  return c2 * (first + absorb);
+}
+#endif
+
 // checked right after each launch, without synchronising (reference: cudaCheckErrors(cudaGetLastError()))
 #define KW_LAUNCH_CHECK() KW_HIP(hipGetLastError())
 

@@ -340,6 +340,42 @@ __global__ __launch_bounds__(256) void k_sum_pressure_linear_lossless(kw_constan
   Vec<V>::store(p + i, o);
 }
 
+// Stokes absorption (alpha_power == 2; no counterpart in the reference): the equation of state on the densities and the
+// velocity gradients of this step, kw_stokes_pressure (kw_internal.h) — the arithmetic of the fused density epilogue, terms == 4.
+// NULL medium pointers select the scalars (wave-uniform branches of a bandwidth-bound kernel: no template forms).
+template<int V, bool kNonlinear>
+__global__ __launch_bounds__(256) void k_sum_pressure_stokes(kw_constants c, float* __restrict__ p, const float* __restrict__ rx,
+                                                              const float* __restrict__ ry, const float* __restrict__ rz,
+                                                              const float* __restrict__ dux, const float* __restrict__ duy,
+                                                              const float* __restrict__ duz, const float* __restrict__ c2,
+                                                              const float* __restrict__ bona, const float* __restrict__ rho0,
+                                                              const float* __restrict__ tau)
+{
+  size_t i;
+  if (!flat_index<V>(c.n_elements, i)) return;
+  using VT = typename Vec<V>::T;
+  const VT vrx = Vec<V>::load(rx + i), vry = Vec<V>::load(ry + i), vrz = Vec<V>::load(rz + i);
+  const VT vdx = Vec<V>::load(dux + i), vdy = Vec<V>::load(duy + i), vdz = Vec<V>::load(duz + i);
+  VT vc{}, vb{}, vr0{}, vtau{};
+  if (c2 != nullptr) vc = Vec<V>::load(c2 + i);
+  if (kNonlinear && bona != nullptr) vb = Vec<V>::load(bona + i);
+  if (rho0 != nullptr) vr0 = Vec<V>::load(rho0 + i);
+  if (tau != nullptr) vtau = Vec<V>::load(tau + i);
+  VT o;
+#pragma unroll
+  for (int k = 0; k < V; k++)
+  {
+    const float ec2    = (c2 != nullptr) ? get(vc, k) : c.c2;
+    const float eb     = (kNonlinear && bona != nullptr) ? get(vb, k) : c.b_on_a;
+    const float er0    = (rho0 != nullptr) ? get(vr0, k) : c.rho0;
+    const float etau   = (tau != nullptr) ? get(vtau, k) : c.absorb_tau;
+    const float rhoSum = get(vrx, k) + get(vry, k) + get(vrz, k);
+    const float duSum  = get(vdx, k) + get(vdy, k) + get(vdz, k);
+    put(o, k, kw_stokes_pressure(kNonlinear, ec2, etau, er0, eb, rhoSum, duSum));
+  }
+  Vec<V>::store(p + i, o);
+}
+
 // SolverCudaKernels.cu:864-884
 template<int V, bool kC2Scalar>
 __global__ __launch_bounds__(256) void k_add_initial_pressure_source(kw_constants c, float* __restrict__ p,
@@ -1107,6 +1143,37 @@ kw_status kw_sum_pressure_linear_lossless(kw_ctx* ctx, float* p, const float* rx
     else    LAUNCH((k_sum_pressure_linear_lossless<1, true>), g, dim3(256), c, p, rx, ry, rz, c2);
   }
   return KW_OK;
+}
+
+static kw_status sum_stokes_impl(bool nonlinear, kw_ctx* ctx, const char* name, float* p, const float* rx, const float* ry, const float* rz,
+                                 const float* dux, const float* duy, const float* duz, const float* c2, const float* bona,
+                                 const float* rho0, const float* tau)
+{
+  KW_CHECK_CONSTS(ctx);
+  KW_PROF(ctx, name);
+  KW_REQUIRE(p && rx && ry && rz && dux && duy && duz);
+  const kw_constants& c = ctx->c;
+  const bool v4 = c.n_elements % 4 == 0 && all_aligned16(p, rx, ry, rz, dux, duy, duz, c2, bona, rho0, tau);
+  const dim3 g  = v4 ? grid1d(c.n_elements / 4) : grid1d(c.n_elements);
+#define SPS(V, N) LAUNCH((k_sum_pressure_stokes<V, N>), g, dim3(256), c, p, rx, ry, rz, dux, duy, duz, c2, bona, rho0, tau)
+  if (v4) { if (nonlinear) SPS(4, true); else SPS(4, false); }
+  else    { if (nonlinear) SPS(1, true); else SPS(1, false); }
+#undef SPS
+  return KW_OK;
+}
+
+kw_status kw_sum_pressure_stokes_nonlinear(kw_ctx* ctx, float* p, const float* rx, const float* ry, const float* rz,
+                                           const float* duxdx, const float* duydy, const float* duzdz, const float* c2,
+                                           const float* bona, const float* rho0, const float* tau)
+{
+  return sum_stokes_impl(true, ctx, "sum_pressure_stokes_nonlinear", p, rx, ry, rz, duxdx, duydy, duzdz, c2, bona, rho0, tau);
+}
+
+kw_status kw_sum_pressure_stokes_linear(kw_ctx* ctx, float* p, const float* rx, const float* ry, const float* rz,
+                                        const float* duxdx, const float* duydy, const float* duzdz, const float* c2,
+                                        const float* rho0, const float* tau)
+{
+  return sum_stokes_impl(false, ctx, "sum_pressure_stokes_linear", p, rx, ry, rz, duxdx, duydy, duzdz, c2, nullptr, rho0, tau);
 }
 
 kw_status kw_compute_velocity_shift(kw_ctx* ctx, int axis, float* spectrum, const float* shift)

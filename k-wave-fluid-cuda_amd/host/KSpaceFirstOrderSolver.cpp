@@ -207,7 +207,12 @@ template<SD sd> void KSpaceFirstOrderSolver::preProcessing()
     real(MI::kDtRho0Sgy).scalarDividedBy(mParameters.getDt());
     real(MI::kDtRho0Sgz).scalarDividedBy(mParameters.getDt());
   }
-  if (mParameters.getAbsorbingFlag() != 0)
+  if (mParameters.isStokesAbsorption())
+  { // tau alone: nabla1 = k^0 = 1 and eta ~ tan(pi) = 0 are not represented
+    generateKappa();
+    generateTauAndEta();
+  }
+  else if (mParameters.getAbsorbingFlag() != 0)
   {
     generateKappaAndNablas();
     generateTauAndEta();
@@ -573,15 +578,17 @@ void KSpaceFirstOrderSolver::fusedDensity(bool nonlinear)
 {
   const MatrixContainer& c = mMatrixContainer;
   const bool absorbing     = mParameters.getAbsorbingFlag() != 0;
+  const bool stokes        = mParameters.isStokesAbsorption();
   const bool pSourceActive = mParameters.getPressureSourceFlag() > mParameters.getTimeIndex();
-  mTermsFused              = absorbing && !pSourceActive;
-  // lossless media: the equation of state (computePressure*'s lossless branch) is part of the density kernel, and the
-  // spectrum of the new p is chained unless p is about to be overwritten by the initial pressure source (step 0)
-  mPressureFused           = !absorbing && !pSourceActive;
+  mTermsFused              = absorbing && !stokes && !pSourceActive;
+  // lossless media and Stokes absorption: the equation of state (computePressure*'s element-wise branches) is part of the
+  // density kernel, and the spectrum of the new p is chained unless p is about to be overwritten by the initial pressure
+  // source (step 0)
+  mPressureFused           = (!absorbing || stokes) && !pSourceActive;
   const bool chainP        = mPressureFused &&
                              !((mParameters.getTimeIndex() == 0) && (mParameters.getInitialPressureSourceFlag() == 1));
   const bool storeDu       = absorbing && pSourceActive; // the stand-alone terms kernel will need the gradients
-  const int  terms         = mTermsFused ? (nonlinear ? 2 : 1) : (mPressureFused ? 3 : 0);
+  const int  terms         = mTermsFused ? (nonlinear ? 2 : 1) : (mPressureFused ? (stokes ? 4 : 3) : 0);
   const int  flags         = (mVelocityChained ? KW_FUSED_U_IN_SCRATCH : 0) |
                              ((mTermsFused || chainP) ? KW_FUSED_CHAIN_TERMS : 0);
   // aliasing of the temporaries as in :2184-2190 (nonlinear) / :2221-2225 (linear)
@@ -592,6 +599,7 @@ void KSpaceFirstOrderSolver::fusedDensity(bool nonlinear)
   {
     t0 = getP().getDeviceData();
     t1 = const_cast<float*>(c.realDeviceOrNull(MI::kC2)); // input in this mode (see kw_fused_density)
+    if (stokes) t2 = const_cast<float*>(c.realDeviceOrNull(MI::kAbsorbTau)); // input too
     mPressureInScratch = chainP;
   }
   kwCheck(kw_fused_density(mParameters.getHipParameters().getContext(), nonlinear ? 1 : 0,
@@ -630,7 +638,11 @@ template<SD sd> void KSpaceFirstOrderSolver::computeDensityLinear()
 
 template<SD sd> void KSpaceFirstOrderSolver::computePressureNonlinear()
 { // :2180-2210
-  if (mParameters.getAbsorbingFlag())
+  if (mParameters.isStokesAbsorption())
+  {
+    if (!(mFused && mPressureFused)) SolverHipKernels::sumPressureStokesNonlinear(mMatrixContainer);
+  }
+  else if (mParameters.getAbsorbingFlag())
   {
     RealMatrix& densitySum          = getTemp1RealND();
     RealMatrix& nonlinearTerm       = getTemp2RealND();
@@ -669,7 +681,11 @@ template<SD sd> void KSpaceFirstOrderSolver::computePressureNonlinear()
 
 template<SD sd> void KSpaceFirstOrderSolver::computePressureLinear()
 { // :2217-2245
-  if (mParameters.getAbsorbingFlag())
+  if (mParameters.isStokesAbsorption())
+  {
+    if (!(mFused && mPressureFused)) SolverHipKernels::sumPressureStokesLinear(mMatrixContainer);
+  }
+  else if (mParameters.getAbsorbingFlag())
   {
     RealMatrix& densitySum           = getTemp1RealND();
     RealMatrix& velocityGradientTerm = getTemp2RealND();
@@ -985,6 +1001,8 @@ void KSpaceFirstOrderSolver::generateKappaAndNablas()
 
 void KSpaceFirstOrderSolver::generateTauAndEta()
 { // tau = -2 a c0^(y-1),  eta = 2 a c0^y tan(pi y / 2),  a = alpha_coeff * 100 (1e-6 / 2 pi)^y / (20 log10 e)  [Np]
+  // Stokes absorption (y == 2): tau alone — the same expression; eta is neither stored nor used
+  const bool  stokes  = mParameters.isStokesAbsorption();
   const float power   = mParameters.getAlphaPower();
   const float tanTerm = std::tan(static_cast<float>(M_PI_2) * power);
   const float neper   = (100.0f * std::pow(1.0e-6f / (2.0f * static_cast<float>(M_PI)), power)) / (20.0f * static_cast<float>(M_LOG10E));
@@ -993,7 +1011,7 @@ void KSpaceFirstOrderSolver::generateTauAndEta()
   {
     const float a2 = 2.0f * mParameters.getAlphaCoeffScalar() * neper;
     mParameters.setAbsorbTauScalar((-a2) * std::pow(mParameters.getC0Scalar(), power - 1));
-    mParameters.setAbsorbEtaScalar(a2 * std::pow(mParameters.getC0Scalar(), power) * tanTerm);
+    mParameters.setAbsorbEtaScalar(stokes ? 0.0f : a2 * std::pow(mParameters.getC0Scalar(), power) * tanTerm);
     return;
   }
   // per voxel as soon as either operand is an array; alpha_coeff was loaded into Temp1, the c2 matrix still holds c0
@@ -1002,7 +1020,7 @@ void KSpaceFirstOrderSolver::generateTauAndEta()
   const float  alphaScalar = alphaIsScalar ? mParameters.getAlphaCoeffScalar() : 0.0f;
   const float  c0Scalar    = c0IsScalar ? mParameters.getC0Scalar() : 0.0f;
   float* tau = real(MI::kAbsorbTau).getHostData();
-  float* eta = real(MI::kAbsorbEta).getHostData();
+  float* eta = stokes ? nullptr : real(MI::kAbsorbEta).getHostData();
   const size_t n = mParameters.getFullDimensionSizes().nElements();
 #pragma omp parallel for schedule(static)
   for (size_t i = 0; i < n; i++)
@@ -1010,7 +1028,7 @@ void KSpaceFirstOrderSolver::generateTauAndEta()
     const float a2 = 2.0f * neper * (alpha ? alpha[i] : alphaScalar);
     const float c  = c0 ? c0[i] : c0Scalar;
     tau[i] = (-a2) * std::pow(c, power - 1.0f);
-    eta[i] = a2 * std::pow(c, power) * tanTerm;
+    if (eta != nullptr) eta[i] = a2 * std::pow(c, power) * tanTerm;
   }
 }
 

@@ -58,6 +58,9 @@ bool nonUniformScalarRho0(const P& p) { return nonUniform(p) && p.getRho0ScalarF
 bool bOnAArray(const P& p) { return p.getNonLinearFlag() && !p.getBOnAScalarFlag(); }
 bool absorbing(const P& p) { return p.getAbsorbingFlag() != 0; }
 bool absorbingArrays(const P& p) { return absorbing(p) && !(p.getC0ScalarFlag() && p.getAlphaCoeffScalarFlag()); }
+// Stokes absorption needs tau alone: no eta, no nabla spectra
+bool powerLaw(const P& p) { return p.getAbsorptionType() == P::AbsorptionType::kPowerLaw; }
+bool powerLawArrays(const P& p) { return powerLaw(p) && absorbingArrays(p); }
 bool alphaCoeffArray(const P& p) { return absorbing(p) && !p.getAlphaCoeffScalarFlag(); }
 bool noAlphaCoeffArray(const P& p) { return !alphaCoeffArray(p); }
 bool indexMask(const P& p) { return p.getSensorMaskType() == P::SensorMaskType::kIndex && p.getSensorMaskIndexSize() > 0; }
@@ -139,9 +142,9 @@ const Row kSchema[] = {
   GRID(kDtRho0Sgz, 0, "dt_rho0_sgz_nonuniform", nonUniformScalarRho0),
   GRID(kBOnA, kFromFile, kBonAName, bOnAArray),
   GRID(kAbsorbTau, 0, "absorb_tau", absorbingArrays),
-  GRID(kAbsorbEta, 0, "absorb_eta", absorbingArrays),
-  { MI::kAbsorbNabla1, MT::kReal, Extent::kSpectrum, nullptr, 0, "absorb_nabla1_r", absorbing },
-  { MI::kAbsorbNabla2, MT::kReal, Extent::kSpectrum, nullptr, 0, "absorb_nabla2_r", absorbing },
+  GRID(kAbsorbEta, 0, "absorb_eta", powerLawArrays),
+  { MI::kAbsorbNabla1, MT::kReal, Extent::kSpectrum, nullptr, 0, "absorb_nabla1_r", powerLaw },
+  { MI::kAbsorbNabla2, MT::kReal, Extent::kSpectrum, nullptr, 0, "absorb_nabla2_r", powerLaw },
   { MI::kSourceKappa, MT::kReal, Extent::kSpectrum, nullptr, 0, "source_kappa_r", kSpaceCorrectedSource },
   { MI::kDdxKShiftPosR, MT::kComplex, Extent::kSpectrumX, nullptr, kFromFile, kDdxKShiftPosRName, always },
   { MI::kDdyKShiftPos, MT::kComplex, Extent::kSpectrumY, nullptr, kFromFile, kDdyKShiftPosName, always },

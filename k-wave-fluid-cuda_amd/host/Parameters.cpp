@@ -164,6 +164,9 @@ void Parameters::init(const InputProvider& in, const Options& options)
   {
     in.readScalarValue(kAlphaPowerName, mAlphaPower);
     if (mAlphaPower == 1.0f) throw std::invalid_argument("Error: Illegal value of alpha_power (must not equal to 1.0)");
+    if (isStokesAbsorption() && mAlphaPower != 2.0f)
+      throw std::invalid_argument(std::string("Error: Illegal value of ") + kAlphaPowerName + " (" + std::to_string(mAlphaPower) +
+                                  "): " + kAbsorbingFlagName + " = 2 (Stokes absorption) needs " + kAlphaPowerName + " = 2");
     mAlphaCoeffScalarFlag = in.getDatasetDimensionSizes(kAlphaCoeffName) == scalarSizes;
     if (mAlphaCoeffScalarFlag) in.readScalarValue(kAlphaCoeffName, mAlphaCoeffScalar);
   }

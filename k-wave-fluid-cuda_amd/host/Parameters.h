@@ -160,6 +160,14 @@ class Parameters
 
   size_t getNonUniformGridFlag() const { return mNonUniformGridFlag; }
   size_t getAbsorbingFlag() const { return mAbsorbingFlag; }
+  // absorbing_flag of the input file: 0 lossless, 2 Stokes absorption (k-Wave's alpha_mode = 'stokes': alpha_power == 2, the
+  // equation of state is element-wise and the step has no absorption FFT stage), anything else the power law
+  enum class AbsorptionType { kNone, kPowerLaw, kStokes };
+  AbsorptionType getAbsorptionType() const
+  {
+    return (mAbsorbingFlag == 0) ? AbsorptionType::kNone : (mAbsorbingFlag == 2) ? AbsorptionType::kStokes : AbsorptionType::kPowerLaw;
+  }
+  bool   isStokesAbsorption() const { return getAbsorptionType() == AbsorptionType::kStokes; }
   size_t getNonLinearFlag() const { return mNonLinearFlag; }
   bool   getBOnAScalarFlag() const { return mBOnAScalarFlag; }
   float  getBOnAScalar() const { return mBOnAScalar; }

@@ -153,6 +153,20 @@ void sumPressureTermsLinear(const RealMatrix& absorbTauTerm, const RealMatrix& a
                                        c.realDeviceOrNull(MI::kC2), c.realDeviceOrNull(MI::kAbsorbTau),
                                        c.realDeviceOrNull(MI::kAbsorbEta)));
 }
+void sumPressureStokesNonlinear(const MatrixContainer& c)
+{
+  kwCheck(kw_sum_pressure_stokes_nonlinear(ctx(), real(c, MI::kP), real(c, MI::kRhoX), real(c, MI::kRhoY), real(c, MI::kRhoZ),
+                                           real(c, MI::kDuxdx), real(c, MI::kDuydy), real(c, MI::kDuzdz),
+                                           c.realDeviceOrNull(MI::kC2), c.realDeviceOrNull(MI::kBOnA),
+                                           c.realDeviceOrNull(MI::kRho0), c.realDeviceOrNull(MI::kAbsorbTau)));
+}
+void sumPressureStokesLinear(const MatrixContainer& c)
+{
+  kwCheck(kw_sum_pressure_stokes_linear(ctx(), real(c, MI::kP), real(c, MI::kRhoX), real(c, MI::kRhoY), real(c, MI::kRhoZ),
+                                        real(c, MI::kDuxdx), real(c, MI::kDuydy), real(c, MI::kDuzdz),
+                                        c.realDeviceOrNull(MI::kC2), c.realDeviceOrNull(MI::kRho0),
+                                        c.realDeviceOrNull(MI::kAbsorbTau)));
+}
 template<SD sd> void sumPressureNonlinearLossless(const MatrixContainer& c)
 {
   kwCheck(kw_sum_pressure_nonlinear_lossless(ctx(), real(c, MI::kP), real(c, MI::kRhoX), real(c, MI::kRhoY),

@@ -45,6 +45,9 @@ void sumPressureTermsNonlinear(const RealMatrix& nonlinearTerm, const RealMatrix
                                const RealMatrix& absorbEtaTerm, const MatrixContainer& container);
 void sumPressureTermsLinear(const RealMatrix& absorbTauTerm, const RealMatrix& absorbEtaTerm,
                             const RealMatrix& densitySum, const MatrixContainer& container);
+// Stokes absorption: the element-wise equation of state on the densities and the stored velocity gradients
+void sumPressureStokesNonlinear(const MatrixContainer& container);
+void sumPressureStokesLinear(const MatrixContainer& container);
 template<SD simulationDimension = SD::k3D> void sumPressureNonlinearLossless(const MatrixContainer& container);
 template<SD simulationDimension = SD::k3D> void sumPressureLinearLossless(const MatrixContainer& container);
 void computeVelocityShiftInX(HipFftComplexMatrix& fftShiftTemp, const ComplexMatrix& xShiftNegR);

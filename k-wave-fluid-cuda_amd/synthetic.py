@@ -126,7 +126,7 @@ def make_problem(nx: int, ny: Optional[int] = None, nz: Optional[int] = None, *,
                  source_mode: int = 0, source_many: int = 0, sensor: str = "plane",
                  hetero_subset: Optional[dict] = None, seed: int = 0x5EED1234,
                  nt_src: Optional[int] = None, zslab: Optional[tuple] = None,
-                 nonuniform: bool = False) -> Dict[str, np.ndarray]:
+                 nonuniform: bool = False, stokes: bool = False) -> Dict[str, np.ndarray]:
     """Build one synthetic problem.
 
     source: "p0" (1 MPa Gaussian ball), "p_source" (1 MHz tone burst on plane x=12),
@@ -134,6 +134,8 @@ def make_problem(nx: int, ny: Optional[int] = None, nz: Optional[int] = None, *,
     hetero_subset: optionally {"c0": bool, "rho0": bool, "BonA": bool, "alpha_coeff": bool} to mix
             scalar / array medium parameters (detected per dataset by shape in the reference:
             /root/reference/Parameters/Parameters.cpp:426-459).
+    stokes: with absorbing, Stokes absorption (k-Wave's alpha_mode = 'stokes'): alpha_power = 2 and absorbing_flag = 2 —
+            the run whose reference is the power law itself at alpha_power = 2 (stokes_as_power_law).
     zslab:  (z_lo, z_hi): build the 3-D arrays only for planes z_lo <= z < z_hi (multi-GPU runs generate their own
             slab; every other dataset — scalars, operators, PML vectors, index masks — stays global and is cut to
             the slab by dist.partition_problem(..., arrays_are_local=True)).
@@ -186,7 +188,7 @@ def make_problem(nx: int, ny: Optional[int] = None, nz: Optional[int] = None, *,
     if absorbing:
         pr["alpha_coeff"] = (_full(0.75 + 0.25 * np.cos(two_pi * x / nx), shape, nzl)
                              if het["alpha_coeff"] else scalar_f(0.75))
-        pr["alpha_power"] = scalar_f(1.5)
+        pr["alpha_power"] = scalar_f(2.0 if stokes else 1.5)
 
     dt = float(F32(cfl * dx / c_ref))
 
@@ -207,7 +209,9 @@ def make_problem(nx: int, ny: Optional[int] = None, nz: Optional[int] = None, *,
             pr[f"d{ax}ud{ax}n"] = (1.0 + 0.15 * np.sin(two_pi * t / nn)).astype(F32).reshape(shape)
             pr[f"d{ax}ud{ax}n_sg{ax}"] = (1.0 + 0.15 * np.sin(two_pi * (t + 0.5) / nn)).astype(F32).reshape(shape)
     pr["nonlinear_flag"] = scalar_u(int(nonlinear))
-    pr["absorbing_flag"] = scalar_u(int(absorbing))
+    if stokes and not absorbing:
+        raise ValueError("stokes needs absorbing=True")
+    pr["absorbing_flag"] = scalar_u(2 if (absorbing and stokes) else int(absorbing))
 
     # ---- operators + PML ----------------------------------------------------------------------
     pr.update(kspace_operators(nx, ny, nz, dx, dy, dz))
@@ -294,6 +298,16 @@ def make_problem(nx: int, ny: Optional[int] = None, nz: Optional[int] = None, *,
         raise ValueError(sensor)
     pr["sensor_mask_index"] = (lin.astype(U64) + U64(1)).reshape(1, 1, -1)
     return pr
+
+
+def stokes_as_power_law(pr: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
+    """The same problem with absorbing_flag = 1: the power law at alpha_power = 2, which is what a Stokes problem
+    (absorbing_flag = 2) computes — nabla1 = |k|^0 = 1 and eta ~ tan(pi) = 0 — and therefore its reference."""
+    if int(np.asarray(pr["absorbing_flag"]).ravel()[0]) != 2:
+        raise ValueError("not a Stokes problem")
+    out = dict(pr)
+    out["absorbing_flag"] = np.array([[[1]]], dtype=U64)
+    return out
 
 
 def is_scalar(a: np.ndarray) -> bool:
