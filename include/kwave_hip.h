@@ -290,6 +290,21 @@ KW_API kw_status kw_sum_pressure_terms_nonlinear(kw_ctx* ctx, float* p, const fl
 KW_API kw_status kw_sum_pressure_terms_linear(kw_ctx* ctx, float* p, const float* absorb_tau_term,
                                               const float* absorb_eta_term, const float* density_sum, const float* c2,
                                               const float* absorb_tau, const float* absorb_eta);
+/* One-term power-law absorption (new with this build; k-Wave's medium.alpha_mode = 'no_dispersion', absorbing_flag = 3:
+ * eta = 0; = 'no_absorption', absorbing_flag = 4: tau = 0): the two-term sum above with the absent product removed, every
+ * fp32 product and sum rounded on its own (no fma contraction), in this order:
+ *   which == 0 (no_dispersion):  p = c2 * (first + (fft_divider * (term * coef)))   coef = absorb_tau
+ *   which == 1 (no_absorption):  p = c2 * (first - (fft_divider * (term * coef)))   coef = absorb_eta
+ * For finite inputs that is the two-term sum with the other coefficient exactly 0.  term = the inverse transform of
+ * nabla1 * F{rho0 * sum du} (which == 0) or of nabla2 * F{sum rho} (which == 1); first = the nonlinear term or the density
+ * sum.  c2 / coef NULL -> the scalars of kw_constants (coef: absorb_tau or absorb_eta by `which`).
+ * kw_fused_absorption_pressure_one evaluates the same expression (same bits) in its x-inverse epilogue. */
+KW_API kw_status kw_compute_absorbtion_term_one(kw_ctx* ctx, float* fft_part, const float* absorb_nabla);
+KW_API kw_status kw_sum_pressure_terms_one_nonlinear(kw_ctx* ctx, float* p, const float* nonlinear_term,
+                                                     const float* absorb_term, const float* c2, const float* coef,
+                                                     int which);
+KW_API kw_status kw_sum_pressure_terms_one_linear(kw_ctx* ctx, float* p, const float* absorb_term,
+                                                  const float* density_sum, const float* c2, const float* coef, int which);
 /* sumPressureNonlinearLossless (.cuh:429, .cu:2067-2200) */
 KW_API kw_status kw_sum_pressure_nonlinear_lossless(kw_ctx* ctx, float* p, const float* rho_x, const float* rho_y,
                                                     const float* rho_z, const float* c2, const float* b_on_a,
@@ -449,7 +464,13 @@ KW_API kw_status kw_fused_initial_velocity(kw_ctx* ctx, const float* p, float* u
  * KW_FUSED_CHAIN_TERMS the spectrum of the new p is left for kw_fused_velocity(KW_FUSED_P_IN_SCRATCH).
  * terms==4 (Stokes absorption, alpha_power == 2): as terms==3 with the absorbing term of kw_sum_pressure_stokes_* (same
  * association order, same bits) on the gradients of this step: t0 = p (output), t1 = c2 array or NULL, t2 = absorb_tau
- * array or NULL (both INPUTS, not written; NULL -> the scalar of kw_constants); chains the spectrum of p like terms==3. */
+ * array or NULL (both INPUTS, not written; NULL -> the scalar of kw_constants); chains the spectrum of p like terms==3.
+ * terms==5 (one-term power law, no_dispersion) and terms==6 (no_absorption): the terms of 1 / 2 that
+ * kw_fused_absorption_pressure_one reads, and no others.  `first` goes where 1 / 2 put it: t0 = sum rho (linear), t1 =
+ * nonlinear term (nonlinear).  The one term of the absorption round trip goes where 1 / 2 put it as well: terms==5,
+ * rho0 * sum du into t1 (linear) / t2 (nonlinear); terms==6, sum rho into t0 (rho0 * sum du is not computed).  With
+ * KW_FUSED_CHAIN_TERMS that one term is not stored: its x-spectrum is left in scratch for
+ * kw_fused_absorption_pressure_one(KW_FUSED_TERMS_IN_SCRATCH), and only `first` is written.  Unused t arrays may be NULL. */
 KW_API kw_status kw_fused_density(kw_ctx* ctx, int nonlinear, const float* ux_sgx, const float* uy_sgy,
                                   const float* uz_sgz, float* rho_x, float* rho_y, float* rho_z, const float* pml_x,
                                   const float* pml_y, const float* pml_z, const float* rho0,
@@ -469,6 +490,13 @@ KW_API kw_status kw_fused_absorption_pressure(kw_ctx* ctx, float* p, const float
                                               const float* density_sum, const float* first,
                                               const float* nabla1_padded, const float* nabla2_padded, const float* c2,
                                               const float* absorb_tau, const float* absorb_eta, int flags);
+/* the absorbing branch with one term (absorbing_flag 3 / 4; see kw_sum_pressure_terms_one_*): one forward transform of
+ * `term`, times nabla_padded (nabla1 for which == 0, nabla2 for which == 1), one inverse, then p = c2 * (first +- ...) with
+ * coef = absorb_tau / absorb_eta array or NULL for the scalar of kw_constants.  One exchange each way on slabs.  flags as
+ * for kw_fused_absorption_pressure (TERMS_IN_SCRATCH: the term's spectrum was chained by kw_fused_density(terms 5 / 6)). */
+KW_API kw_status kw_fused_absorption_pressure_one(kw_ctx* ctx, float* p, const float* term, const float* first,
+                                                  const float* nabla_padded, const float* c2, const float* coef,
+                                                  int which, int flags);
 #define KW_FUSED_TERMS_IN_SCRATCH 1 /* kw_fused_absorption_pressure: the two terms' spectra were chained by kw_fused_density */
 #define KW_FUSED_CHAIN_P          2 /* ... and the kernel that writes p forward-transforms it for the next kw_fused_velocity */
 /* tuning probe: one pass of the pipeline over its scratch (0 y-pass, 1 line pass along z, 2 z-fused, 3 y-pass x3) */

@@ -26,7 +26,9 @@ SLOWEST_FIRST = ("kw_fused_xinv_other.hip", "kw_fused_main.hip", "kw_fused_xinv_
                  "kw_fused_xinv_density_chain_tail.hip", "kw_fused_xinv_other_tail.hip", "kw_fused_xinv_density_plain_long.hip",
                  "kw_fused_xinv_density_chain_long.hip", "kw_fused_xinv_density_stokes_tail.hip",
                  "kw_fused_xinv_density_chain_short.hip", "kw_fused_xinv_density_plain_short.hip",
-                 "kw_fused_xinv_density_stokes_long.hip", "kw_fused_xinv_density_stokes_short.hip")
+                 "kw_fused_xinv_density_oneterm_tail.hip", "kw_fused_xinv_psum_one_tail.hip", "kw_fused_xinv_psum_one.hip",
+                 "kw_fused_xinv_density_stokes_long.hip", "kw_fused_xinv_density_stokes_short.hip",
+                 "kw_fused_xinv_density_oneterm_long.hip", "kw_fused_xinv_density_oneterm_short.hip")
 # the fused pipeline's device code, which each of its code objects (kw_fused_*.hip) includes: no code object itself
 INCLUDED_ONLY = ("kw_fused.hip",)
 HIP_LIB = os.path.join(LIB_DIR, "libkwave_hip.so")

@@ -126,6 +126,9 @@ _SIG: Dict[str, list] = {
     "kw_sum_pressure_nonlinear_lossless": [_P] + [_P] * 7,
     "kw_sum_pressure_linear_lossless": [_P] + [_P] * 5,
     "kw_sum_pressure_stokes_nonlinear": [_P] + [_P] * 11,
+    "kw_compute_absorbtion_term_one": [_P, _P, _P],
+    "kw_sum_pressure_terms_one_nonlinear": [_P] + [_P] * 5 + [C.c_int],
+    "kw_sum_pressure_terms_one_linear": [_P] + [_P] * 5 + [C.c_int],
     "kw_sum_pressure_stokes_linear": [_P] + [_P] * 10,
     "kw_compute_velocity_shift": [_P, C.c_int, _P, _P],
     "kw_measure_copy_bandwidth": [_P, C.c_size_t, C.c_int, C.POINTER(C.c_double)],
@@ -158,6 +161,7 @@ _SIG: Dict[str, list] = {
     "kw_fused_density": [_P, C.c_int] + [_P] * 14 + [_P] * 3 + [C.c_int, _P, _P, _P, _P, C.c_int],
     "kw_fused_velocity_gradient": [_P] + [_P] * 10 + [C.c_int],
     "kw_fused_absorption_pressure": [_P] + [_P] * 9 + [C.c_int],
+    "kw_fused_absorption_pressure_one": [_P] + [_P] * 6 + [C.c_int, C.c_int],
     "kw_fused_scale_source": [_P, _P, _P],
     "kw_fused_probe": [_P, C.c_int, _P],
     "kw_sample_index": [_P, C.c_int, _P, _P, _P, _U64],

@@ -111,14 +111,16 @@ struct XinvArgs
   // EPI_STORE: out[0]; EPI_VELOCITY/INITVEL: u[3], dtrho[3] (NULL -> scalar), pml[3]
   // EPI_DENSITY: rho[3] in/out, pml[3], rho0, bona, du[3] (optional store), t[3] terms outputs, flags
   // EPI_PSUM: p, first, c2, tau, eta
+  // EPI_PSUM1: p, first, c2, the one coefficient (tau or eta by `which`)
   float*        out[3];
   const float*  m0[3]; // dtrho / (rho0, bona, -) / (first, c2, -)
-  const float*  m1[3]; // pml / (tau, eta, -)
+  const float*  m1[3]; // pml / (tau, eta, -) / (tau or eta, -, -)
   float*        aux[3]; // du stores / -
   float*        t[3];  // pressure-term outputs
   int           nonlinear;
   int           terms; // 0 none, 1 linear (t0 = sum rho, t1 = rho0*sum du), 2 nonlinear (t0, t1 = nonlinear term, t2),
-                       // 3 lossless pressure (t0 = p, m0[2] = c2), 4 Stokes pressure (as 3, and t[2] = absorb_tau array or NULL: INPUT)
+                       // 3 lossless pressure (t0 = p, m0[2] = c2), 4 Stokes pressure (as 3, and t[2] = absorb_tau array or NULL: INPUT),
+                       // 5 one-term power law (`which` below; first -> t0 linear / t1 nonlinear; the one term as 1 / 2 place it)
   uint32_t      comp0; // first component of this launch (per-array launches)
   float2*       fout[3]; // CHAIN: where the forward x-transform of the epilogue's result goes (scratch rows)
   uint32_t      tile0;   // first 2*NL-row tile of this launch (chunked plane-local passes)
@@ -126,6 +128,8 @@ struct XinvArgs
   uint32_t      nrows;      // rows of the grid (ny * nz): bounds the partial last tile (TAIL kernels)
   uint32_t      side_off;   // element offset of the x-Nyquist side array in in[] / fout[] (0: none)
   const float2* ymul[3];    // PLANE kernels: optional factor ymul[ky] applied to array i before its y-inverse (ddy of the gradient)
+  int           which;      // one-term power law (density terms == 5, EPI_PSUM1), the same for every wave: 0 no_dispersion
+                            // (the term is rho0 * sum du, its coefficient tau), 1 no_absorption (sum rho, eta)
 };
 
 struct XshiftArgs
@@ -150,6 +154,15 @@ kw_status xinv_density_stokes_short(int chain, kw_ctx* ctx, int ncomp, const Xin
 kw_status xinv_density_stokes_long(int chain, kw_ctx* ctx, int ncomp, const XinvArgs& a, uint32_t tile0, uint32_t ntiles);
 kw_status xinv_density_stokes_tail(int chain, kw_ctx* ctx, int ncomp, const XinvArgs& a, uint32_t tile0, uint32_t ntiles);
 kw_status xinv_density_stokes_plane(int chain, kw_ctx* ctx, int ncomp, const XinvArgs& a, uint32_t plane0, uint32_t nplanes);
+// the one-term power law (absorbing_flag 3 / 4): its density epilogue (terms == 5; kw_fused_xinv_density_oneterm_*.hip) and
+// its pressure sum over one inverse (EPI_PSUM1; kw_fused_xinv_psum_one*.hip), plain and chained, in code objects of their own
+kw_status xinv_density_oneterm_short(int chain, kw_ctx* ctx, int ncomp, const XinvArgs& a, uint32_t tile0, uint32_t ntiles);
+kw_status xinv_density_oneterm_long(int chain, kw_ctx* ctx, int ncomp, const XinvArgs& a, uint32_t tile0, uint32_t ntiles);
+kw_status xinv_density_oneterm_tail(int chain, kw_ctx* ctx, int ncomp, const XinvArgs& a, uint32_t tile0, uint32_t ntiles);
+kw_status xinv_density_oneterm_plane(int chain, kw_ctx* ctx, int ncomp, const XinvArgs& a, uint32_t plane0, uint32_t nplanes);
+kw_status xinv_psum_one(int chain, kw_ctx* ctx, int ncomp, const XinvArgs& a, uint32_t tile0, uint32_t ntiles);
+kw_status xinv_psum_one_tail(int chain, kw_ctx* ctx, int ncomp, const XinvArgs& a, uint32_t tile0, uint32_t ntiles);
+kw_status xinv_psum_one_plane(int chain, kw_ctx* ctx, int ncomp, const XinvArgs& a, uint32_t plane0, uint32_t nplanes);
 kw_status xinv_other(int epi, int chain, kw_ctx* ctx, int ncomp, const XinvArgs& a, uint32_t tile0, uint32_t ntiles);
 kw_status xinv_other_tail(int epi, int chain, kw_ctx* ctx, int ncomp, const XinvArgs& a, uint32_t tile0, uint32_t ntiles);
 // whole-plane tiles (small grids, see k_xinv); with density-chain-short and other
@@ -1066,7 +1079,7 @@ template<int L, bool TAIL = false> __global__ __launch_bounds__(GeoX<L>::THREADS
 // =====================================================================================================================
 // x-inverse + epilogue
 // =====================================================================================================================
-enum Epi { EPI_STORE = 0, EPI_VELOCITY = 1, EPI_INITVEL = 2, EPI_DENSITY = 3, EPI_PSUM = 4 };
+enum Epi { EPI_STORE = 0, EPI_VELOCITY = 1, EPI_INITVEL = 2, EPI_DENSITY = 3, EPI_PSUM = 4, EPI_PSUM1 = 5 };
 
 
 // standalone inverse of one array for this block's 32 rows; the thread of role sb = XRole<G, R1> ends with
@@ -1342,7 +1355,7 @@ __global__ __launch_bounds__((Geo<L, PLANE ? L / 2 : nl_x(L)>::THREADS), (EPI ==
   // issued before the loads).  GQ is bounded by the register budget of each epilogue.
   // measured on one box: density 1 (2 spills registers: -1 %), pressure sum 2 (1 gives a fourth wave but -1.4 %),
   // velocity 4 (8: -1 %)
-  constexpr int GQ = gq_pick(NQ, (EPI == EPI_DENSITY) ? 1 : (EPI == EPI_PSUM) ? 2 : 4);
+  constexpr int GQ = gq_pick(NQ, (EPI == EPI_DENSITY) ? 1 : (EPI == EPI_PSUM || EPI == EPI_PSUM1) ? 2 : 4);
   // power-of-two rows: x is the same for every float4 of a thread (one PML-x load per thread); the 3 * 2^m rows whose
   // float4 count does not divide the block take x (and the PML-x operand) per float4
   constexpr bool XFIX = (G::THREADS % Q4 == 0);
@@ -1350,7 +1363,7 @@ __global__ __launch_bounds__((Geo<L, PLANE ? L / 2 : nl_x(L)>::THREADS), (EPI ==
   float4 pmlx4 = make_float4(1.f, 1.f, 1.f, 1.f);
   if (XFIX && ((EPI == EPI_VELOCITY && comp == 0) || EPI == EPI_DENSITY)) pmlx4 = ld4(a.m1[0] + xfix);
   const bool hetRho0 = (EPI == EPI_DENSITY) && (a.m0[0] != nullptr);
-  const bool hetBonA = (EPI == EPI_DENSITY) && (terms == 2 || ((terms == 3 || terms == 4) && a.nonlinear)) && (a.m0[1] != nullptr);
+  const bool hetBonA = (EPI == EPI_DENSITY) && (terms == 2 || ((terms == 3 || terms == 4 || terms == 5) && a.nonlinear)) && (a.m0[1] != nullptr);
   const bool hetC2   = (EPI == EPI_DENSITY) && (terms == 3 || terms == 4) && (a.m0[2] != nullptr);
   const bool hetTau  = (EPI == EPI_DENSITY) && (terms == 4) && (a.t[2] != nullptr);
 #pragma unroll
@@ -1396,6 +1409,12 @@ __global__ __launch_bounds__((Geo<L, PLANE ? L / 2 : nl_x(L)>::THREADS), (EPI ==
         if (a.m0[1] != nullptr) op1[g] = ld4(a.m0[1] + i);
         if (a.m1[0] != nullptr) op2[g] = ld4(a.m1[0] + i);
         if (a.m1[1] != nullptr) op3[g] = ld4(a.m1[1] + i);
+      }
+      else if (EPI == EPI_PSUM1)
+      {
+        op0[g] = ld4(a.m0[0] + i);
+        if (a.m0[1] != nullptr) op1[g] = ld4(a.m0[1] + i);
+        if (a.m1[0] != nullptr) op2[g] = ld4(a.m1[0] + i);
       }
     }
 #pragma unroll
@@ -1555,6 +1574,34 @@ __global__ __launch_bounds__((Geo<L, PLANE ? L / 2 : nl_x(L)>::THREADS), (EPI ==
           if (row_ok) st4(a.t[0] + i, pn);
           if constexpr (CHAIN) { if (e_ok) *reinterpret_cast<float4*>(&ldsr[(e / Q4) * RP + x]) = pn; }
         }
+        else if (terms == 5)
+        { // one-term power law: `first` goes where the pressure sum reads it (t0 linear, t1 nonlinear: as terms 1 and 2 put
+          // it) and ONE array takes the absorption round trip: rho0 * sum du (no_dispersion) or sum rho (no_absorption,
+          // where rho0 * sum du is not computed).  Chained, that array's row goes through the real tile like the first
+          // chained row of terms 1 / 2; plain, it is stored where terms 1 / 2 store it (t1 | t2, t0).
+          const float4 b4 = hetBonA ? op4[g] : make_float4(k.b_on_a, k.b_on_a, k.b_on_a, k.b_on_a);
+          float4 fi, tm;
+#pragma unroll
+          for (int t = 0; t < 4; t++)
+          {
+            const float eRhoSum = (f4get(nrx, t) + f4get(nry, t) + f4get(nrz, t));
+            if (a.nonlinear) f4put(fi, t, ((f4get(b4, t) * eRhoSum * eRhoSum) / (2.0f * f4get(r04, t))) + eRhoSum);
+            else f4put(fi, t, eRhoSum);
+            f4put(tm, t, eRhoSum);
+          }
+          if (a.which == 0)
+          {
+#pragma unroll
+            for (int t = 0; t < 4; t++) f4put(tm, t, f4get(r04, t) * (f4get(dux, t) + f4get(duy, t) + f4get(duz, t)));
+          }
+          if (row_ok) st4((a.nonlinear ? a.t[1] : a.t[0]) + i, fi);
+          if constexpr (CHAIN) { if (e_ok) *reinterpret_cast<float4*>(&ldsr[(e / Q4) * RP + x]) = tm; }
+          else
+          {
+            if (a.which == 0) { if (row_ok) st4((a.nonlinear ? a.t[2] : a.t[1]) + i, tm); }
+            else if (a.nonlinear) { if (row_ok) st4(a.t[0] + i, tm); } // (linear: sum rho is `first`, stored above)
+          }
+        }
         else if (terms == 1)
         { // :1733-1741
           float4 o0, o1;
@@ -1584,6 +1631,20 @@ __global__ __launch_bounds__((Geo<L, PLANE ? L / 2 : nl_x(L)>::THREADS), (EPI ==
         if (row_ok) st4(a.out[0] + i, o);
         if constexpr (CHAIN) fw[0][q] = o;
       }
+      else if (EPI == EPI_PSUM1)
+      { // the power law's sum with one term (kw_one_term_pressure, kw_internal.h): the arithmetic of kw_sum_pressure_terms_one_*
+        const float4 tm = res[0][q];
+        const float4 fi = op0[g];
+        const float  cs = a.which ? k.absorb_eta : k.absorb_tau;
+        const float4 c24 = (a.m0[1] != nullptr) ? op1[g] : make_float4(k.c2, k.c2, k.c2, k.c2);
+        const float4 co4 = (a.m1[0] != nullptr) ? op2[g] : make_float4(cs, cs, cs, cs);
+        float4 o;
+#pragma unroll
+        for (int t = 0; t < 4; t++)
+          f4put(o, t, kw_one_term_pressure(a.which, f4get(c24, t), f4get(fi, t), k.fft_divider, f4get(tm, t), f4get(co4, t)));
+        if (row_ok) st4(a.out[0] + i, o);
+        if constexpr (CHAIN) fw[0][q] = o;
+      }
     }
   }
 
@@ -1595,7 +1656,7 @@ __global__ __launch_bounds__((Geo<L, PLANE ? L / 2 : nl_x(L)>::THREADS), (EPI ==
 #pragma unroll
     for (int jf = 0; jf < NF; jf++)
     {
-      if (EPI == EPI_DENSITY && jf == 1 && (terms == 3 || terms == 4)) break; // lossless / Stokes: only p is chained
+      if (EPI == EPI_DENSITY && jf == 1 && terms >= 3) break; // lossless / Stokes: only p is chained; one-term power law: one term
       if (!(FW0_IN_LDS && jf == 0))
       {
 #pragma unroll
@@ -1796,6 +1857,21 @@ kw_status launch_xinv_density_stokes(int chain, kw_ctx* ctx, int ncomp, const Xi
 {
   return chain ? launch_xinv_impl<EPI_DENSITY, true, 4, TAIL, LINES, PLANE>(ctx, ncomp, a, tile0, ntiles)
                : launch_xinv_impl<EPI_DENSITY, false, 4, TAIL, LINES, PLANE>(ctx, ncomp, a, tile0, ntiles);
+}
+
+// the one-term power law's epilogues: density (terms == 5) and pressure sum over one inverse
+template<bool TAIL, int LINES, bool PLANE = false>
+kw_status launch_xinv_density_oneterm(int chain, kw_ctx* ctx, int ncomp, const XinvArgs& a, uint32_t tile0, uint32_t ntiles)
+{
+  return chain ? launch_xinv_impl<EPI_DENSITY, true, 5, TAIL, LINES, PLANE>(ctx, ncomp, a, tile0, ntiles)
+               : launch_xinv_impl<EPI_DENSITY, false, 5, TAIL, LINES, PLANE>(ctx, ncomp, a, tile0, ntiles);
+}
+
+template<bool TAIL, bool PLANE = false>
+kw_status launch_xinv_psum_one(int chain, kw_ctx* ctx, int ncomp, const XinvArgs& a, uint32_t tile0, uint32_t ntiles)
+{
+  return chain ? launch_xinv_impl<EPI_PSUM1, true, 0, TAIL, X_ALL, PLANE>(ctx, ncomp, a, tile0, ntiles)
+               : launch_xinv_impl<EPI_PSUM1, false, 0, TAIL, X_ALL, PLANE>(ctx, ncomp, a, tile0, ntiles);
 }
 
 template<bool TAIL, bool PLANE = false>

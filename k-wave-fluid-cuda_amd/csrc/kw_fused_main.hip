@@ -233,9 +233,9 @@ template<int EPI, bool CHAIN = false, int TERMS = 0>
 kw_status launch_xinv(kw_ctx* ctx, int ncomp, XinvArgs a, uint32_t z0 = 0, uint32_t nzc = 0, bool plane = false)
 {
   const kw_constants& c = ctx->c;
-  static const char* const names[5][2] = { { "k_xinv_store", "k_xinv_store" }, { "k_xinv_velocity", "k_xinv_velocity_chain" },
+  static const char* const names[6][2] = { { "k_xinv_store", "k_xinv_store" }, { "k_xinv_velocity", "k_xinv_velocity_chain" },
                                            { "k_xinv_initvel", "k_xinv_initvel" }, { "k_xinv_density", "k_xinv_density_chain" },
-                                           { "k_xinv_psum", "k_xinv_psum_chain" } };
+                                           { "k_xinv_psum", "k_xinv_psum_chain" }, { "k_xinv_psum_one", "k_xinv_psum_one_chain" } };
   KW_PROF(ctx, names[EPI][CHAIN ? 1 : 0]);
   a.tw = ctx->fused.tw[0];
   a.c  = c;
@@ -243,7 +243,9 @@ kw_status launch_xinv(kw_ctx* ctx, int ncomp, XinvArgs a, uint32_t z0 = 0, uint3
   a.side_off = ctx->fused.side_off;
   a.nrows = c.ny * c.nz;
   if (plane) // one block per z-plane; the kernel does the plane's y transforms as well
-    return EPI != EPI_DENSITY ? xinv_other_plane(EPI, CHAIN ? 1 : 0, ctx, ncomp, a, z0, nzc ? nzc : c.nz)
+    return EPI == EPI_PSUM1   ? xinv_psum_one_plane(CHAIN ? 1 : 0, ctx, ncomp, a, z0, nzc ? nzc : c.nz)
+           : EPI != EPI_DENSITY ? xinv_other_plane(EPI, CHAIN ? 1 : 0, ctx, ncomp, a, z0, nzc ? nzc : c.nz)
+           : TERMS == 5       ? xinv_density_oneterm_plane(CHAIN ? 1 : 0, ctx, ncomp, a, z0, nzc ? nzc : c.nz)
            : TERMS == 4       ? xinv_density_stokes_plane(CHAIN ? 1 : 0, ctx, ncomp, a, z0, nzc ? nzc : c.nz)
                               : xinv_density_plane(CHAIN ? 1 : 0, TERMS, ctx, ncomp, a, z0, nzc ? nzc : c.nz);
   const uint32_t rows_per_tile = 2u * static_cast<uint32_t>(nl_x(c.nx));
@@ -252,14 +254,18 @@ kw_status launch_xinv(kw_ctx* ctx, int ncomp, XinvArgs a, uint32_t z0 = 0, uint3
   const bool long_lines = c.nx >= KW_LONG_LINES;
   if (full > 0)
   {
-    if (EPI != EPI_DENSITY) KW_TRY(xinv_other(EPI, CHAIN ? 1 : 0, ctx, ncomp, a, tile0, full));
+    if (EPI == EPI_PSUM1) KW_TRY(xinv_psum_one(CHAIN ? 1 : 0, ctx, ncomp, a, tile0, full));
+    else if (EPI != EPI_DENSITY) KW_TRY(xinv_other(EPI, CHAIN ? 1 : 0, ctx, ncomp, a, tile0, full));
+    else if (TERMS == 5) KW_TRY((long_lines ? xinv_density_oneterm_long : xinv_density_oneterm_short)(CHAIN ? 1 : 0, ctx, ncomp, a, tile0, full));
     else if (TERMS == 4) KW_TRY((long_lines ? xinv_density_stokes_long : xinv_density_stokes_short)(CHAIN ? 1 : 0, ctx, ncomp, a, tile0, full));
     else if (CHAIN) KW_TRY((long_lines ? xinv_density_chain_long : xinv_density_chain_short)(TERMS, ctx, ncomp, a, tile0, full));
     else KW_TRY((long_lines ? xinv_density_plain_long : xinv_density_plain_short)(TERMS, ctx, ncomp, a, tile0, full));
   }
   if (rows % rows_per_tile != 0)
   {
-    if (EPI != EPI_DENSITY) KW_TRY(xinv_other_tail(EPI, CHAIN ? 1 : 0, ctx, ncomp, a, tile0 + full, 1));
+    if (EPI == EPI_PSUM1) KW_TRY(xinv_psum_one_tail(CHAIN ? 1 : 0, ctx, ncomp, a, tile0 + full, 1));
+    else if (EPI != EPI_DENSITY) KW_TRY(xinv_other_tail(EPI, CHAIN ? 1 : 0, ctx, ncomp, a, tile0 + full, 1));
+    else if (TERMS == 5) KW_TRY(xinv_density_oneterm_tail(CHAIN ? 1 : 0, ctx, ncomp, a, tile0 + full, 1));
     else if (TERMS == 4) KW_TRY(xinv_density_stokes_tail(CHAIN ? 1 : 0, ctx, ncomp, a, tile0 + full, 1));
     else KW_TRY((CHAIN ? xinv_density_chain_tail : xinv_density_plain_tail)(TERMS, ctx, ncomp, a, tile0 + full, 1));
   }
@@ -1030,9 +1036,14 @@ kw_status kw_fused_density(kw_ctx* ctx, int nonlinear, const float* ux, const fl
   KW_REQUIRE(!chain_terms || terms != 0);
   KW_REQUIRE(ux && uy && uz && rx && ry && rz && pmlx && pmly && pmlz && kappa_padded && ddx && ddy && ddz);
   KW_REQUIRE((duxdx == nullptr) == (duydy == nullptr) && (duxdx == nullptr) == (duzdz == nullptr));
-  KW_REQUIRE(terms >= 0 && terms <= 4);
+  KW_REQUIRE(terms >= 0 && terms <= 6);
   KW_REQUIRE(terms == 0 || terms >= 3 || (t0 && t1 && (terms == 1 || t2)));
-  KW_REQUIRE(terms < 3 || t0 != nullptr);
+  KW_REQUIRE(!(terms == 3 || terms == 4) || t0 != nullptr);
+  if (terms >= 5)
+  { // one-term power law: `first` (t0 linear, t1 nonlinear) and, unless chained, the array the one term is stored in
+    KW_REQUIRE(nonlinear ? t1 != nullptr : t0 != nullptr);
+    KW_REQUIRE(chain_terms || (terms == 5 ? (nonlinear ? t2 : t1) != nullptr : t0 != nullptr));
+  }
   float2** S = ctx->fused.s;
   const float* in3[3] = { ux, uy, uz };
   ZArgs z{};
@@ -1061,11 +1072,12 @@ kw_status kw_fused_density(kw_ctx* ctx, int nonlinear, const float* ux, const fl
   for (int i = 0; i < 3; i++) { x.in[i] = S[i]; x.out[i] = rho[i]; x.m1[i] = pml[i]; x.aux[i] = du[i]; x.t[i] = t[i]; }
   x.m0[0]     = rho0;
   x.m0[1]     = bona;
-  x.m0[2]     = (terms >= 3) ? t1 : nullptr; // lossless / Stokes pressure: t0 = p (out), t1 = c2 array or NULL (in),
+  x.m0[2]     = (terms == 3 || terms == 4) ? t1 : nullptr; // lossless / Stokes pressure: t0 = p (out), t1 = c2 array or NULL (in),
                                              // Stokes: t2 = absorb_tau array or NULL (in; travels as x.t[2], never written)
   x.nonlinear = nonlinear;
   x.terms     = terms;
-  x.fout[0]   = S[0]; // chained: x-spectrum of rho0 * sum(du)
+  x.which     = (terms == 6) ? 1 : 0; // one-term power law: 5 no_dispersion, 6 no_absorption — one kernel set (TERMS == 5)
+  x.fout[0]   = S[0]; // chained: x-spectrum of rho0 * sum(du) (terms == 6: of sum(rho), the one chained array)
   x.fout[1]   = S[1]; //          x-spectrum of sum(rho)
   // one specialised kernel per pressure-term mode
 #define DENSITY_TAIL(T)                                                                                                \
@@ -1089,7 +1101,8 @@ kw_status kw_fused_density(kw_ctx* ctx, int nonlinear, const float* ux, const fl
     case 1: DENSITY_TAIL(1); break;
     case 2: DENSITY_TAIL(2); break;
     case 3: DENSITY_TAIL(3); break;
-    default: DENSITY_TAIL(4); break;
+    case 4: DENSITY_TAIL(4); break;
+    default: DENSITY_TAIL(5); break;
   }
 #undef DENSITY_TAIL
   return KW_OK;
@@ -1173,6 +1186,56 @@ kw_status kw_fused_absorption_pressure(kw_ctx* ctx, float* p, const float* vel_g
   }
   else if (chain_p) KW_TRY((launch_xinv<EPI_PSUM, true>(ctx, 1, x)));
   else KW_TRY(launch_xinv<EPI_PSUM>(ctx, 1, x));
+  return KW_OK;
+}
+
+// The absorbing branch with one term (absorbing_flag 3 / 4): p = c2*(first + d*(tau*ifftn(nabla1*fftn(term)))) for which == 0
+// (no_dispersion: term = rho0 * sum du), p = c2*(first - d*(eta*ifftn(nabla2*fftn(term)))) for which == 1 (no_absorption:
+// term = sum rho) — one array through every pass of the stage, one exchange each way on slabs
+kw_status kw_fused_absorption_pressure_one(kw_ctx* ctx, float* p, const float* term, const float* first,
+                                           const float* nabla_padded, const float* c2, const float* coef, int which, int flags)
+{
+  const bool terms_in_scratch = (flags & KW_FUSED_TERMS_IN_SCRATCH) != 0;
+  const bool chain_p          = (flags & KW_FUSED_CHAIN_P) != 0;
+  KW_FUSED_READY(ctx);
+  KW_PROF(ctx, "fused_absorption_pressure_one");
+  KW_REQUIRE(p && first && nabla_padded);
+  KW_REQUIRE(terms_in_scratch || term != nullptr);
+  KW_REQUIRE(which == 0 || which == 1);
+  KW_REQUIRE((flags & ~(KW_FUSED_TERMS_IN_SCRATCH | KW_FUSED_CHAIN_P)) == 0);
+  float2** S = ctx->fused.s;
+  const float* in1[1] = { term };
+  ZArgs z{};
+  z.in[0] = S[0]; z.out[0] = S[0];
+  z.op[0] = nabla_padded;
+  if (ctx->fused.slab)
+  {
+    KW_TRY(slab_chain<Z_ABSORB>(ctx, 1, terms_in_scratch ? nullptr : in1, z));
+  }
+  else
+  {
+    KW_TRY(forward_xy(ctx, 1, terms_in_scratch ? nullptr : in1));
+    KW_TRY(launch_zfused<Z_ABSORB>(ctx, 1, z));
+  }
+  XinvArgs x{};
+  x.in[0] = S[0];
+  x.out[0] = p;
+  x.m0[0] = first; x.m0[1] = c2;
+  x.m1[0] = coef;
+  x.which = which;
+  x.fout[0] = S[0]; // chained: x-spectrum of the new p
+  if (!ctx->fused.slab && !ctx->fused.two_d)
+  {
+    if (chain_p) KW_TRY((plane_local_tail<EPI_PSUM1, true>(ctx, 1, 1, x, 1)));
+    else KW_TRY((plane_local_tail<EPI_PSUM1, false>(ctx, 1, 1, x, 0)));
+  }
+  else if (ctx->fused.slab && ctx->fused.pipelined)
+  {
+    if (chain_p) KW_TRY((pslab_tail<EPI_PSUM1, true>(ctx, 1, 1, x, 1)));
+    else KW_TRY((pslab_tail<EPI_PSUM1, false>(ctx, 1, 1, x, 0)));
+  }
+  else if (chain_p) KW_TRY((launch_xinv<EPI_PSUM1, true>(ctx, 1, x)));
+  else KW_TRY(launch_xinv<EPI_PSUM1>(ctx, 1, x));
   return KW_OK;
 }
 

@@ -188,6 +188,17 @@ __device__ __forceinline__ float kw_stokes_pressure(bool nonlinear, float c2, fl
   if (nonlinear) first = (((bOnA * rhoSum) * rhoSum) / (2.0f * rho0)) + rhoSum;
   return c2 * (first + absorb);
 }
+
+// One-term power-law absorption (absorbing_flag == 3: no_dispersion, eta = 0; == 4: no_absorption, tau = 0): the power law's
+// sum p = c2*(first + fftDivider*((tauTerm*tau) - (etaTerm*eta))) with the absent product removed.  The x-inverse epilogue of
+// kw_fused_absorption_pressure_one and kw_sum_pressure_terms_one_* both evaluate it here, without contraction into fma:
+//   which == 0: p = c2 * (first + (fftDivider * (term * tau)))      which == 1: p = c2 * (first - (fftDivider * (term * eta)))
+__device__ __forceinline__ float kw_one_term_pressure(int which, float c2, float first, float fftDivider, float term, float coef)
+{
+#pragma clang fp contract(off)
+  const float scaled = fftDivider * (term * coef);
+  return which ? c2 * (first - scaled) : c2 * (first + scaled);
+}
 #endif
 
 // checked right after each launch, without synchronising (reference: cudaCheckErrors(cudaGetLastError()))

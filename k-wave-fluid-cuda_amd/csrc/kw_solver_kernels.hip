@@ -287,6 +287,32 @@ __global__ __launch_bounds__(256) void k_sum_pressure_terms(kw_constants c, floa
   Vec<V>::store(p + i, o);
 }
 
+// the one-term power law (absorbing_flag 3 / 4): kw_one_term_pressure (kw_internal.h), as the fused epilogue evaluates it
+template<int V, bool kC2Scalar, bool kCoefScalar>
+__global__ __launch_bounds__(256) void k_sum_pressure_terms_one(kw_constants c, float* __restrict__ p,
+                                                                 const float* __restrict__ first,
+                                                                 const float* __restrict__ term,
+                                                                 const float* __restrict__ c2,
+                                                                 const float* __restrict__ coef, int which)
+{
+  size_t i;
+  if (!flat_index<V>(c.n_elements, i)) return;
+  using VT = typename Vec<V>::T;
+  const VT vf = Vec<V>::load(first + i), vt = Vec<V>::load(term + i);
+  VT vc{}, vk{};
+  if (!kC2Scalar) vc = Vec<V>::load(c2 + i);
+  if (!kCoefScalar) vk = Vec<V>::load(coef + i);
+  VT o;
+#pragma unroll
+  for (int k = 0; k < V; k++)
+  {
+    const float ec2 = kC2Scalar ? c.c2 : get(vc, k);
+    const float eco = kCoefScalar ? (which ? c.absorb_eta : c.absorb_tau) : get(vk, k);
+    put(o, k, kw_one_term_pressure(which, ec2, get(vf, k), c.fft_divider, get(vt, k), eco));
+  }
+  Vec<V>::store(p + i, o);
+}
+
 // SolverCudaKernels.cu:2067-2084
 template<int V, bool kC2Scalar, bool kBonAScalar, bool kRho0Scalar>
 __global__ __launch_bounds__(256) void k_sum_pressure_nonlinear_lossless(
@@ -631,6 +657,21 @@ __global__ __launch_bounds__(256) void k_absorbtion_term(kw_constants c, float* 
   }
   CVec<P>::store(A + 2 * i, va);
   CVec<P>::store(B + 2 * i, vb);
+}
+
+// the same for one spectrum (one-term power law)
+template<int P>
+__global__ __launch_bounds__(256) void k_absorbtion_term_one(kw_constants c, float* __restrict__ A, const float* __restrict__ n)
+{
+  size_t i;
+  if (!flat_cindex<P>(c.n_elements_complex, i)) return;
+  float2 va[P];
+  float  v[P];
+  CVec<P>::load(A + 2 * i, va);
+  CVec<P>::loadr(n + i, v);
+#pragma unroll
+  for (int k = 0; k < P; k++) va[k] = cscale(va[k], v[k]);
+  CVec<P>::store(A + 2 * i, va);
 }
 
 // SolverCudaKernels.cu:740-745
@@ -1062,6 +1103,54 @@ kw_status kw_compute_absorbtion_term(kw_ctx* ctx, float* A, float* B, const floa
   if (p2) LAUNCH((k_absorbtion_term<2>), grid1d(c.n_elements_complex / 2), dim3(256), c, A, B, n1, n2);
   else    LAUNCH((k_absorbtion_term<1>), grid1d(c.n_elements_complex), dim3(256), c, A, B, n1, n2);
   return KW_OK;
+}
+
+kw_status kw_compute_absorbtion_term_one(kw_ctx* ctx, float* A, const float* n)
+{
+  KW_CHECK_CONSTS(ctx);
+  KW_PROF(ctx, "compute_absorbtion_term_one");
+  KW_REQUIRE(A && n);
+  const kw_constants& c = ctx->c;
+  const bool p2 = (c.n_elements_complex % 2 == 0) && all_aligned16(A) && ((reinterpret_cast<uintptr_t>(n) & 7u) == 0);
+  if (p2) LAUNCH((k_absorbtion_term_one<2>), grid1d(c.n_elements_complex / 2), dim3(256), c, A, n);
+  else    LAUNCH((k_absorbtion_term_one<1>), grid1d(c.n_elements_complex), dim3(256), c, A, n);
+  return KW_OK;
+}
+
+static kw_status sum_terms_one_impl(kw_ctx* ctx, float* p, const float* first, const float* term, const float* c2,
+                                    const float* coef, int which)
+{
+  KW_CHECK_CONSTS(ctx);
+  KW_PROF(ctx, "sum_pressure_terms_one");
+  KW_REQUIRE(p && first && term);
+  KW_REQUIRE(which == 0 || which == 1);
+  const kw_constants& c = ctx->c;
+  const bool v4 = c.n_elements % 4 == 0 && all_aligned16(p, first, term, c2, coef);
+  const dim3 g  = v4 ? grid1d(c.n_elements / 4) : grid1d(c.n_elements);
+#define ST1(V, C, T) LAUNCH((k_sum_pressure_terms_one<V, C, T>), g, dim3(256), c, p, first, term, c2, coef, which)
+  if (v4)
+  {
+    if (c2) { if (coef) ST1(4, false, false); else ST1(4, false, true); }
+    else    { if (coef) ST1(4, true, false);  else ST1(4, true, true); }
+  }
+  else
+  {
+    if (c2) { if (coef) ST1(1, false, false); else ST1(1, false, true); }
+    else    { if (coef) ST1(1, true, false);  else ST1(1, true, true); }
+  }
+#undef ST1
+  return KW_OK;
+}
+
+kw_status kw_sum_pressure_terms_one_nonlinear(kw_ctx* ctx, float* p, const float* nonlinearTerm, const float* term,
+                                              const float* c2, const float* coef, int which)
+{
+  return sum_terms_one_impl(ctx, p, nonlinearTerm, term, c2, coef, which);
+}
+kw_status kw_sum_pressure_terms_one_linear(kw_ctx* ctx, float* p, const float* term, const float* densitySum,
+                                           const float* c2, const float* coef, int which)
+{
+  return sum_terms_one_impl(ctx, p, densitySum, term, c2, coef, which);
 }
 
 static kw_status sum_terms_impl(kw_ctx* ctx, float* p, const float* first, const float* tauTerm, const float* etaTerm,

@@ -588,7 +588,9 @@ void KSpaceFirstOrderSolver::fusedDensity(bool nonlinear)
   const bool chainP        = mPressureFused &&
                              !((mParameters.getTimeIndex() == 0) && (mParameters.getInitialPressureSourceFlag() == 1));
   const bool storeDu       = absorbing && pSourceActive; // the stand-alone terms kernel will need the gradients
-  const int  terms         = mTermsFused ? (nonlinear ? 2 : 1) : (mPressureFused ? (stokes ? 4 : 3) : 0);
+  // one-term power law: the density kernel leaves `first` and the one term that takes the absorption round trip (5 / 6)
+  const int  powerLawTerms = mParameters.isNoDispersionAbsorption() ? 5 : mParameters.isNoAbsorptionDispersion() ? 6 : (nonlinear ? 2 : 1);
+  const int  terms         = mTermsFused ? powerLawTerms : (mPressureFused ? (stokes ? 4 : 3) : 0);
   const int  flags         = (mVelocityChained ? KW_FUSED_U_IN_SCRATCH : 0) |
                              ((mTermsFused || chainP) ? KW_FUSED_CHAIN_TERMS : 0);
   // aliasing of the temporaries as in :2184-2190 (nonlinear) / :2221-2225 (linear)
@@ -636,11 +638,44 @@ template<SD sd> void KSpaceFirstOrderSolver::computeDensityLinear()
   }
 }
 
+// fused: the one-term absorption stage; the kernel that writes p also leaves its spectrum for the next step's velocity
+// stage, unless p is about to be overwritten by the initial pressure source (step 0)
+void KSpaceFirstOrderSolver::fusedAbsorptionPressureOne(RealMatrix& term, RealMatrix& first, int which)
+{
+  const bool chainP = !((mParameters.getTimeIndex() == 0) && (mParameters.getInitialPressureSourceFlag() == 1));
+  kwCheck(kw_fused_absorption_pressure_one(mParameters.getHipParameters().getContext(), getP().getDeviceData(),
+                                           term.getDeviceData(), first.getDeviceData(), which ? mNabla2Padded : mNabla1Padded,
+                                           mMatrixContainer.realDeviceOrNull(MI::kC2),
+                                           mMatrixContainer.realDeviceOrNull(which ? MI::kAbsorbEta : MI::kAbsorbTau), which,
+                                           (mTermsFused ? KW_FUSED_TERMS_IN_SCRATCH : 0) | (chainP ? KW_FUSED_CHAIN_P : 0)));
+  mPressureInScratch = chainP;
+}
+
 template<SD sd> void KSpaceFirstOrderSolver::computePressureNonlinear()
 { // :2180-2210
   if (mParameters.isStokesAbsorption())
   {
     if (!(mFused && mPressureFused)) SolverHipKernels::sumPressureStokesNonlinear(mMatrixContainer);
+  }
+  else if (mParameters.isOneTermAbsorption())
+  { // the power law's branch below with one term: no_dispersion keeps tau * F^-1{nabla1 F{rho0 sum du}}, no_absorption
+    // eta * F^-1{nabla2 F{sum rho}} — one transform pair, one operator, one coefficient
+    const int   which               = mParameters.isNoAbsorptionDispersion() ? 1 : 0;
+    RealMatrix& densitySum          = getTemp1RealND();
+    RealMatrix& nonlinearTerm       = getTemp2RealND();
+    RealMatrix& velocityGradientSum = getTemp3RealND();
+    RealMatrix& absorbTerm          = which ? densitySum : velocityGradientSum; // transformed in place
+    if (!(mFused && mTermsFused))
+      SolverHipKernels::computePressureTermsNonlinear<sd>(densitySum, nonlinearTerm, velocityGradientSum, mMatrixContainer);
+    if (mFused)
+    {
+      fusedAbsorptionPressureOne(absorbTerm, nonlinearTerm, which);
+      return;
+    }
+    getTempHipFftX().computeR2CFftND(absorbTerm);
+    SolverHipKernels::computeAbsorbtionTermOne(getTempHipFftX(), real(which ? MI::kAbsorbNabla2 : MI::kAbsorbNabla1));
+    getTempHipFftX().computeC2RFftND(absorbTerm);
+    SolverHipKernels::sumPressureTermsOneNonlinear(nonlinearTerm, absorbTerm, which, mMatrixContainer);
   }
   else if (mParameters.getAbsorbingFlag())
   {
@@ -684,6 +719,26 @@ template<SD sd> void KSpaceFirstOrderSolver::computePressureLinear()
   if (mParameters.isStokesAbsorption())
   {
     if (!(mFused && mPressureFused)) SolverHipKernels::sumPressureStokesLinear(mMatrixContainer);
+  }
+  else if (mParameters.isOneTermAbsorption())
+  { // (see computePressureNonlinear) — here `first` is the density sum itself
+    const int   which                = mParameters.isNoAbsorptionDispersion() ? 1 : 0;
+    RealMatrix& densitySum           = getTemp1RealND();
+    RealMatrix& velocityGradientTerm = getTemp2RealND();
+    if (!(mFused && mTermsFused))
+      SolverHipKernels::computePressureTermsLinear<sd>(densitySum, velocityGradientTerm, mMatrixContainer);
+    RealMatrix& term = which ? densitySum : velocityGradientTerm;
+    if (mFused)
+    {
+      fusedAbsorptionPressureOne(term, densitySum, which);
+      return;
+    }
+    // no_absorption: the density sum is also `first`, so its transformed copy goes to the third temporary
+    RealMatrix& absorbTerm = which ? getTemp3RealND() : velocityGradientTerm;
+    getTempHipFftX().computeR2CFftND(term);
+    SolverHipKernels::computeAbsorbtionTermOne(getTempHipFftX(), real(which ? MI::kAbsorbNabla2 : MI::kAbsorbNabla1));
+    getTempHipFftX().computeC2RFftND(absorbTerm);
+    SolverHipKernels::sumPressureTermsOneLinear(absorbTerm, densitySum, which, mMatrixContainer);
   }
   else if (mParameters.getAbsorbingFlag())
   {
@@ -857,11 +912,8 @@ void KSpaceFirstOrderSolver::initializeFusedPipeline()
   mUseStepGraph = mParameters.getOptions().stepGraph;
   if (mParameters.isSlabDecomposed()) mUseStepGraph = false; // the exchange callbacks cannot be recorded
   mKappaPadded = importPadded(MI::kKappa);
-  if (mMatrixContainer.has(MI::kAbsorbNabla1))
-  {
-    mNabla1Padded = importPadded(MI::kAbsorbNabla1);
-    mNabla2Padded = importPadded(MI::kAbsorbNabla2);
-  }
+  if (mMatrixContainer.has(MI::kAbsorbNabla1)) mNabla1Padded = importPadded(MI::kAbsorbNabla1);
+  if (mMatrixContainer.has(MI::kAbsorbNabla2)) mNabla2Padded = importPadded(MI::kAbsorbNabla2);
   if (mMatrixContainer.has(MI::kSourceKappa)) mSourceKappaPadded = importPadded(MI::kSourceKappa);
   if (mParameters.needsShiftedVelocity())
   { // filters of the one-kernel-per-axis shift: the half-length shift vectors of the input file extended to full length
@@ -989,20 +1041,24 @@ void KSpaceFirstOrderSolver::generateKappaAndNablas()
   const float twoPi    = static_cast<float>(M_PI) * 2.0f;
   const float power    = mParameters.getAlphaPower();
   float* kappa  = real(MI::kKappa).getHostData();
-  float* nabla1 = real(MI::kAbsorbNabla1).getHostData();
-  float* nabla2 = real(MI::kAbsorbNabla2).getHostData();
+  // (the one-term modes hold the operator of their term alone)
+  float* nabla1 = mParameters.usesAbsorbTauTerm() ? real(MI::kAbsorbNabla1).getHostData() : nullptr;
+  float* nabla2 = mParameters.usesAbsorbEtaTerm() ? real(MI::kAbsorbNabla2).getHostData() : nullptr;
   SpectralBins(mParameters).sweep([=](size_t i, float r) {
     const float k = twoPi * r;
     kappa[i]      = sincOrOne(halfStep * k);
-    nabla1[i]     = finiteOrZero(std::pow(k, power - 2.0f));
-    nabla2[i]     = finiteOrZero(std::pow(k, power - 1.0f));
+    if (nabla1 != nullptr) nabla1[i] = finiteOrZero(std::pow(k, power - 2.0f));
+    if (nabla2 != nullptr) nabla2[i] = finiteOrZero(std::pow(k, power - 1.0f));
   });
 }
 
 void KSpaceFirstOrderSolver::generateTauAndEta()
 { // tau = -2 a c0^(y-1),  eta = 2 a c0^y tan(pi y / 2),  a = alpha_coeff * 100 (1e-6 / 2 pi)^y / (20 log10 e)  [Np]
   // Stokes absorption (y == 2): tau alone — the same expression; eta is neither stored nor used
+  // no_dispersion: tau alone, no_absorption: eta alone — the unused scalar is 0, the unused array does not exist
   const bool  stokes  = mParameters.isStokesAbsorption();
+  const bool  noTau   = mParameters.isNoAbsorptionDispersion();
+  const bool  noEta   = stokes || mParameters.isNoDispersionAbsorption();
   const float power   = mParameters.getAlphaPower();
   const float tanTerm = std::tan(static_cast<float>(M_PI_2) * power);
   const float neper   = (100.0f * std::pow(1.0e-6f / (2.0f * static_cast<float>(M_PI)), power)) / (20.0f * static_cast<float>(M_LOG10E));
@@ -1010,8 +1066,8 @@ void KSpaceFirstOrderSolver::generateTauAndEta()
   if (alphaIsScalar && c0IsScalar)
   {
     const float a2 = 2.0f * mParameters.getAlphaCoeffScalar() * neper;
-    mParameters.setAbsorbTauScalar((-a2) * std::pow(mParameters.getC0Scalar(), power - 1));
-    mParameters.setAbsorbEtaScalar(stokes ? 0.0f : a2 * std::pow(mParameters.getC0Scalar(), power) * tanTerm);
+    mParameters.setAbsorbTauScalar(noTau ? 0.0f : (-a2) * std::pow(mParameters.getC0Scalar(), power - 1));
+    mParameters.setAbsorbEtaScalar(noEta ? 0.0f : a2 * std::pow(mParameters.getC0Scalar(), power) * tanTerm);
     return;
   }
   // per voxel as soon as either operand is an array; alpha_coeff was loaded into Temp1, the c2 matrix still holds c0
@@ -1019,15 +1075,15 @@ void KSpaceFirstOrderSolver::generateTauAndEta()
   const float* c0    = c0IsScalar ? nullptr : real(MI::kC2).getHostData();
   const float  alphaScalar = alphaIsScalar ? mParameters.getAlphaCoeffScalar() : 0.0f;
   const float  c0Scalar    = c0IsScalar ? mParameters.getC0Scalar() : 0.0f;
-  float* tau = real(MI::kAbsorbTau).getHostData();
-  float* eta = stokes ? nullptr : real(MI::kAbsorbEta).getHostData();
+  float* tau = noTau ? nullptr : real(MI::kAbsorbTau).getHostData();
+  float* eta = noEta ? nullptr : real(MI::kAbsorbEta).getHostData();
   const size_t n = mParameters.getFullDimensionSizes().nElements();
 #pragma omp parallel for schedule(static)
   for (size_t i = 0; i < n; i++)
   {
     const float a2 = 2.0f * neper * (alpha ? alpha[i] : alphaScalar);
     const float c  = c0 ? c0[i] : c0Scalar;
-    tau[i] = (-a2) * std::pow(c, power - 1.0f);
+    if (tau != nullptr) tau[i] = (-a2) * std::pow(c, power - 1.0f);
     if (eta != nullptr) eta[i] = a2 * std::pow(c, power) * tanTerm;
   }
 }

@@ -55,6 +55,7 @@ class KSpaceFirstOrderSolver
   template<SD simulationDimension> void computeDensityNonliner();
   template<SD simulationDimension> void computeDensityLinear();
   void fusedDensity(bool nonlinear);
+  void fusedAbsorptionPressureOne(RealMatrix& term, RealMatrix& first, int which);
   template<SD simulationDimension> void computePressureNonlinear();
   template<SD simulationDimension> void computePressureLinear();
   void addVelocitySource();

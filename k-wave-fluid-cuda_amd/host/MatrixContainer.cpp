@@ -58,9 +58,12 @@ bool nonUniformScalarRho0(const P& p) { return nonUniform(p) && p.getRho0ScalarF
 bool bOnAArray(const P& p) { return p.getNonLinearFlag() && !p.getBOnAScalarFlag(); }
 bool absorbing(const P& p) { return p.getAbsorbingFlag() != 0; }
 bool absorbingArrays(const P& p) { return absorbing(p) && !(p.getC0ScalarFlag() && p.getAlphaCoeffScalarFlag()); }
-// Stokes absorption needs tau alone: no eta, no nabla spectra
-bool powerLaw(const P& p) { return p.getAbsorptionType() == P::AbsorptionType::kPowerLaw; }
-bool powerLawArrays(const P& p) { return powerLaw(p) && absorbingArrays(p); }
+// Stokes absorption needs tau alone: no eta, no nabla spectra; the one-term modes (no_dispersion / no_absorption) the
+// operator and the coefficient of their term alone
+bool tauArray(const P& p) { return absorbingArrays(p) && !p.isNoAbsorptionDispersion(); }
+bool etaArray(const P& p) { return absorbingArrays(p) && p.usesAbsorbEtaTerm(); }
+bool nabla1(const P& p) { return p.usesAbsorbTauTerm(); }
+bool nabla2(const P& p) { return p.usesAbsorbEtaTerm(); }
 bool alphaCoeffArray(const P& p) { return absorbing(p) && !p.getAlphaCoeffScalarFlag(); }
 bool noAlphaCoeffArray(const P& p) { return !alphaCoeffArray(p); }
 bool indexMask(const P& p) { return p.getSensorMaskType() == P::SensorMaskType::kIndex && p.getSensorMaskIndexSize() > 0; }
@@ -141,10 +144,10 @@ const Row kSchema[] = {
   GRID(kDtRho0Sgy, 0, "dt_rho0_sgy_nonuniform", nonUniformScalarRho0),
   GRID(kDtRho0Sgz, 0, "dt_rho0_sgz_nonuniform", nonUniformScalarRho0),
   GRID(kBOnA, kFromFile, kBonAName, bOnAArray),
-  GRID(kAbsorbTau, 0, "absorb_tau", absorbingArrays),
-  GRID(kAbsorbEta, 0, "absorb_eta", powerLawArrays),
-  { MI::kAbsorbNabla1, MT::kReal, Extent::kSpectrum, nullptr, 0, "absorb_nabla1_r", powerLaw },
-  { MI::kAbsorbNabla2, MT::kReal, Extent::kSpectrum, nullptr, 0, "absorb_nabla2_r", powerLaw },
+  GRID(kAbsorbTau, 0, "absorb_tau", tauArray),
+  GRID(kAbsorbEta, 0, "absorb_eta", etaArray),
+  { MI::kAbsorbNabla1, MT::kReal, Extent::kSpectrum, nullptr, 0, "absorb_nabla1_r", nabla1 },
+  { MI::kAbsorbNabla2, MT::kReal, Extent::kSpectrum, nullptr, 0, "absorb_nabla2_r", nabla2 },
   { MI::kSourceKappa, MT::kReal, Extent::kSpectrum, nullptr, 0, "source_kappa_r", kSpaceCorrectedSource },
   { MI::kDdxKShiftPosR, MT::kComplex, Extent::kSpectrumX, nullptr, kFromFile, kDdxKShiftPosRName, always },
   { MI::kDdyKShiftPos, MT::kComplex, Extent::kSpectrumY, nullptr, kFromFile, kDdyKShiftPosName, always },

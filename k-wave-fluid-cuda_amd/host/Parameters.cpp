@@ -116,6 +116,9 @@ void Parameters::init(const InputProvider& in, const Options& options)
     throw std::invalid_argument("2-D simulations have no transducer or z-velocity source");
   in.readScalarValue(kNonUniformGridFlagName, mNonUniformGridFlag);
   in.readScalarValue(kAbsorbingFlagName, mAbsorbingFlag);
+  if (mAbsorbingFlag > 4)
+    throw std::invalid_argument(std::string("Error: Illegal value of ") + kAbsorbingFlagName + " (" + std::to_string(mAbsorbingFlag) +
+                                "): 0 lossless, 1 power law, 2 Stokes, 3 no_dispersion, 4 no_absorption");
   in.readScalarValue(kNonLinearFlagName, mNonLinearFlag);
   if (mNonUniformGridFlag != 0 && !isSimulation3D())
     throw std::invalid_argument("Non-uniform grids are implemented for 3-D simulations only");

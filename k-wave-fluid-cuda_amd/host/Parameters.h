@@ -161,13 +161,26 @@ class Parameters
   size_t getNonUniformGridFlag() const { return mNonUniformGridFlag; }
   size_t getAbsorbingFlag() const { return mAbsorbingFlag; }
   // absorbing_flag of the input file: 0 lossless, 2 Stokes absorption (k-Wave's alpha_mode = 'stokes': alpha_power == 2, the
-  // equation of state is element-wise and the step has no absorption FFT stage), anything else the power law
-  enum class AbsorptionType { kNone, kPowerLaw, kStokes };
+  // equation of state is element-wise and the step has no absorption FFT stage), 3 the power law without its dispersion
+  // term (alpha_mode = 'no_dispersion': eta = 0; tau and nabla1 alone exist), 4 without its absorption term ('no_absorption':
+  // tau = 0; eta and nabla2 alone exist), 1 the power law; init() refuses anything above 4
+  enum class AbsorptionType { kNone, kPowerLaw, kStokes, kNoDispersion, kNoAbsorption };
   AbsorptionType getAbsorptionType() const
   {
-    return (mAbsorbingFlag == 0) ? AbsorptionType::kNone : (mAbsorbingFlag == 2) ? AbsorptionType::kStokes : AbsorptionType::kPowerLaw;
+    return (mAbsorbingFlag == 0)   ? AbsorptionType::kNone
+           : (mAbsorbingFlag == 2) ? AbsorptionType::kStokes
+           : (mAbsorbingFlag == 3) ? AbsorptionType::kNoDispersion
+           : (mAbsorbingFlag == 4) ? AbsorptionType::kNoAbsorption
+                                   : AbsorptionType::kPowerLaw;
   }
   bool   isStokesAbsorption() const { return getAbsorptionType() == AbsorptionType::kStokes; }
+  bool   isNoDispersionAbsorption() const { return getAbsorptionType() == AbsorptionType::kNoDispersion; }
+  bool   isNoAbsorptionDispersion() const { return getAbsorptionType() == AbsorptionType::kNoAbsorption; }
+  // the power law with one of its two terms: one operator, one coefficient, one 3-D round trip per step
+  bool   isOneTermAbsorption() const { return isNoDispersionAbsorption() || isNoAbsorptionDispersion(); }
+  // which of the power law's operand pairs this run generates and holds: (tau, nabla1) and (eta, nabla2)
+  bool   usesAbsorbTauTerm() const { return getAbsorptionType() == AbsorptionType::kPowerLaw || isNoDispersionAbsorption(); }
+  bool   usesAbsorbEtaTerm() const { return getAbsorptionType() == AbsorptionType::kPowerLaw || isNoAbsorptionDispersion(); }
   size_t getNonLinearFlag() const { return mNonLinearFlag; }
   bool   getBOnAScalarFlag() const { return mBOnAScalarFlag; }
   float  getBOnAScalar() const { return mBOnAScalar; }

@@ -153,6 +153,22 @@ void sumPressureTermsLinear(const RealMatrix& absorbTauTerm, const RealMatrix& a
                                        c.realDeviceOrNull(MI::kC2), c.realDeviceOrNull(MI::kAbsorbTau),
                                        c.realDeviceOrNull(MI::kAbsorbEta)));
 }
+void computeAbsorbtionTermOne(HipFftComplexMatrix& fftPart, const RealMatrix& absorbNabla)
+{
+  kwCheck(kw_compute_absorbtion_term_one(ctx(), fftPart.getDeviceData(), absorbNabla.getDeviceData()));
+}
+void sumPressureTermsOneNonlinear(const RealMatrix& nonlinearTerm, const RealMatrix& absorbTerm, int which, const MatrixContainer& c)
+{
+  kwCheck(kw_sum_pressure_terms_one_nonlinear(ctx(), real(c, MI::kP), nonlinearTerm.getDeviceData(), absorbTerm.getDeviceData(),
+                                              c.realDeviceOrNull(MI::kC2),
+                                              c.realDeviceOrNull(which ? MI::kAbsorbEta : MI::kAbsorbTau), which));
+}
+void sumPressureTermsOneLinear(const RealMatrix& absorbTerm, const RealMatrix& densitySum, int which, const MatrixContainer& c)
+{
+  kwCheck(kw_sum_pressure_terms_one_linear(ctx(), real(c, MI::kP), absorbTerm.getDeviceData(), densitySum.getDeviceData(),
+                                           c.realDeviceOrNull(MI::kC2),
+                                           c.realDeviceOrNull(which ? MI::kAbsorbEta : MI::kAbsorbTau), which));
+}
 void sumPressureStokesNonlinear(const MatrixContainer& c)
 {
   kwCheck(kw_sum_pressure_stokes_nonlinear(ctx(), real(c, MI::kP), real(c, MI::kRhoX), real(c, MI::kRhoY), real(c, MI::kRhoZ),

@@ -45,6 +45,12 @@ void sumPressureTermsNonlinear(const RealMatrix& nonlinearTerm, const RealMatrix
                                const RealMatrix& absorbEtaTerm, const MatrixContainer& container);
 void sumPressureTermsLinear(const RealMatrix& absorbTauTerm, const RealMatrix& absorbEtaTerm,
                             const RealMatrix& densitySum, const MatrixContainer& container);
+// one-term power law (no_dispersion: which = 0, tau; no_absorption: which = 1, eta): one spectrum, one coefficient
+void computeAbsorbtionTermOne(HipFftComplexMatrix& fftPart, const RealMatrix& absorbNabla);
+void sumPressureTermsOneNonlinear(const RealMatrix& nonlinearTerm, const RealMatrix& absorbTerm, int which,
+                                  const MatrixContainer& container);
+void sumPressureTermsOneLinear(const RealMatrix& absorbTerm, const RealMatrix& densitySum, int which,
+                               const MatrixContainer& container);
 // Stokes absorption: the element-wise equation of state on the densities and the stored velocity gradients
 void sumPressureStokesNonlinear(const MatrixContainer& container);
 void sumPressureStokesLinear(const MatrixContainer& container);

@@ -119,6 +119,9 @@ def _sg_mean(a: np.ndarray, axis: int) -> np.ndarray:
     return 0.5 * (a + nxt)
 
 
+ALPHA_MODE_FLAGS = {"no_dispersion": 3, "no_absorption": 4}  # absorbing_flag of k-Wave's medium.alpha_mode settings
+
+
 def make_problem(nx: int, ny: Optional[int] = None, nz: Optional[int] = None, *,
                  heterogeneous: bool = True, nonlinear: bool = True, absorbing: bool = True,
                  source: str = "p0", nt: int = 110, pml_size: int = 10, pml_alpha: float = 2.0,
@@ -126,7 +129,8 @@ def make_problem(nx: int, ny: Optional[int] = None, nz: Optional[int] = None, *,
                  source_mode: int = 0, source_many: int = 0, sensor: str = "plane",
                  hetero_subset: Optional[dict] = None, seed: int = 0x5EED1234,
                  nt_src: Optional[int] = None, zslab: Optional[tuple] = None,
-                 nonuniform: bool = False, stokes: bool = False) -> Dict[str, np.ndarray]:
+                 nonuniform: bool = False, stokes: bool = False,
+                 alpha_mode: Optional[str] = None) -> Dict[str, np.ndarray]:
     """Build one synthetic problem.
 
     source: "p0" (1 MPa Gaussian ball), "p_source" (1 MHz tone burst on plane x=12),
@@ -136,6 +140,9 @@ def make_problem(nx: int, ny: Optional[int] = None, nz: Optional[int] = None, *,
             /root/reference/Parameters/Parameters.cpp:426-459).
     stokes: with absorbing, Stokes absorption (k-Wave's alpha_mode = 'stokes'): alpha_power = 2 and absorbing_flag = 2 —
             the run whose reference is the power law itself at alpha_power = 2 (stokes_as_power_law).
+    alpha_mode: with absorbing, "no_dispersion" (absorbing_flag = 3: the power law without its eta term) or
+            "no_absorption" (absorbing_flag = 4: without its tau term), k-Wave's medium.alpha_mode; alpha_power stays 1.5.
+            The reference of such a run is the power law with the other coefficient zeroed (alpha_mode_as_power_law).
     zslab:  (z_lo, z_hi): build the 3-D arrays only for planes z_lo <= z < z_hi (multi-GPU runs generate their own
             slab; every other dataset — scalars, operators, PML vectors, index masks — stays global and is cut to
             the slab by dist.partition_problem(..., arrays_are_local=True)).
@@ -211,7 +218,12 @@ def make_problem(nx: int, ny: Optional[int] = None, nz: Optional[int] = None, *,
     pr["nonlinear_flag"] = scalar_u(int(nonlinear))
     if stokes and not absorbing:
         raise ValueError("stokes needs absorbing=True")
-    pr["absorbing_flag"] = scalar_u(2 if (absorbing and stokes) else int(absorbing))
+    if alpha_mode is not None and alpha_mode not in ALPHA_MODE_FLAGS:
+        raise ValueError(f"alpha_mode must be one of {sorted(ALPHA_MODE_FLAGS)}")
+    if alpha_mode is not None and (stokes or not absorbing):
+        raise ValueError("alpha_mode needs absorbing=True and excludes stokes")
+    pr["absorbing_flag"] = scalar_u(ALPHA_MODE_FLAGS[alpha_mode] if alpha_mode is not None
+                                    else 2 if (absorbing and stokes) else int(absorbing))
 
     # ---- operators + PML ----------------------------------------------------------------------
     pr.update(kspace_operators(nx, ny, nz, dx, dy, dz))
@@ -305,6 +317,17 @@ def stokes_as_power_law(pr: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
     (absorbing_flag = 2) computes — nabla1 = |k|^0 = 1 and eta ~ tan(pi) = 0 — and therefore its reference."""
     if int(np.asarray(pr["absorbing_flag"]).ravel()[0]) != 2:
         raise ValueError("not a Stokes problem")
+    out = dict(pr)
+    out["absorbing_flag"] = np.array([[[1]]], dtype=U64)
+    return out
+
+
+def alpha_mode_as_power_law(pr: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
+    """The same problem with absorbing_flag = 1, the full power law.  A one-term problem (absorbing_flag = 3 / 4) computes
+    this power law with eta (no_dispersion) or tau (no_absorption) set to zero: a reference builds its operators from this
+    problem and zeroes that coefficient before stepping."""
+    if int(np.asarray(pr["absorbing_flag"]).ravel()[0]) not in ALPHA_MODE_FLAGS.values():
+        raise ValueError("not a no_dispersion / no_absorption problem")
     out = dict(pr)
     out["absorbing_flag"] = np.array([[[1]]], dtype=U64)
     return out
