@@ -140,12 +140,12 @@ def test_nonuniform_grid(syn, mode):
 STAGE_GRIDS = [((32, 32, 16), 1), ((32, 32, 16), 0), ((64, 64, 16), 1), ((256, 16, 16), 1), ((100, 16, 108), 1)]
 
 
-def density_and_pressure_stages(syn, dims, plane, which, nonlinear, arrays):
-    """kw_fused_density(terms = 5 | 6) followed by kw_fused_absorption_pressure_one, plain and chained, on the white noise
-    that Grid draws for these dims (the same for every `plane`); returns the grid, its host inputs and, per flags, what
-    the two calls wrote"""
-    from test_gpu_stages import CHAIN_TERMS, TERMS_IN_SCRATCH, Grid
-    g = Grid(syn, dims, plane_kernels=plane)
+def density_and_pressure_stages(g, which, nonlinear, arrays):
+    """kw_fused_density(terms = 5 | 6) followed by kw_fused_absorption_pressure_one, plain and chained, on white noise
+    that the Grid g (test_gpu_stages.Grid) draws next (a fresh Grid of the same dims draws the same for every
+    `plane_kernels`); returns its host inputs and, per flags, what the two calls wrote.  The plain call also stores
+    the three gradients."""
+    from test_gpu_stages import CHAIN_TERMS, TERMS_IN_SCRATCH
     d = g.dev
     u_h = g.comps([g.noise() for _ in range(3)])
     rho_h = g.comps([g.noise() for _ in range(3)])
@@ -165,25 +165,24 @@ def density_and_pressure_stages(syn, dims, plane, which, nonlinear, arrays):
     for flags in (0, CHAIN_TERMS):
         rho = [g.field(x) for x in rho_h]
         t = [g.field(x) for x in t_init]
+        du = [g.field(g.noise()) for _ in range(3)] if flags == 0 else [None] * 3
         d.call("fused_density", nonlinear, *[x.ptr for x in u_d], *[x.ptr for x in rho], *[x.ptr for x in pml_d], ptr(dev["rho0"]),
-               g.padded["kappa"].ptr, *[x.ptr for x in dd], None, None, None, 5 + which, ptr(dev["bona"]), *[x.ptr for x in t], flags)
+               g.padded["kappa"].ptr, *[x.ptr for x in dd], *[ptr(x) for x in du], 5 + which, ptr(dev["bona"]),
+               *[x.ptr for x in t], flags)
         p = g.field(g.noise())
         d.call("fused_absorption_pressure_one", p.ptr, None if flags else t[i_term].ptr, t[i_first].ptr, nabla.ptr, ptr(dev["c2"]),
                ptr(dev["coef"]), which, TERMS_IN_SCRATCH if flags else 0)
-        out[flags] = dict(rho=[x.read() for x in rho], t=[x.read() for x in t], p=p.read())
-    return g, dict(u=u_h, rho=rho_h, pml=pml, med=med, t_init=t_init, i_first=i_first, i_term=i_term), out
+        out[flags] = dict(rho=[x.read() for x in rho], t=[x.read() for x in t], p=p.read(),
+                          du=[x.read() for x in du if x is not None])
+    return dict(u=u_h, rho=rho_h, pml=pml, med=med, t_init=t_init, i_first=i_first, i_term=i_term), out
 
 
-@pytest.mark.parametrize("dims,plane", STAGE_GRIDS)
-@pytest.mark.parametrize("which", [0, 1])
-@pytest.mark.parametrize("nonlinear", [1, 0])
-@pytest.mark.parametrize("arrays", [True, False])
-def test_density_stage_terms(syn, dims, plane, which, nonlinear, arrays):
-    """kw_fused_density(terms = 5 | 6) on white noise between guard bands: densities, `first` and the one term against
-    the fp64 stage function; the chained call stores `first` alone (same bits) and leaves the other t arrays untouched;
-    its spectrum, consumed by kw_fused_absorption_pressure_one(TERMS_IN_SCRATCH), gives the bits of the unchained stage."""
+def density_stage_terms(g, which, nonlinear, arrays, rec=None):
+    """the body of test_density_stage_terms on the Grid g: asserts every bit identity and returns {quantity: rel-L2
+    against fp64}; rec(label, got, fp64), when given, is handed each stored quantity, and p also against the fp64 stage
+    function applied to the float32 `first` and term that the plain call stored (one stage's rounding, not two)"""
     from test_gpu_stages import CHAIN_TERMS
-    g, inp, out = density_and_pressure_stages(syn, dims, plane, which, nonlinear, arrays)
+    inp, out = density_and_pressure_stages(g, which, nonlinear, arrays)
     u_h, rho_h, pml, med, t_init, i_first, i_term = (inp[k] for k in ("u", "rho", "pml", "med", "t_init", "i_first", "i_term"))
     bits = lambda a, b: np.array_equal(a.view(np.uint32), b.view(np.uint32))  # noqa: E731
     for a in range(3):
@@ -208,23 +207,45 @@ def test_density_stage_terms(syn, dims, plane, which, nonlinear, arrays):
     want = knp.stage_absorption_pressure(first, vgt, S, zero if which else g.k64["nabla1"], g.k64["nabla2"] if which else zero,
                                          f8(med["c2"], C2), 0.0 if which else coef, coef if which else 0.0)
     errs["p"] = rel_l2(out[0]["p"], want)
-    print(f"{dims} plane={plane} which={which} nonlinear={nonlinear} arrays={arrays}: {errs}")
-    assert max(errs.values()) <= TOL, errs
-    g.check_readonly()
-    g.close()
+    if rec is not None:
+        for a in range(3):
+            rec(f"one-term rho{a}", out[0]["rho"][a], ref["rho"][a])
+            rec(f"one-term du{a}", out[0]["du"][a], ref["du"][a])
+        rec("one-term first", out[0]["t"][i_first], first)
+        rec("one-term term", out[0]["t"][i_term], S if which else vgt)
+        stored = [out[0]["t"][i].astype(np.float64) for i in (i_first, i_term)]
+        rec("one-term p from the stored term", out[0]["p"], knp.stage_absorption_pressure(
+            stored[0], stored[1], stored[1], zero if which else g.k64["nabla1"], g.k64["nabla2"] if which else zero,
+            f8(med["c2"], C2), 0.0 if which else coef, coef if which else 0.0))
+    return errs
 
 
 @pytest.mark.parametrize("dims,plane", STAGE_GRIDS)
 @pytest.mark.parametrize("which", [0, 1])
+@pytest.mark.parametrize("nonlinear", [1, 0])
 @pytest.mark.parametrize("arrays", [True, False])
-def test_pressure_stage_bits_and_fp64(syn, dims, plane, which, arrays):
-    """kw_fused_absorption_pressure_one on white noise: p against the fp64 stage function; the chained call gives the
-    same p and a spectrum from which kw_fused_velocity(P_IN_SCRATCH) computes the bits it computes from p; the
-    element-wise kernel fed the stage's own inverse-transformed term gives the same bits; the two-term entry point with
-    a zero coefficient array holds the fp64 bound too (its bits are compared and printed, not gated)."""
-    from test_gpu_stages import CHAIN_P, P_IN_SCRATCH, Grid
+def test_density_stage_terms(syn, dims, plane, which, nonlinear, arrays):
+    """kw_fused_density(terms = 5 | 6) on white noise between guard bands: densities, `first` and the one term against
+    the fp64 stage function; the chained call stores `first` alone (same bits) and leaves the other t arrays untouched;
+    its spectrum, consumed by kw_fused_absorption_pressure_one(TERMS_IN_SCRATCH), gives the bits of the unchained stage."""
+    from test_gpu_stages import Grid
     g = Grid(syn, dims, plane_kernels=plane)
+    try:
+        errs = density_stage_terms(g, which, nonlinear, arrays)
+        print(f"{dims} plane={plane} which={which} nonlinear={nonlinear} arrays={arrays}: {errs}")
+        assert max(errs.values()) <= TOL, errs
+        g.check_readonly()
+    finally:
+        g.close()
+
+
+def pressure_stage(g, which, arrays, rec=None):
+    """the body of test_pressure_stage_bits_and_fp64 on the Grid g: asserts every bit identity and returns (rel-L2(p),
+    rel-L2(p of the two-term entry point), whether those two agree in every bit); rec(label, got, fp64), when given, is
+    handed p"""
+    from test_gpu_stages import CHAIN_P, P_IN_SCRATCH
     d = g.dev
+    dims = (g.nx, g.ny, g.nz)
     first_h, term_h = g.noise(), g.noise()
     c2 = g.media(1.0, 3.0) if arrays else None
     coef = g.media(0.5, 1.0) if arrays else None
@@ -281,11 +302,29 @@ def test_pressure_stage_bits_and_fp64(syn, dims, plane, which, arrays):
            g.padded["nabla2"].ptr, ptr(c2_d), *tau_eta, 0)
     p2_h = p2.read()
     err2 = rel_l2(p2_h, want)
-    print(f"{dims} plane={plane} which={which} arrays={arrays}: rel-L2(p) = {err:.3e}, two-term entry {err2:.3e}, "
-          f"two-term bits equal: {bits(p2_h, p_plain)}")
-    assert err <= TOL and err2 <= TOL
-    g.check_readonly()
-    g.close()
+    if rec is not None:
+        rec("one-term pressure stage p", p_plain, want)
+    return err, err2, bits(p2_h, p_plain)
+
+
+@pytest.mark.parametrize("dims,plane", STAGE_GRIDS)
+@pytest.mark.parametrize("which", [0, 1])
+@pytest.mark.parametrize("arrays", [True, False])
+def test_pressure_stage_bits_and_fp64(syn, dims, plane, which, arrays):
+    """kw_fused_absorption_pressure_one on white noise: p against the fp64 stage function; the chained call gives the
+    same p and a spectrum from which kw_fused_velocity(P_IN_SCRATCH) computes the bits it computes from p; the
+    element-wise kernel fed the stage's own inverse-transformed term gives the same bits; the two-term entry point with
+    a zero coefficient array holds the fp64 bound too (its bits are compared and printed, not gated)."""
+    from test_gpu_stages import Grid
+    g = Grid(syn, dims, plane_kernels=plane)
+    try:
+        err, err2, same = pressure_stage(g, which, arrays)
+        print(f"{dims} plane={plane} which={which} arrays={arrays}: rel-L2(p) = {err:.3e}, two-term entry {err2:.3e}, "
+              f"two-term bits equal: {same}")
+        assert err <= TOL and err2 <= TOL
+        g.check_readonly()
+    finally:
+        g.close()
 
 
 @pytest.mark.parametrize("which", [0, 1])
@@ -294,15 +333,19 @@ def test_stage_whole_plane_form_gives_the_bits_of_the_three_launch_form(syn, whi
     """(32,32,16) with plane_kernels 1 and 0 on the same inputs: the density epilogue (terms 5 | 6) and the one-term
     pressure sum, plain and chained, write the same bits in their whole-plane and their three-launch forms"""
     outs = {}
+    from test_gpu_stages import Grid
     for plane in (1, 0):
-        g, _, outs[plane] = density_and_pressure_stages(syn, (32, 32, 16), plane, which, nonlinear, arrays)
-        g.close()
+        g = Grid(syn, (32, 32, 16), plane_kernels=plane)
+        try:
+            _, outs[plane] = density_and_pressure_stages(g, which, nonlinear, arrays)
+        finally:
+            g.close()
     for flags, res in outs[1].items():
         other = outs[0][flags]
         assert np.abs(res["p"]).max() > 0
         assert np.array_equal(res["p"].view(np.uint32), other["p"].view(np.uint32)), ("p", flags)
-        for name in ("rho", "t"):
-            for a in range(3):
+        for name in ("rho", "t", "du"):
+            for a in range(len(res[name])):
                 assert np.array_equal(res[name][a].view(np.uint32), other[name][a].view(np.uint32)), (name, a, flags)
 
 

@@ -213,16 +213,10 @@ def test_entry_points_reject_bad_arguments(syn):
 
 
 # ---- 6: bits --------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("dims,plane", [((32, 32, 16), 1), ((32, 32, 16), 0), ((64, 64, 16), 1), ((256, 16, 16), 1),
-                                        ((100, 16, 108), 1), ((512, 16, 16), 1), ((48, 32, 1), 1)])
-@pytest.mark.parametrize("nonlinear,arrays", [(1, True), (0, False)])
-def test_density_stage_bits_and_fp64(syn, dims, plane, nonlinear, arrays):
-    """kw_fused_density(terms = 4) on white-noise inputs between guard bands: plain and chained give the same p, which
-    is also what kw_sum_pressure_stokes_* computes from the densities and gradients the plain call stored (the path of a
-    step with an active pressure source); p against the fp64 stage functions of the oracle.  The chained spectrum is
-    consumed by kw_fused_velocity(KW_FUSED_P_IN_SCRATCH), which must give the bits of the call that reads p."""
-    from test_gpu_stages import CHAIN_TERMS, P_IN_SCRATCH, Grid
-    g = Grid(syn, dims, plane_kernels=plane)
+def density_stage(g, nonlinear, arrays, rec=None):
+    """the body of test_density_stage_bits_and_fp64 on the Grid g (test_gpu_stages.Grid): asserts every bit identity and
+    returns rel-L2(p) against fp64; rec(label, got, fp64), when given, is handed the stored densities and gradients"""
+    from test_gpu_stages import CHAIN_TERMS, P_IN_SCRATCH
     d = g.dev
     u_h = g.comps([g.noise() for _ in range(3)])
     rho_h = g.comps([g.noise() for _ in range(3)])
@@ -265,6 +259,10 @@ def test_density_stage_bits_and_fp64(syn, dims, plane, nonlinear, arrays):
     else:
         d.call("sum_pressure_stokes_linear", *args, ptr(dev["rho0"]), ptr(dev["tau"]))
     assert np.array_equal(q.read().view(np.uint32), out[0]["p"].view(np.uint32)), "element-wise kernel differs from the epilogue"
+    du_plain = [x.read() for x in out[0]["du_dev"]]
+    for a in range(3):  # inputs of the element-wise kernel, and the p that kw_fused_velocity read
+        assert np.array_equal(out[0]["rho_dev"][a].read().view(np.uint32), out[0]["rho"][a].view(np.uint32)), f"rho{a} changed"
+    assert np.array_equal(out[CHAIN_TERMS]["p_dev"].read().view(np.uint32), out[0]["p"].view(np.uint32)), "p changed"
     # fp64
     f8 = lambda x, s: x.astype(np.float64) if x is not None else s  # noqa: E731
     ref = knp.stage_density([x.astype(np.float64) for x in u_h], [x.astype(np.float64) for x in rho_h],
@@ -273,11 +271,30 @@ def test_density_stage_bits_and_fp64(syn, dims, plane, nonlinear, arrays):
     S, first, vgt = (ref["t"][0], ref["t"][1], ref["t"][2]) if nonlinear else (ref["t"][0], ref["t"][0], ref["t"][1])
     ones = np.ones((g.nz, g.ny, g.nx // 2 + 1))
     want = knp.stage_absorption_pressure(first, vgt, S, ones, 0.0 * ones, f8(med["c2"], C2), f8(med["tau"], TAU), 0.0)
-    err = rel_l2(out[0]["p"], want)
-    print(f"{dims} plane={plane} nonlinear={nonlinear} arrays={arrays}: rel-L2(p) = {err:.3e}")
-    assert err <= TOL
-    g.check_readonly()
-    g.close()
+    if rec is not None:  # what the plain call stored, quantity by quantity
+        for a in range(3):
+            rec(f"stokes rho{a}", out[0]["rho"][a], ref["rho"][a])
+            rec(f"stokes du{a}", du_plain[a], ref["du"][a])
+    return rel_l2(out[0]["p"], want)
+
+
+@pytest.mark.parametrize("dims,plane", [((32, 32, 16), 1), ((32, 32, 16), 0), ((64, 64, 16), 1), ((256, 16, 16), 1),
+                                        ((100, 16, 108), 1), ((512, 16, 16), 1), ((48, 32, 1), 1)])
+@pytest.mark.parametrize("nonlinear,arrays", [(1, True), (0, False)])
+def test_density_stage_bits_and_fp64(syn, dims, plane, nonlinear, arrays):
+    """kw_fused_density(terms = 4) on white-noise inputs between guard bands: plain and chained give the same p, which
+    is also what kw_sum_pressure_stokes_* computes from the densities and gradients the plain call stored (the path of a
+    step with an active pressure source); p against the fp64 stage functions of the oracle.  The chained spectrum is
+    consumed by kw_fused_velocity(KW_FUSED_P_IN_SCRATCH), which must give the bits of the call that reads p."""
+    from test_gpu_stages import Grid
+    g = Grid(syn, dims, plane_kernels=plane)
+    try:
+        err = density_stage(g, nonlinear, arrays)
+        print(f"{dims} plane={plane} nonlinear={nonlinear} arrays={arrays}: rel-L2(p) = {err:.3e}")
+        assert err <= TOL
+        g.check_readonly()
+    finally:
+        g.close()
 
 
 @pytest.mark.parametrize("dims", [(32, 32, 32), (64, 64, 16)])

@@ -1,5 +1,9 @@
 """Every entry point of csrc/kw_solver_kernels.hip, and the 1-D FFT wrapper, called on its own against a float64
-restatement of its header and the SolverCudaKernels.cu lines it cites.
+restatement of its header and the SolverCudaKernels.cu lines it cites.  That includes the kernels without a counterpart in
+the reference, restated from include/kwave_hip.h alone: kw_sum_pressure_stokes_{nonlinear,linear} (Stokes absorption),
+kw_sum_pressure_terms_one_{nonlinear,linear} and kw_compute_absorbtion_term_one (one-term power law).  The fused
+epilogues are compared with the first four bit for bit (tests/test_gpu_absorption_lengths.py); both sides of that
+comparison call one __device__ function, so the exact numpy float32 restatements here are what pins that function.
 
 Inputs are white noise with O(1) media, PML vectors in (0, 1] and random complex ddx/ddy/ddz.  Every array sits between
 NaN guard bands (gpu_buffers.Guarded); read-only inputs must come back unchanged.
@@ -359,6 +363,67 @@ def test_sum_pressure_linear_lossless(dev, dims, c2_array):
         check_variants(dev, "sum_pressure_linear_lossless", items, out)
 
 
+def pick(g, array, name):
+    """the float32 operand of an exact restatement: the array, or the scalar of kw_constants that NULL selects"""
+    return np.float32(getattr(g.k, name)) if array is None else array
+
+
+STOKES_MEDIA = (15, 0, 5, 10)  # bits: c2, bona, rho0, tau arrays (all, none, and each argument once on either side)
+
+
+@pytest.mark.parametrize("media", STOKES_MEDIA, ids=lambda m: f"c2={m & 1} bona={(m >> 1) & 1} rho0={(m >> 2) & 1} tau={m >> 3}")
+@pytest.mark.parametrize("nonlinear", [True, False], ids=["nonlinear", "linear"])
+@pytest.mark.parametrize("dims", GRIDS, ids=gid)
+def test_sum_pressure_stokes(dev, dims, nonlinear, media):
+    """kwave_hip.h (Stokes absorption), exact: every product and sum rounded on its own, in the header's order (the
+    shared kw_stokes_pressure switches fma contraction off; the division is correctly rounded, 2 rho0 is exact):
+      rhoSum = (rx + ry) + rz;  duSum = (dx + dy) + dz;  absorb = tau (rho0 duSum)
+      first = rhoSum  |  (((B/A rhoSum) rhoSum) / (2 rho0)) + rhoSum;  p = c2 (first + absorb)
+    The fused density epilogue (terms == 4) is compared with this kernel bit for bit elsewhere; both call one __device__
+    function, so this restatement is what pins that function itself."""
+    g = G(dev, dims)
+    r, du = [g.noise() for _ in range(3)], [g.noise() for _ in range(3)]
+    c2, bona = opt_array(g, media & 1, 1.0, 3.0), opt_array(g, nonlinear and media & 2, 0.2, 1.0)
+    rho0, tau = opt_array(g, media & 4, 0.8, 1.8), opt_array(g, media & 8, 0.5, 1.0)
+    entry = "sum_pressure_stokes_nonlinear" if nonlinear else "sum_pressure_stokes_linear"
+    items = [Arg("p", g.noise())] + [Arg(f"r{a}", r[a], ro=True) for a in range(3)] + \
+            [Arg(f"du{a}", du[a], ro=True) for a in range(3)] + [Arg("c2", c2, ro=True)] + \
+            ([Arg("bona", bona, ro=True)] if nonlinear else []) + [Arg("rho0", rho0, ro=True), Arg("tau", tau, ro=True)]
+    out = call(dev, entry, items)
+    cc, b, r0, ta = pick(g, c2, "c2"), pick(g, bona, "b_on_a"), pick(g, rho0, "rho0"), pick(g, tau, "absorb_tau")
+    rho_sum, du_sum = (r[0] + r[1]) + r[2], (du[0] + du[1]) + du[2]
+    absorb = ta * (r0 * du_sum)
+    first = (((b * rho_sum) * rho_sum) / (np.float32(2.0) * r0)) + rho_sum if nonlinear else rho_sum
+    check_exact(f"{entry} media={media}", out["p"], cc * (first + absorb))
+    if g.aligned:
+        check_variants(dev, entry, items, out, None if media == 15 else ["p", "r1", "du2"])
+
+
+@pytest.mark.parametrize("which", [0, 1], ids=["no_dispersion", "no_absorption"])
+@pytest.mark.parametrize("coef_array", [True, False], ids=["coef array", "coef scalar"])
+@pytest.mark.parametrize("c2_array", [True, False], ids=["c2 array", "c2 scalar"])
+@pytest.mark.parametrize("entry", ["sum_pressure_terms_one_nonlinear", "sum_pressure_terms_one_linear"])
+@pytest.mark.parametrize("dims", GRIDS, ids=gid)
+def test_sum_pressure_terms_one(dev, dims, entry, c2_array, coef_array, which):
+    """kwave_hip.h (one-term power law), exact: p = c2 (first + (fd (term coef))) for which == 0 (coef NULL -> absorb_tau),
+    p = c2 (first - (fd (term coef))) for which == 1 (coef NULL -> absorb_eta); no fma contraction (kw_one_term_pressure)"""
+    g = G(dev, dims)
+    first, term = g.noise(), g.noise()
+    c2 = opt_array(g, c2_array, 1.0, 3.0)
+    coef = opt_array(g, coef_array, 0.2, 1.0)
+    terms = [Arg("first", first, ro=True), Arg("term", term, ro=True)]
+    if entry == "sum_pressure_terms_one_linear":   # (p, term, densitySum, ...)
+        terms = terms[::-1]
+    items = [Arg("p", g.noise())] + terms + [Arg("c2", c2, ro=True), Arg("coef", coef, ro=True), which]
+    out = call(dev, entry, items)
+    cc, co = pick(g, c2, "c2"), pick(g, coef, "absorb_eta" if which else "absorb_tau")
+    scaled = np.float32(g.k.fft_divider) * (term * co)
+    check_exact(f"{entry} c2={c2_array} coef={coef_array} which={which}", out["p"],
+                cc * (first - scaled) if which else cc * (first + scaled))
+    if g.aligned:
+        check_variants(dev, entry, items, out, None if (c2_array and coef_array) else ["p", "term"])
+
+
 @pytest.mark.parametrize("c2_array", [True, False], ids=["c2 array", "c2 scalar"])
 @pytest.mark.parametrize("dims", GRIDS, ids=gid)
 def test_add_initial_pressure_source(dev, dims, c2_array):
@@ -500,6 +565,19 @@ def test_compute_absorbtion_term(dev, dims):
     check_exact("absorption B", out["B"], Bh * n2[..., None])
     if g.aligned:
         check_variants(dev, "compute_absorbtion_term", items, out)
+
+
+@pytest.mark.parametrize("dims", GRIDS, ids=gid)
+def test_compute_absorbtion_term_one(dev, dims):
+    """kwave_hip.h (one-term power law), exact: the same for one spectrum, A *= nabla (k_absorbtion_term_one scales both
+    parts by the real operator: one product per component, no sum)"""
+    g = G(dev, dims)
+    Ah, n = g.cnoise(g.cshape), g.media(0.0, 2.0, g.cshape)
+    items = [Arg("A", Ah, cplx=True), Arg("n", n, ro=True)]
+    out = call(dev, "compute_absorbtion_term_one", items)
+    check_exact("absorption term, one spectrum", out["A"], Ah * n[..., None])
+    if g.aligned:
+        check_variants(dev, "compute_absorbtion_term_one", items, out)
 
 
 @pytest.mark.parametrize("dims", GRIDS, ids=gid)
