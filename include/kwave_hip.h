@@ -590,6 +590,22 @@ KW_API kw_status kw_element_source_row(kw_ctx* ctx, float* row, const float* ele
 KW_API kw_status kw_sample_elements(kw_ctx* ctx, float* out, const float* p, const uint32_t* ptr,
                                     const kw_csr_entry* entries, uint32_t n_elements, uint64_t nnz,
                                     const uint32_t* chunk_ptr, uint32_t n_chunks, float* partials);
+/* The velocity components of an array share one index set and one weight matrix: these two forms serve up to three fields
+ * in one pass over the CSR, each entry read once.
+ * kw_element_source_rows: rows[c] = the row kw_element_source_row gives for element_inputs[c] at time_index, bit for bit
+ * (same CSR order, same fma chain from 0, one thread per point), for c = 0, 1, 2 in one launch.  rows and element_inputs
+ * are host arrays of three device pointers; a component whose rows[c] is NULL is skipped and element_inputs[c] is then
+ * never read, on the host or on the device.  With all three NULL nothing is launched. */
+KW_API kw_status kw_element_source_rows(kw_ctx* ctx, float* const rows[3], const float* const element_inputs[3],
+                                        const uint32_t* ptr, const kw_csr_entry* entries, uint32_t n_points,
+                                        uint32_t n_elements, uint64_t time_index);
+/* kw_sample_elements_multi: outs[f][e] = what kw_sample_elements gives on fields[f], bit for bit, for f < n_fields
+ * (1 .. 3): the same chunks, per-lane stride, wave64 butterfly and four-wave pairing with one accumulator per field, then
+ * one launch that adds the chunk partials of every field in chunk order.  outs and fields are host arrays of n_fields
+ * device pointers; partials holds n_fields * n_chunks floats (field f's chunk b at f * n_chunks + b).  No atomics. */
+KW_API kw_status kw_sample_elements_multi(kw_ctx* ctx, uint32_t n_fields, float* const outs[], const float* const fields[],
+                                          const uint32_t* ptr, const kw_csr_entry* entries, uint32_t n_elements,
+                                          uint64_t nnz, const uint32_t* chunk_ptr, uint32_t n_chunks, float* partials);
 
 #ifdef __cplusplus
 }

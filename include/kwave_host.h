@@ -39,7 +39,14 @@ typedef struct kwh_dataset
  *   p_source_element_weight float  (1, 1, nnz)            weight of each entry
  * make point k receive v_k(t) = sum_j weight_j * signal[t][element_j] (fp32 fma in CSR order); p_source_mode then applies
  * as to a p_source_many = 1 source with series row t = v(t).  p_source_input must be absent and p_source_many, if
- * given, 1.  kwh_create checks every CSR (offsets, counts, element and grid index ranges) and names the dataset. */
+ * given, 1.  kwh_create checks every CSR (offsets, counts, element and grid index ranges) and names the dataset.
+ *
+ * Weighted velocity source: the same for ux / uy / uz.  The components share u_source_index and therefore one CSR:
+ *   u_source_element_ptr / _index / _weight   as p_source_element_*, row k = point k of u_source_index
+ *   ux_ / uy_ / uz_source_element_input float (1, u?_source_flag, E)  one signal per element, per component
+ * A component is active when its flag is above 0; the active components are all weighted or all plain, share E, and
+ * may have different flags (a component stops when its own flag runs out).  u?_source_input must be absent,
+ * u_source_many, if given, 1, and transducer_source_flag 0.  u_source_mode applies as to a u_source_many = 1 source. */
 
 /* what the reference takes from the command line for the loop (CommandLineParameters.cpp:264-292) */
 typedef struct kwh_options
@@ -96,6 +103,11 @@ typedef struct kwh_options
                                  of the CSR (sensor_element_ptr: E + 1 0-based offsets; sensor_element_index: 1-based
                                  linear grid indices).  Independent of sensor_mask_*.  Without the three datasets,
                                  kwh_create fails. */
+  int32_t  u_elements;        /* --u_elements: the same weighted sensor over the staggered velocities: streams "ux_elements",
+                                 "uy_elements" and (3-D) "uz_elements", each (Nt - s) rows of E values; the components are
+                                 reduced together, one read of the CSR per step (kw_sample_elements_multi) */
+  int32_t  u_non_staggered_elements; /* --u_non_staggered_elements: the same over the velocities shifted to the pressure
+                                 grid (as --u_non_staggered_raw samples them): "ux_non_staggered_elements", ... */
 } kwh_options;
 /* gathers `bytes` bytes of every rank, in rank order, into all (nranks * bytes); the same result on every rank; 0 = ok.
  * Any transport the launcher has will do: MPI_Allgather, torch.distributed.all_gather on a gloo group, files. */

@@ -5,6 +5,8 @@ The solver takes the array in this weighted form (include/kwave_host.h):
 
 * source: `p_source_element_input` (one signal per element) and a point-major CSR matrix (`p_source_element_ptr`,
   `p_source_element_index`, `p_source_element_weight`) over the points of `p_source_index`;
+* velocity source: the same with `u_source_element_ptr/_index/_weight` over the points of `u_source_index`, shared by
+  the components, and `ux_/uy_/uz_source_element_input` (one signal per element and component);
 * sensor (`--p_elements`): an element-major CSR matrix (`sensor_element_ptr`, `sensor_element_index`,
   `sensor_element_weight`) whose rows give one value per element and step, `p_elements[t][e] = sum_j w_j p[index_j]`.
 
@@ -63,6 +65,29 @@ def weighted_source(elements: Sequence[Element], signals: np.ndarray) -> Dict[st
     }
 
 
+def weighted_velocity_source(elements: Sequence[Element], signals_x=None, signals_y=None, signals_z=None
+                             ) -> Dict[str, np.ndarray]:
+    """Datasets of a weighted velocity source.  signals_x / _y / _z: (Nt_src, E) arrays or None; a component left out is
+    not driven (its flag is 0).  The components may differ in Nt_src.  The points and the CSR are those of
+    weighted_source and are shared by the components; u_source_many is 1 and u_source_mode is left to the caller."""
+    given = {c: np.asarray(s, dtype=np.float32) for c, s in (("x", signals_x), ("y", signals_y), ("z", signals_z))
+             if s is not None}
+    if not given:
+        raise ValueError("a weighted velocity source needs the signals of at least one component")
+    for c, sig in given.items():
+        if sig.ndim != 2 or sig.shape[1] != len(elements):
+            raise ValueError(f"signals_{c} must be (Nt, E={len(elements)}), got {sig.shape}")
+    csr = weighted_source(elements, next(iter(given.values())))
+    out = {"u_source_index": csr["p_source_index"], "u_source_many": np.array([[[1]]], dtype=U64)}
+    for part in ("ptr", "index", "weight"):
+        out["u_source_element_" + part] = csr["p_source_element_" + part]
+    for c in "xyz":
+        out[f"u{c}_source_flag"] = np.array([[[given[c].shape[0] if c in given else 0]]], dtype=U64)
+        if c in given:
+            out[f"u{c}_source_element_input"] = np.ascontiguousarray(given[c]).reshape(1, *given[c].shape)
+    return out
+
+
 def weighted_sensor(elements: Sequence[Element]) -> Dict[str, np.ndarray]:
     """Datasets of a weighted sensor (record it with --p_elements / HostSolver(..., p_elements=1)): element e's row holds
     its points and weights in the order given."""
@@ -90,6 +115,20 @@ def expand_source(ds: Dict[str, np.ndarray]) -> np.ndarray:
     out = np.zeros((sig.shape[0], ptr.size - 1), dtype=np.float64)
     np.add.at(out.T, rows, (w[:, None] * sig[:, col].T))
     return out.astype(np.float32).reshape(1, sig.shape[0], -1)
+
+
+def expand_velocity_source(ds: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
+    """The expanded (u_source_many = 1) series of a weighted velocity source: {"ux_source_input": (1, Nt_src, Npts)
+    float32, ...} for the components that `ds` drives, each as expand_source gives it."""
+    out = {}
+    for c in "xyz":
+        name = f"u{c}_source_element_input"
+        if name in ds:
+            one = {"p_source_element_input": ds[name]}
+            for part in ("ptr", "index", "weight"):
+                one["p_source_element_" + part] = ds["u_source_element_" + part]
+            out[f"u{c}_source_input"] = expand_source(one)
+    return out
 
 
 def sensor_matrix(ds: Dict[str, np.ndarray], n_grid: int) -> np.ndarray:

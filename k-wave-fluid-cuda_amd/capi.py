@@ -179,6 +179,8 @@ _SIG: Dict[str, list] = {
     "kw_divide": [_P, _P, C.c_float, _U64],
     "kw_element_source_row": [_P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _U64],
     "kw_sample_elements": [_P, _P, _P, _P, _P, C.c_uint32, _U64, _P, C.c_uint32, _P],
+    "kw_element_source_rows": [_P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _U64],
+    "kw_sample_elements_multi": [_P, C.c_uint32, _P, _P, _P, _P, C.c_uint32, _U64, _P, C.c_uint32, _P],
 }
 
 ELEMENT_CHUNK = 1024  # KW_ELEMENT_CHUNK

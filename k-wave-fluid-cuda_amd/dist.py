@@ -65,13 +65,15 @@ def partition_problem(pr: Dict[str, np.ndarray], rank: int, nranks: int, arrays_
     if "u_source_index" in pr:
         u_sel, u_loc = local_index(pr["u_source_index"])
 
-    # weighted pressure source: this rank's points keep their CSR rows (ptr rebuilt); the element signals are replicated
-    src_rows = None
-    if p_sel is not None and "p_source_element_ptr" in pr:
-        ptr = np.asarray(pr["p_source_element_ptr"]).reshape(-1).astype(np.int64)
-        src_rows = np.concatenate([np.arange(ptr[k], ptr[k + 1]) for k in p_sel]) if p_sel.size else np.zeros(0, np.int64)
-        lens = ptr[p_sel + 1] - ptr[p_sel]
-        out["p_source_element_ptr"] = np.concatenate([[0], np.cumsum(lens)]).astype(U64).reshape(1, 1, -1)
+    # weighted pressure / velocity source: this rank's points keep their CSR rows (ptr rebuilt); the element signals are
+    # replicated
+    src_rows = {}
+    for q, q_sel in (("p", p_sel), ("u", u_sel)):
+        if q_sel is not None and q + "_source_element_ptr" in pr:
+            ptr = np.asarray(pr[q + "_source_element_ptr"]).reshape(-1).astype(np.int64)
+            src_rows[q] = np.concatenate([np.arange(ptr[k], ptr[k + 1]) for k in q_sel]) if q_sel.size else np.zeros(0, np.int64)
+            lens = ptr[q_sel + 1] - ptr[q_sel]
+            out[q + "_source_element_ptr"] = np.concatenate([[0], np.cumsum(lens)]).astype(U64).reshape(1, 1, -1)
     # weighted sensor: the entries whose grid point lies in this slab, re-based; all E rows stay (possibly empty)
     if "sensor_element_ptr" in pr:
         ptr = np.asarray(pr["sensor_element_ptr"]).reshape(-1).astype(np.int64)
@@ -85,10 +87,11 @@ def partition_problem(pr: Dict[str, np.ndarray], rank: int, nranks: int, arrays_
 
     for name, a in pr.items():
         a = np.asarray(a)
-        if name in ("p_source_element_ptr", "sensor_element_ptr", "sensor_element_index", "sensor_element_weight"):
+        if name in ("p_source_element_ptr", "u_source_element_ptr", "sensor_element_ptr", "sensor_element_index",
+                    "sensor_element_weight"):
             continue  # built above
-        if name in ("p_source_element_index", "p_source_element_weight") and src_rows is not None:
-            out[name] = np.ascontiguousarray(a.reshape(-1)[src_rows]).reshape(1, 1, -1)
+        if name[1:] in ("_source_element_index", "_source_element_weight") and name[0] in src_rows:
+            out[name] = np.ascontiguousarray(a.reshape(-1)[src_rows[name[0]]]).reshape(1, 1, -1)
             continue
         if name == "Nz":
             out[name] = np.array([[[z1 - z0]]], dtype=U64)

@@ -127,7 +127,9 @@ INPUT_DATASETS = (
     "uz_source_input", "transducer_source_input", "delay_mask", "sensor_mask_index", "sensor_mask_corners",
     # weighted transducer arrays (new with this build): element signals and CSR weight matrices
     "p_source_element_input", "p_source_element_ptr", "p_source_element_index", "p_source_element_weight",
-    "sensor_element_ptr", "sensor_element_index", "sensor_element_weight")
+    "sensor_element_ptr", "sensor_element_index", "sensor_element_weight",
+    "u_source_element_ptr", "u_source_element_index", "u_source_element_weight",
+    "ux_source_element_input", "uy_source_element_input", "uz_source_element_input")
 
 
 def dataset_exists(path: str, name: str) -> bool:

@@ -8,7 +8,8 @@
 
 static kw_ctx* ctx() { return Parameters::getInstance().getHipParameters().getContext(); }
 
-void ElementCsr::upload(const size_t* ptr, size_t rows, const size_t* cols1, const float* weights, size_t nnz, bool chunks)
+void ElementCsr::upload(const size_t* ptr, size_t rows, const size_t* cols1, const float* weights, size_t nnz, bool chunks,
+                        size_t fields)
 {
   release();
   mRows = rows;
@@ -31,7 +32,7 @@ void ElementCsr::upload(const size_t* ptr, size_t rows, const size_t* cols1, con
   {
     mChunkPtr = static_cast<uint32_t*>(put(cp.data(), cp.size() * sizeof(uint32_t)));
     void* d   = nullptr;
-    kwCheck(kw_malloc(ctx(), mChunks * sizeof(float), &d));
+    kwCheck(kw_malloc(ctx(), fields * mChunks * sizeof(float), &d));
     mPartials = static_cast<float*>(d);
   }
 }

@@ -19,7 +19,9 @@ class ElementCsr
   ElementCsr(const ElementCsr&)            = delete;
   ElementCsr& operator=(const ElementCsr&) = delete;
 
-  void upload(const size_t* ptr, size_t rows, const size_t* cols1, const float* weights, size_t nnz, bool chunks);
+  /// fields: how many fields one kw_sample_elements_multi call reduces over this matrix (sizes the partial sums)
+  void upload(const size_t* ptr, size_t rows, const size_t* cols1, const float* weights, size_t nnz, bool chunks,
+              size_t fields = 1);
   void release();
 
   size_t               rows() const { return mRows; }

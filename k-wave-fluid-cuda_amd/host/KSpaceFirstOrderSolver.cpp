@@ -41,6 +41,7 @@ void KSpaceFirstOrderSolver::freeMemory()
 {
   releaseFusedPipeline();
   mSourceElements.release();
+  mVelocitySourceElements.release();
   mOutputStreamContainer.freeStreams();
   mMatrixContainer.freeMatrices();
   HipFftComplexMatrix::destroyAllPlansAndStaticData();
@@ -55,6 +56,11 @@ void KSpaceFirstOrderSolver::loadInputData(const InputProvider& input)
     mSourceElements.upload(index(MI::kPressureSourceElementPtr).getHostData(), mParameters.getPressureSourceIndexSize(),
                            index(MI::kPressureSourceElementIndex).getHostData(),
                            real(MI::kPressureSourceElementWeight).getHostData(), mParameters.getPressureSourceElementNnz(), false);
+  if (mParameters.getVelocitySourceElementFlag())
+    mVelocitySourceElements.upload(index(MI::kVelocitySourceElementPtr).getHostData(), mParameters.getVelocitySourceIndexSize(),
+                                   index(MI::kVelocitySourceElementIndex).getHostData(),
+                                   real(MI::kVelocitySourceElementWeight).getHostData(),
+                                   mParameters.getVelocitySourceElementNnz(), false);
   mOutputStreamContainer.createStreams();
 }
 
@@ -779,21 +785,44 @@ template<SD sd> void KSpaceFirstOrderSolver::computePressureLinear()
 void KSpaceFirstOrderSolver::addVelocitySource()
 { // :2252-2303
   const size_t timeIndex = mParameters.getTimeIndex();
-  struct Comp { size_t flag; MI u; MI input; };
-  const Comp comps[3] = {{mParameters.getVelocityXSourceFlag(), MI::kUxSgx, MI::kVelocityXSourceInput},
-                         {mParameters.getVelocityYSourceFlag(), MI::kUySgy, MI::kVelocityYSourceInput},
-                         {mParameters.getVelocityZSourceFlag(), MI::kUzSgz, MI::kVelocityZSourceInput}};
+  struct Comp { size_t flag; MI u; MI input; MI elementInput; };
+  const Comp comps[3] = {
+    {mParameters.getVelocityXSourceFlag(), MI::kUxSgx, MI::kVelocityXSourceInput, MI::kVelocityXSourceElementInput},
+    {mParameters.getVelocityYSourceFlag(), MI::kUySgy, MI::kVelocityYSourceInput, MI::kVelocityYSourceElementInput},
+    {mParameters.getVelocityZSourceFlag(), MI::kUzSgz, MI::kVelocityZSourceInput, MI::kVelocityZSourceElementInput}};
+  // weighted source: this step's rows v_c(t) = W s_c(t) of the components still running go into their one-row series
+  // buffers in one launch; the kernels below then read row 0 of a u_source_many = 1 source (as addPressureSource does)
+  size_t seriesRow = timeIndex;
+  if (mParameters.getVelocitySourceElementFlag())
+  {
+    float*       rows[3]   = {nullptr, nullptr, nullptr};
+    const float* inputs[3] = {nullptr, nullptr, nullptr};
+    bool any = false;
+    for (int c = 0; c < 3; c++)
+    {
+      if (!(comps[c].flag > timeIndex)) continue;
+      rows[c]   = real(comps[c].input).getDeviceData();
+      inputs[c] = real(comps[c].elementInput).getDeviceData();
+      any       = true;
+    }
+    if (any)
+      kwCheck(kw_element_source_rows(mParameters.getHipParameters().getContext(), rows, inputs, mVelocitySourceElements.ptr(),
+                                     mVelocitySourceElements.entries(),
+                                     static_cast<uint32_t>(mParameters.getVelocitySourceIndexSize()),
+                                     static_cast<uint32_t>(mParameters.getVelocitySourceElementCount()), timeIndex));
+    seriesRow = 0;
+  }
   for (const Comp& c : comps)
   {
     if (!(c.flag > timeIndex)) continue;
     if (mParameters.getVelocitySourceMode() != Parameters::SourceMode::kAdditive)
     {
-      SolverHipKernels::addVelocitySource(real(c.u), real(c.input), index(MI::kVelocitySourceIndex));
+      SolverHipKernels::addVelocitySource(real(c.u), real(c.input), index(MI::kVelocitySourceIndex), seriesRow);
     }
     else
     {
       RealMatrix& scaledSource = getTemp1RealND();
-      scaleSource(scaledSource, real(c.input), index(MI::kVelocitySourceIndex), mParameters.getVelocitySourceMany(), timeIndex);
+      scaleSource(scaledSource, real(c.input), index(MI::kVelocitySourceIndex), mParameters.getVelocitySourceMany(), seriesRow);
       SolverHipKernels::addVelocityScaledSource(real(c.u), scaledSource);
     }
   }

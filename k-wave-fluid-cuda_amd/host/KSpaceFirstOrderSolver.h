@@ -117,5 +117,6 @@ class KSpaceFirstOrderSolver
   float*                mNabla2Padded = nullptr;
   float*                mSourceKappaPadded = nullptr;
   ElementCsr            mSourceElements; // weighted pressure source: point <- element weights (Parameters::getPressureSourceElementFlag)
+  ElementCsr            mVelocitySourceElements; // weighted velocity source, all components (getVelocitySourceElementFlag)
 };
 #endif

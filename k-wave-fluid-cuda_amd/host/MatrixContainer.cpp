@@ -77,7 +77,14 @@ bool anyVelocityIndex(const P& p) { return transducer(p) || uxSource(p) || uySou
 bool pSource(const P& p) { return p.getPressureSourceFlag() != 0; }
 bool pSourceWeighted(const P& p) { return pSource(p) && p.getPressureSourceElementFlag(); }
 bool pSourceExpanded(const P& p) { return pSource(p) && !p.getPressureSourceElementFlag(); }
-bool sensorElements(const P& p) { return p.getStorePressureElementsFlag(); }
+bool sensorElements(const P& p) { return p.getStoreAnyElementsFlag(); }
+bool uWeighted(const P& p) { return p.getVelocitySourceElementFlag(); }
+bool uxSourceWeighted(const P& p) { return uxSource(p) && uWeighted(p); }
+bool uySourceWeighted(const P& p) { return uySource(p) && uWeighted(p); }
+bool uzSourceWeighted(const P& p) { return uzSource(p) && uWeighted(p); }
+bool uxSourceExpanded(const P& p) { return uxSource(p) && !uWeighted(p); }
+bool uySourceExpanded(const P& p) { return uySource(p) && !uWeighted(p); }
+bool uzSourceExpanded(const P& p) { return uzSource(p) && !uWeighted(p); }
 bool kSpaceCorrectedSource(const P& p)
 {
   return ((p.getVelocitySourceMode() == P::SourceMode::kAdditive) || (p.getPressureSourceMode() == P::SourceMode::kAdditive)) &&
@@ -104,6 +111,13 @@ DimensionSizes dimsSensorElementEntries(const P& p) { return DimensionSizes(1, 1
 DimensionSizes dimsUxInput(const P& p) { return seriesOf(p.getVelocitySourceMany(), p.getVelocitySourceIndexSize(), p.getVelocityXSourceFlag()); }
 DimensionSizes dimsUyInput(const P& p) { return seriesOf(p.getVelocitySourceMany(), p.getVelocitySourceIndexSize(), p.getVelocityYSourceFlag()); }
 DimensionSizes dimsUzInput(const P& p) { return seriesOf(p.getVelocitySourceMany(), p.getVelocitySourceIndexSize(), p.getVelocityZSourceFlag()); }
+// weighted velocity source: per component flag x E element signals and one row of Npts values; one CSR for all of them
+DimensionSizes dimsUxElementInput(const P& p) { return DimensionSizes(p.getVelocitySourceElementCount(), p.getVelocityXSourceFlag(), 1); }
+DimensionSizes dimsUyElementInput(const P& p) { return DimensionSizes(p.getVelocitySourceElementCount(), p.getVelocityYSourceFlag(), 1); }
+DimensionSizes dimsUzElementInput(const P& p) { return DimensionSizes(p.getVelocitySourceElementCount(), p.getVelocityZSourceFlag(), 1); }
+DimensionSizes dimsVelocityRow(const P& p) { return DimensionSizes(std::max<size_t>(p.getVelocitySourceIndexSize(), 1), 1, 1); }
+DimensionSizes dimsVelocityElementPtr(const P& p) { return DimensionSizes(1, 1, p.getVelocitySourceIndexSize() + 1); }
+DimensionSizes dimsVelocityElementEntries(const P& p) { return DimensionSizes(1, 1, p.getVelocitySourceElementNnz()); }
 DimensionSizes dimsShiftTemp(const P& p)
 { // the 1-D transform workspace of the non-staggered velocity: the largest of the three half-spectra (MatrixContainer.cpp:336-352)
   const DimensionSizes g = p.getFullDimensionSizes();
@@ -196,9 +210,18 @@ const Row kSchema[] = {
   { MI::kSensorElementIndex, MT::kIndex, Extent::kByRule, dimsSensorElementEntries, kFromFile, kSensorElementIndexName, sensorElements },
   { MI::kSensorElementWeight, MT::kReal, Extent::kByRule, dimsSensorElementEntries, kFromFile, kSensorElementWeightName, sensorElements },
   { MI::kPressureSourceIndex, MT::kIndex, Extent::kByRule, dimsPressureIndex, kFromFile, kPressureSourceIndexName, pSource },
-  { MI::kVelocityXSourceInput, MT::kReal, Extent::kByRule, dimsUxInput, kFromFile, kVelocityXSourceInputName, uxSource },
-  { MI::kVelocityYSourceInput, MT::kReal, Extent::kByRule, dimsUyInput, kFromFile, kVelocityYSourceInputName, uySource },
-  { MI::kVelocityZSourceInput, MT::kReal, Extent::kByRule, dimsUzInput, kFromFile, kVelocityZSourceInputName, uzSource },
+  { MI::kVelocityXSourceInput, MT::kReal, Extent::kByRule, dimsUxInput, kFromFile, kVelocityXSourceInputName, uxSourceExpanded },
+  { MI::kVelocityYSourceInput, MT::kReal, Extent::kByRule, dimsUyInput, kFromFile, kVelocityYSourceInputName, uySourceExpanded },
+  { MI::kVelocityZSourceInput, MT::kReal, Extent::kByRule, dimsUzInput, kFromFile, kVelocityZSourceInputName, uzSourceExpanded },
+  { MI::kVelocityXSourceInput, MT::kReal, Extent::kByRule, dimsVelocityRow, 0, "ux_source_row", uxSourceWeighted },
+  { MI::kVelocityYSourceInput, MT::kReal, Extent::kByRule, dimsVelocityRow, 0, "uy_source_row", uySourceWeighted },
+  { MI::kVelocityZSourceInput, MT::kReal, Extent::kByRule, dimsVelocityRow, 0, "uz_source_row", uzSourceWeighted },
+  { MI::kVelocityXSourceElementInput, MT::kReal, Extent::kByRule, dimsUxElementInput, kFromFile, kVelocityXSourceElementInputName, uxSourceWeighted },
+  { MI::kVelocityYSourceElementInput, MT::kReal, Extent::kByRule, dimsUyElementInput, kFromFile, kVelocityYSourceElementInputName, uySourceWeighted },
+  { MI::kVelocityZSourceElementInput, MT::kReal, Extent::kByRule, dimsUzElementInput, kFromFile, kVelocityZSourceElementInputName, uzSourceWeighted },
+  { MI::kVelocitySourceElementPtr, MT::kIndex, Extent::kByRule, dimsVelocityElementPtr, kFromFile, kVelocitySourceElementPtrName, uWeighted },
+  { MI::kVelocitySourceElementIndex, MT::kIndex, Extent::kByRule, dimsVelocityElementEntries, kFromFile, kVelocitySourceElementIndexName, uWeighted },
+  { MI::kVelocitySourceElementWeight, MT::kReal, Extent::kByRule, dimsVelocityElementEntries, kFromFile, kVelocitySourceElementWeightName, uWeighted },
   // non-staggered velocity (MatrixContainer.cpp:330-385); z lines and z_shift_neg_r keep their global length on a slab
   { MI::kTempHipFftShift, MT::kFft, Extent::kByRule, dimsShiftTemp, 0, "hipfft_shift_temp", shifted },
   GRID(kUxShifted, 0, "ux_shifted", shifted),

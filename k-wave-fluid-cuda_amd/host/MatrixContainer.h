@@ -41,7 +41,10 @@ class MatrixContainer
     // weighted transducer arrays: element signals + CSR of the source, CSR of the sensor (read from the input; the
     // device copies the kernels use are packed by ElementCsr, ElementArrays.h)
     kPressureSourceElementInput, kPressureSourceElementPtr, kPressureSourceElementIndex, kPressureSourceElementWeight,
-    kSensorElementPtr, kSensorElementIndex, kSensorElementWeight
+    kSensorElementPtr, kSensorElementIndex, kSensorElementWeight,
+    // weighted velocity source: one CSR over u_source_index, element signals per component
+    kVelocitySourceElementPtr, kVelocitySourceElementIndex, kVelocitySourceElementWeight,
+    kVelocityXSourceElementInput, kVelocityYSourceElementInput, kVelocityZSourceElementInput
   };
 
   MatrixContainer() = default;

@@ -41,8 +41,14 @@ MatrixName kPressureSourceElementInputName = "p_source_element_input", kPressure
            kPressureSourceElementWeightName = "p_source_element_weight";
 MatrixName kSensorElementPtrName = "sensor_element_ptr", kSensorElementIndexName = "sensor_element_index",
            kSensorElementWeightName = "sensor_element_weight";
+// weighted velocity source: one point-major CSR over u_source_index for all components, one signal set per component
+MatrixName kVelocitySourceElementPtrName = "u_source_element_ptr", kVelocitySourceElementIndexName = "u_source_element_index",
+           kVelocitySourceElementWeightName = "u_source_element_weight";
+MatrixName kVelocityXSourceElementInputName = "ux_source_element_input",
+           kVelocityYSourceElementInputName = "uy_source_element_input",
+           kVelocityZSourceElementInputName = "uz_source_element_input";
 // output / state names
-MatrixName kPElementsName = "p_elements";
+MatrixName kPElementsName = "p_elements", kElementsSuffix = "_elements"; // ux_elements ..., ux_non_staggered_elements ...
 MatrixName kPName = "p", kPRmsName = "p_rms", kPMaxName = "p_max", kPMinName = "p_min", kPMaxAllName = "p_max_all",
            kPMinAllName = "p_min_all", kPressureFinalName = "p_final";
 MatrixName kUxName = "ux", kUyName = "uy", kUzName = "uz";

@@ -467,6 +467,47 @@ void ElementOutputStream::flushRaw()
   mFlushedSteps++;
 }
 
+// ---- VelocityElementOutputStream ------------------------------------------------------------------------------------
+VelocityElementOutputStream::VelocityElementOutputStream(const std::string& name, const RealMatrix& source,
+                                                         const IndexMatrix& ptr, const IndexMatrix& index,
+                                                         const RealMatrix& weight, VelocityElementOutputStream* leader)
+  : ElementOutputStream(name, source, ptr, index, weight), mLeader(leader)
+{
+  (leader ? leader : this)->mGroup.push_back(this);
+}
+void VelocityElementOutputStream::create()
+{
+  mSize = mPtr.size() - 1;
+  allocateMemory();
+  // the group is complete by now (the container is set up before the input is read): partials for every field of it
+  if (mLeader == nullptr)
+    mCsr.upload(mPtr.getHostData(), mSize, mIndex.getHostData(), mWeight.getHostData(), mIndex.size(), true, mGroup.size());
+}
+void VelocityElementOutputStream::sample()
+{
+  if (mLeader != nullptr) return; // sampled with its leader, earlier in this pass over the container
+  const uint32_t nFields = static_cast<uint32_t>(mGroup.size());
+  float*       outs[3]   = {nullptr, nullptr, nullptr};
+  const float* fields[3] = {nullptr, nullptr, nullptr};
+  for (uint32_t f = 0; f < nFields; f++)
+  {
+    // the group moves in step: a follower sampled or restored apart from its leader would get its row in the wrong buffer
+    if (mGroup[f]->mSampledSteps != mSampledSteps)
+      throw std::logic_error("stream " + mGroup[f]->mName + " has " + std::to_string(mGroup[f]->mSampledSteps) +
+                             " sampled steps, its leader " + mName + " has " + std::to_string(mSampledSteps));
+    outs[f]   = mGroup[f]->mDeviceRaw[mGroup[f]->mSampledSteps & 1];
+    fields[f] = mGroup[f]->mSourceMatrix.getDeviceData();
+  }
+  kwCheck(kw_sample_elements_multi(ctx(), nFields, outs, fields, mCsr.ptr(), mCsr.entries(), static_cast<uint32_t>(mSize),
+                                   mCsr.nnz(), mCsr.chunkPtr(), mCsr.chunks(), mCsr.partials()));
+  for (VelocityElementOutputStream* s : mGroup)
+  {
+    const int b = s->mSampledSteps & 1;
+    rawSampleTail(ctx(), s->mDeviceRaw[b], s->mPinned[b], s->mEvent[b], s->mSize);
+    s->mSampledSteps++;
+  }
+}
+
 // ---- WholeDomainOutputStream ----------------------------------------------------------------------------------------
 void WholeDomainOutputStream::create()
 {
@@ -604,6 +645,26 @@ void OutputStreamContainer::init(MatrixContainer& mc)
                                                                 mc.getMatrix<IndexMatrix>(MI::kSensorElementPtr),
                                                                 mc.getMatrix<IndexMatrix>(MI::kSensorElementIndex),
                                                                 mc.getMatrix<RealMatrix>(MI::kSensorElementWeight));
+  // --u_elements / --u_non_staggered_elements: the x stream leads its group, y and (3-D) z follow (enum order = sampling order)
+  auto velocityElements = [&](const std::string& infix, const MI (&fields)[3], const OI (&ids)[3]) {
+    const std::string names[3] = {kUxName, kUyName, kUzName};
+    VelocityElementOutputStream* leader = nullptr;
+    for (int a = 0; a < (is3D ? 3 : 2); a++)
+    {
+      auto* s = new VelocityElementOutputStream(names[a] + infix + kElementsSuffix, mc.getMatrix<RealMatrix>(fields[a]),
+                                                mc.getMatrix<IndexMatrix>(MI::kSensorElementPtr),
+                                                mc.getMatrix<IndexMatrix>(MI::kSensorElementIndex),
+                                                mc.getMatrix<RealMatrix>(MI::kSensorElementWeight), leader);
+      if (leader == nullptr) leader = s;
+      mContainer[ids[a]] = s;
+    }
+  };
+  if (params.getStoreVelocityElementsFlag())
+    velocityElements("", {MI::kUxSgx, MI::kUySgy, MI::kUzSgz},
+                     {OI::kVelocityXElements, OI::kVelocityYElements, OI::kVelocityZElements});
+  if (params.getStoreVelocityNonStaggeredElementsFlag())
+    velocityElements("_non_staggered", {MI::kUxShifted, MI::kUyShifted, MI::kUzShifted},
+                     {OI::kVelocityXNonStaggeredElements, OI::kVelocityYNonStaggeredElements, OI::kVelocityZNonStaggeredElements});
   if (params.getStoreVelocityMaxAllFlag())
   {
     mContainer[OI::kVelocityXMaxAll] = new WholeDomainOutputStream(kUxName + "_max_all", mc.getMatrix<RealMatrix>(MI::kUxSgx), RO::kMax);

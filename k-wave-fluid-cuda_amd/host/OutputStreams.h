@@ -227,11 +227,28 @@ class ElementOutputStream : public BaseOutputStream
   void create() override;
   void sample() override;
   void flushRaw() override;
- private:
+ protected:
   const IndexMatrix& mPtr;
   const IndexMatrix& mIndex;
   const RealMatrix&  mWeight;
   ElementCsr         mCsr;
+};
+
+/// --u_elements / --u_non_staggered_elements: the velocity components over the same weighted sensor.  The stream of the
+/// x component leads: it holds the CSR and, each step, reduces its own field and those of its followers (y, z) with one
+/// kw_sample_elements_multi call, each into that stream's own staging buffer; every component then is an ordinary raw
+/// series of its own name (output file, checkpoint, stream_read).  A follower's sample() has nothing left to do.
+class VelocityElementOutputStream : public ElementOutputStream
+{
+ public:
+  /// leader == nullptr: this stream leads; else it is sampled by `leader` (created before it, sampled before it)
+  VelocityElementOutputStream(const std::string& name, const RealMatrix& source, const IndexMatrix& ptr,
+                              const IndexMatrix& index, const RealMatrix& weight, VelocityElementOutputStream* leader);
+  void create() override;
+  void sample() override;
+ private:
+  VelocityElementOutputStream*              mLeader;
+  std::vector<VelocityElementOutputStream*> mGroup; // leader: itself and its followers, in component order
 };
 
 class WholeDomainOutputStream : public BaseOutputStream
@@ -258,7 +275,9 @@ class OutputStreamContainer
     kIntensityXAvgC, kIntensityYAvgC, kIntensityZAvgC,
     kIntensityXAvg, kIntensityYAvg, kIntensityZAvg, kQTerm, kQTermC,
     kVelocityXC, kVelocityYC, kVelocityZC,
-    kPressureElements
+    kPressureElements,
+    kVelocityXElements, kVelocityYElements, kVelocityZElements,
+    kVelocityXNonStaggeredElements, kVelocityYNonStaggeredElements, kVelocityZNonStaggeredElements
   };
   ~OutputStreamContainer() { freeStreams(); }
   void init(MatrixContainer& matrixContainer); // OutputStreamContainer.cpp:70-325

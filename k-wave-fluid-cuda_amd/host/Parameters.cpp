@@ -135,7 +135,11 @@ void Parameters::init(const InputProvider& in, const Options& options)
   };
   if ((mVelocityXSourceFlag > 0) || (mVelocityYSourceFlag > 0) || (mVelocityZSourceFlag > 0))
   {
-    in.readScalarValue(kVelocitySourceManyName, mVelocitySourceMany);
+    // weighted (readElementArrays checks that every active component then is): one row per step and component
+    if (in.datasetExists(kVelocityXSourceElementInputName) || in.datasetExists(kVelocityYSourceElementInputName) ||
+        in.datasetExists(kVelocityZSourceElementInputName))
+      mVelocitySourceMany = 1;
+    else in.readScalarValue(kVelocitySourceManyName, mVelocitySourceMany);
     size_t m = 0;
     in.readScalarValue(kVelocitySourceModeName, m);
     mVelocitySourceMode = toMode(m, "velocity");
@@ -216,11 +220,12 @@ void Parameters::init(const InputProvider& in, const Options& options)
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Weighted transducer arrays: the CSR datasets are checked here, before anything is allocated on the device, because a
-// bad offset or column would be an out-of-bounds gather in kw_element_source_row / kw_sample_elements.  The device holds
+// bad offset or column would be an out-of-bounds gather in kw_element_source_row(s) / kw_sample_elements(_multi).  The device holds
 // offsets and columns as 32-bit values (kw_csr_entry), which bounds the entry count and, for the sensor, the grid.
 void Parameters::readElementArrays(const InputProvider& in)
 {
   mPressureSourceElementCount = mPressureSourceElementNnz = 0;
+  mVelocitySourceElementCount = mVelocitySourceElementNnz = 0;
   mSensorElementCount = mSensorElementNnz = 0;
   const size_t gridPoints = mFullDimensionSizes.nElements();
   constexpr size_t kMax32 = 0xFFFFFFFFull;
@@ -253,34 +258,83 @@ void Parameters::readElementArrays(const InputProvider& in)
     return nnz;
   };
 
+  // a weighted source's element signals: not beside the plain series, many = 1 if given, (1, flag, E) with E >= 1
+  auto checkElementInput = [&](const std::string& elementName, const std::string& plainName, const std::string& manyName,
+                               size_t flag, const std::string& flagName) {
+    if (in.datasetExists(plainName))
+      throw std::invalid_argument(plainName + " and " + elementName + " cannot both be present");
+    if (in.datasetExists(manyName))
+    {
+      size_t many = 0;
+      in.readScalarValue(manyName, many);
+      if (many != 1) throw std::invalid_argument(manyName + ": must be 1 with " + elementName);
+    }
+    const DimensionSizes dims = in.getDatasetDimensionSizes(elementName); // (E, Nt_src, 1)
+    const size_t elements = dims.nx;
+    if (elements == 0 || dims.nElements() != elements * flag)
+      throw std::invalid_argument(elementName + ": expected (1, " + flagName + " = " + std::to_string(flag) + ", E) with E >= 1");
+    return elements;
+  };
+
   const bool sourceWeighted = in.datasetExists(kPressureSourceElementInputName);
   if (sourceWeighted && mPressureSourceFlag == 0)
     throw std::invalid_argument(kPressureSourceElementInputName + ": present, but p_source_flag is 0");
   if (sourceWeighted)
   {
-    if (in.datasetExists(kPressureSourceInputName))
-      throw std::invalid_argument("p_source_input and " + kPressureSourceElementInputName + " cannot both be present");
-    if (in.datasetExists(kPressureSourceManyName))
-    {
-      size_t many = 0;
-      in.readScalarValue(kPressureSourceManyName, many);
-      if (many != 1) throw std::invalid_argument(kPressureSourceManyName + ": must be 1 with " + kPressureSourceElementInputName);
-    }
-    const DimensionSizes dims = in.getDatasetDimensionSizes(kPressureSourceElementInputName); // (E, Nt_src, 1)
-    const size_t elements = dims.nx;
-    if (elements == 0 || dims.nElements() != elements * mPressureSourceFlag)
-      throw std::invalid_argument(kPressureSourceElementInputName + ": expected (1, p_source_flag = " +
-                                  std::to_string(mPressureSourceFlag) + ", E) with E >= 1");
+    const size_t elements = checkElementInput(kPressureSourceElementInputName, kPressureSourceInputName, kPressureSourceManyName,
+                                              mPressureSourceFlag, kPressureSourceFlagName);
     if (mPressureSourceIndexSize > kMax32) throw std::invalid_argument(kPressureSourceIndexName + ": more than 2^32 - 1 points");
     mPressureSourceElementNnz = checkCsr(kPressureSourceElementPtrName, mPressureSourceIndexSize, kPressureSourceElementIndexName,
                                          kPressureSourceElementWeightName, elements, "weighted pressure source");
     mPressureSourceElementCount = elements;
   }
-  if (mOptions.storePressureElements)
+
+  // velocity: the components share u_source_index and so one CSR; a component is active when its flag is above 0, and
+  // the active ones are all weighted or all plain
+  struct Component { const std::string& elementName; const std::string& plainName; const std::string& flagName; size_t flag; };
+  const Component comps[3] = {
+    {kVelocityXSourceElementInputName, kVelocityXSourceInputName, kVelocityXSourceFlagName, mVelocityXSourceFlag},
+    {kVelocityYSourceElementInputName, kVelocityYSourceInputName, kVelocityYSourceFlagName, mVelocityYSourceFlag},
+    {kVelocityZSourceElementInputName, kVelocityZSourceInputName, kVelocityZSourceFlagName, mVelocityZSourceFlag}};
+  const Component* firstWeighted = nullptr;
+  const Component* firstPlain    = nullptr;
+  size_t velocityElements = 0;
+  for (const Component& c : comps)
   {
+    const bool present = in.datasetExists(c.elementName);
+    if (present && c.flag == 0) throw std::invalid_argument(c.elementName + ": present, but " + c.flagName + " is 0");
+    if (c.flag == 0) continue;
+    if (!present)
+    {
+      if (firstPlain == nullptr) firstPlain = &c;
+      continue;
+    }
+    const size_t elements = checkElementInput(c.elementName, c.plainName, kVelocitySourceManyName, c.flag, c.flagName);
+    if (firstWeighted != nullptr && elements != velocityElements)
+      throw std::invalid_argument(c.elementName + ": has " + std::to_string(elements) + " elements, but " +
+                                  firstWeighted->elementName + " has " + std::to_string(velocityElements));
+    if (firstWeighted == nullptr) firstWeighted = &c;
+    velocityElements = elements;
+  }
+  if (firstWeighted != nullptr)
+  {
+    if (firstPlain != nullptr)
+      throw std::invalid_argument(firstPlain->elementName + ": missing, although " + firstPlain->flagName + " is above 0 and " +
+                                  firstWeighted->elementName + " is present (active velocity components are all weighted or all plain)");
+    if (mTransducerSourceFlag != 0)
+      throw std::invalid_argument(firstWeighted->elementName + ": a weighted velocity source cannot be combined with " +
+                                  kTransducerSourceFlagName);
+    if (mVelocitySourceIndexSize > kMax32) throw std::invalid_argument(kVelocitySourceIndexName + ": more than 2^32 - 1 points");
+    mVelocitySourceElementNnz = checkCsr(kVelocitySourceElementPtrName, mVelocitySourceIndexSize, kVelocitySourceElementIndexName,
+                                         kVelocitySourceElementWeightName, velocityElements, "weighted velocity source");
+    mVelocitySourceElementCount = velocityElements;
+  }
+  if (getStoreAnyElementsFlag())
+  {
+    const char* flag = mOptions.storePressureElements ? "--p_elements" : mOptions.storeVelocityElements ? "--u_elements" : "--u_non_staggered_elements";
     if (!in.datasetExists(kSensorElementPtrName) || !in.datasetExists(kSensorElementIndexName) ||
         !in.datasetExists(kSensorElementWeightName))
-      throw std::invalid_argument("--p_elements needs the datasets " + kSensorElementPtrName + ", " + kSensorElementIndexName +
+      throw std::invalid_argument(std::string(flag) + " needs the datasets " + kSensorElementPtrName + ", " + kSensorElementIndexName +
                                   " and " + kSensorElementWeightName);
     if (gridPoints > kMax32)
       throw std::invalid_argument(kSensorElementIndexName + ": the weighted sensor needs a grid of fewer than 2^32 points");

@@ -58,6 +58,8 @@ class Parameters
     bool   storeIntensityAvg = false, storeQTerm = false, storeQTermC = false; // --I_avg, --Q_term, --Q_term_c
     bool   storeVelocityC = false; // --u_c
     bool   storePressureElements = false; // --p_elements: weighted sensor (sensor_element_*), one series per element
+    bool   storeVelocityElements = false;             // --u_elements: ux/uy/uz_elements over the same sensor_element_*
+    bool   storeVelocityNonStaggeredElements = false; // --u_non_staggered_elements: the same of the shifted velocities
     bool   complex40bit = false;       // --40-bit_complex
     bool   onlyPostProcessing = false; // --post: post-processing of an existing output file, no time loop
     float  frequency = 0.0f;       // --frequency [Hz], alternative to --period
@@ -209,7 +211,13 @@ class Parameters
   bool   getPressureSourceElementFlag() const { return mPressureSourceElementCount != 0; }
   size_t getPressureSourceElementCount() const { return mPressureSourceElementCount; }
   size_t getPressureSourceElementNnz() const { return mPressureSourceElementNnz; }
-  /// weighted sensor (--p_elements): E rows of sensor_element_* over the grid
+  /// weighted velocity source (u?_source_element_input present for every active component): the u_source_index points
+  /// get v_c(t) = W s_c(t) from E element signals per component, all components through one CSR (u_source_element_*);
+  /// the series seen by the source kernels is one row of Npts values per component (u_source_many is 1)
+  bool   getVelocitySourceElementFlag() const { return mVelocitySourceElementCount != 0; }
+  size_t getVelocitySourceElementCount() const { return mVelocitySourceElementCount; }
+  size_t getVelocitySourceElementNnz() const { return mVelocitySourceElementNnz; }
+  /// weighted sensor (--p_elements, --u_elements, --u_non_staggered_elements): E rows of sensor_element_* over the grid
   size_t getSensorElementCount() const { return mSensorElementCount; }
   size_t getSensorElementNnz() const { return mSensorElementNnz; }
   size_t     getVelocitySourceMany() const { return mVelocitySourceMany; }
@@ -243,6 +251,12 @@ class Parameters
   bool getStoreQTermCFlag() const { return mOptions.storeQTermC; }
   bool getStoreVelocityCFlag() const { return mOptions.storeVelocityC; }
   bool getStorePressureElementsFlag() const { return mOptions.storePressureElements; }
+  bool getStoreVelocityElementsFlag() const { return mOptions.storeVelocityElements; }
+  bool getStoreVelocityNonStaggeredElementsFlag() const { return mOptions.storeVelocityNonStaggeredElements; }
+  bool getStoreAnyElementsFlag() const
+  {
+    return mOptions.storePressureElements || mOptions.storeVelocityElements || mOptions.storeVelocityNonStaggeredElements;
+  }
   bool getOnlyPostProcessingFlag() const { return mOptions.onlyPostProcessing; }
   bool get40bitCompressionFlag() const { return mOptions.complex40bit; }
   bool getNoCompressionOverlapFlag() const { return mOptions.noCompressionOverlap; }
@@ -253,7 +267,8 @@ class Parameters
   bool needsShiftedVelocity() const
   {
     return mOptions.storeVelocityNonStaggeredRaw || mOptions.storeVelocityNonStaggeredC || mOptions.storeIntensityAvgC ||
-           mOptions.storeIntensityAvg || mOptions.storeQTerm || mOptions.storeQTermC;
+           mOptions.storeIntensityAvg || mOptions.storeQTerm || mOptions.storeQTermC ||
+           mOptions.storeVelocityNonStaggeredElements;
   }
 
  private:
@@ -287,6 +302,7 @@ class Parameters
   SensorMaskType mSensorMaskType = SensorMaskType::kIndex;
   size_t mSensorMaskIndexSize = 0, mSensorMaskCornersSize = 0;
   size_t mPressureSourceElementCount = 0, mPressureSourceElementNnz = 0;
+  size_t mVelocitySourceElementCount = 0, mVelocitySourceElementNnz = 0;
   size_t mSensorElementCount = 0, mSensorElementNnz = 0;
   void   readElementArrays(const InputProvider& in);
 };

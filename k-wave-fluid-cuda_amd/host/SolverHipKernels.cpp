@@ -36,10 +36,10 @@ void addTransducerSource(const MatrixContainer& c)
                                    (const uint64_t*)c.getMatrix<IndexMatrix>(MI::kDelayMask).getDeviceData(),
                                    Parameters::getInstance().getTimeIndex()));
 }
-void addVelocitySource(RealMatrix& velocity, const RealMatrix& input, const IndexMatrix& index)
+void addVelocitySource(RealMatrix& velocity, const RealMatrix& input, const IndexMatrix& index, size_t seriesRow)
 {
   kwCheck(kw_add_velocity_source(ctx(), velocity.getDeviceData(), input.getDeviceData(),
-                                 (const uint64_t*)index.getDeviceData(), Parameters::getInstance().getTimeIndex()));
+                                 (const uint64_t*)index.getDeviceData(), seriesRow));
 }
 template<SD sd> void addPressureSource(const MatrixContainer& c, size_t seriesRow)
 {

@@ -17,7 +17,9 @@ int getHipCodeVersion();
 template<SD simulationDimension = SD::k3D> void computeVelocityHeterogeneous(const MatrixContainer& container);
 template<SD simulationDimension = SD::k3D> void computeVelocityHomogeneousUniform(const MatrixContainer& container);
 void addTransducerSource(const MatrixContainer& container);
-void addVelocitySource(RealMatrix& velocity, const RealMatrix& velocitySourceInput, const IndexMatrix& velocitySourceIndex);
+/// seriesRow: row of u?_source_input to read (the time index; 0 for the one-row buffer of a weighted source)
+void addVelocitySource(RealMatrix& velocity, const RealMatrix& velocitySourceInput, const IndexMatrix& velocitySourceIndex,
+                       size_t seriesRow);
 /// seriesRow: row of p_source_input to read (the time index; 0 for the one-row buffer of a weighted source)
 template<SD simulationDimension = SD::k3D> void addPressureSource(const MatrixContainer& container, size_t seriesRow);
 void insertSourceIntoScalingMatrix(RealMatrix& scaledSource, const RealMatrix& sourceInput,

@@ -24,6 +24,7 @@ static void usage()
   std::printf("kspaceFirstOrder-HIP -i <input.h5> -o <output.h5> [-g dev] [-s start (1-based)] [--benchmark N]\n"
               "  [-p|--p_raw] [--p_rms] [--p_max] [--p_min] [--p_max_all] [--p_min_all] [--p_final] [--p_elements]\n"
               "  [-u|--u_raw] [--u_rms] [--u_max] [--u_min] [--u_max_all] [--u_min_all] [--u_final] [--u_non_staggered_raw]\n"
+              "  [--u_elements] [--u_non_staggered_elements]\n"
               "  [--p_c] [--u_c] [--u_non_staggered_c] [--I_avg_c] [--I_avg] [--Q_term] [--Q_term_c]\n"
               "  [--period P | --frequency F] [--mos M] [--harmonics H] [--no_overlap] [--granular]\n"
               "  [-c <deflate 0..9>] [--copy_sensor_mask]\n"
@@ -96,6 +97,8 @@ int main(int argc, char** argv)
     else if (a == "--p_min_all") o.p_min_all = 1;
     else if (a == "--p_final") o.p_final = 1;
     else if (a == "--p_elements") o.p_elements = 1;
+    else if (a == "--u_elements") o.u_elements = 1;
+    else if (a == "--u_non_staggered_elements") o.u_non_staggered_elements = 1;
     else if (a == "-u" || a == "--u_raw") o.u_raw = 1;
     else if (a == "--u_rms") o.u_rms = 1;
     else if (a == "--u_max") o.u_max = 1;
@@ -132,7 +135,7 @@ int main(int argc, char** argv)
   if (in.empty() || out.empty()) { usage(); return EXIT_FAILURE; }
   if (o.only_post_processing)
   { // CommandLineParameters.cpp:919-936: --post goes with the post-processed quantities only
-    const bool other = o.p_elements || o.p_raw || o.p_rms || o.p_max || o.p_min || o.p_max_all || o.p_min_all || o.p_final || o.u_raw || o.u_rms ||
+    const bool other = o.p_elements || o.u_elements || o.u_non_staggered_elements || o.p_raw || o.p_rms || o.p_max || o.p_min || o.p_max_all || o.p_min_all || o.p_final || o.u_raw || o.u_rms ||
                        o.u_max || o.u_min || o.u_max_all || o.u_min_all || o.u_final || o.u_non_staggered_raw || o.p_c || o.u_c ||
                        o.u_non_staggered_c || !ckpt.empty();
     if (other || !(o.i_avg || o.i_avg_c || o.q_term || o.q_term_c))

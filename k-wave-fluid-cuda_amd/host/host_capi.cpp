@@ -54,6 +54,8 @@ Parameters::Options kwh_convert_options(const kwh_options* o)
   opt.p2pEmulateLinkGbs   = o->p2p_emulate_link_gbs;
   opt.p2pEmulateLatencyUs = o->p2p_emulate_latency_us;
   opt.storePressureElements = o->p_elements != 0;
+  opt.storeVelocityElements = o->u_elements != 0;
+  opt.storeVelocityNonStaggeredElements = o->u_non_staggered_elements != 0;
   return opt;
 }
 

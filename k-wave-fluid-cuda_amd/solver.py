@@ -45,7 +45,8 @@ class Options(C.Structure):
                 ("complex_40bit", C.c_int32), ("reserved_", C.c_int32), ("exchange_piece_fn", C.c_void_p),
                 ("tuning", C.c_void_p), ("step_graph", C.c_int32), ("comm_p2p", C.c_int32),
                 ("comm_allgather_fn", C.c_void_p), ("comm_allgather_user", C.c_void_p), ("rccl_library", C.c_char_p),
-                ("p2p_emulate_link_gbs", C.c_float), ("p2p_emulate_latency_us", C.c_float), ("p_elements", C.c_int32)]
+                ("p2p_emulate_link_gbs", C.c_float), ("p2p_emulate_latency_us", C.c_float), ("p_elements", C.c_int32),
+                ("u_elements", C.c_int32), ("u_non_staggered_elements", C.c_int32)]
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)  # kwh_allgather_fn
 
