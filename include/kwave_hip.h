@@ -130,6 +130,8 @@ typedef struct kw_tuning
   int32_t  plane_kernels;       /* 1: grids with square planes of 32 / 64 points run each stage's tail (y-inverse,
                                    x-inverse + epilogue, chained x / y forward) as ONE launch whose blocks take whole
                                    z-planes; 0: the three-launch form of the larger grids */
+  uint64_t offgrid_scratch_bytes; /* kw_offgrid_build: device bytes the element boxes of one round may take when the call
+                                   itself names none (20 bytes per box cell; default, and what 0 selects: 256 MiB) */
 } kw_tuning;
 KW_API kw_status   kw_get_tuning(kw_ctx* ctx, kw_tuning* out);
 KW_API kw_status   kw_set_tuning(kw_ctx* ctx, const kw_tuning* tuning);
@@ -606,6 +608,45 @@ KW_API kw_status kw_element_source_rows(kw_ctx* ctx, float* const rows[3], const
 KW_API kw_status kw_sample_elements_multi(kw_ctx* ctx, uint32_t n_fields, float* const outs[], const float* const fields[],
                                           const uint32_t* ptr, const kw_csr_entry* entries, uint32_t n_elements,
                                           uint64_t nnz, const uint32_t* chunk_ptr, uint32_t n_chunks, float* partials);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Off-grid elements (new with this build): the weights of the arrays above from the elements' geometry — what k-Wave's
+ * kWaveArray computes with getArrayGridWeights / offGridPoints.  An element is a set of integration points on its
+ * surface; its weights are the band-limited interpolant (BLI) of those points, a truncated sinc stencil per point.
+ *   Grid      nx x ny x nz points (a 2-D grid has nz == 1).
+ *   Point     three coordinates in grid units, u = x / d + floor(N / 2) per axis (k-Wave's kgrid.x_vec), float64.  The
+ *             call splits u, in float64, into the nearest index n = floor(u + 0.5) and the offset f = u - n in
+ *             [-0.5, 0.5); f goes to the device as fp32.  A point whose n is outside 0 .. N - 1 is an error.
+ *   Stencil   R = ceil(1 / (pi * bli_tolerance)) (0.05 gives 7; at most 64).  Point p of element e adds, to every grid
+ *             point (n_x + d_x, n_y + d_y, n_z + d_z) with |d| <= R per axis that lies inside the grid,
+ *               c = ((scale[e] * s(d_x, f_x)) * s(d_y, f_y)) * s(d_z, f_z),   s(d, f) = sinc(d - f),
+ *             evaluated in fp32 as (-1)^d sin(pi f) / (pi (f - d)), 1 at f - d == 0 (exactly 0 off the point's own index
+ *             when f == 0); on an axis of one point the factor is 1 and d = 0.  No entry is thresholded: the only
+ *             truncation is the box of radius R, clipped at the grid's faces.
+ *   Element   W[e][g] = sum over its points of c.  Each c is rounded to a multiple of 2^-40 and added with 64-bit integer
+ *             atomics into the element's zeroed bounding box, so the sum is exact and the CSR is the same bits on every
+ *             run and under any permutation of an element's points; it is rounded to fp32 once.  A cell is an entry iff
+ *             its sum is not zero.  An element with |scale[e]| * (its point count) >= 2^22 is refused (KW_ERR_INVALID).
+ *   Rounds    as many elements (in order) as fit `scratch_bytes` at 20 bytes per cell of their bounding boxes (the
+ *             points' n, dilated by R and clipped; padded to 256 cells) share one round: a memset, four launches and one
+ *             host round trip (two synchronisations: the entry count, then the entries).  scratch_bytes == 0: kw_tuning::offgrid_scratch_bytes.  An element whose box alone does
+ *             not fit is refused with KW_ERR_ALLOC; kw_last_error names the element and the bytes it needs.
+ * coords holds 3 * P doubles (x, y, z of point 0, then point 1, ...), point_ptr the n_elements + 1 offsets of the
+ * elements' points (point_ptr[0] == 0, P = point_ptr[n_elements]), scale one factor per element; all host arrays, not
+ * written; at most 2^32 points in one build.  Errors in them are KW_ERR_INVALID with the element and the point (counted within the element) named.
+ * The result is a host-side CSR over the elements: row e holds element e's grid points, 0-based linear indices with x
+ * fastest, strictly ascending, and their weights.  Elements without points give empty rows; n_elements == 0 an empty CSR.
+ * The call allocates and frees its own device memory and synchronises the context's stream.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct kw_offgrid kw_offgrid;
+KW_API kw_status kw_offgrid_build(kw_ctx* ctx, const double* coords, const uint64_t* point_ptr, const float* scale,
+                                  uint64_t n_elements, uint32_t nx, uint32_t ny, uint32_t nz, double bli_tolerance,
+                                  uint64_t scratch_bytes, kw_offgrid** out);
+/* the CSR of a build: its sizes, the n_elements + 1 row offsets, and copies of the entries (either may be NULL) */
+KW_API kw_status kw_offgrid_size(kw_ctx* ctx, const kw_offgrid* h, uint64_t* out_n_elements, uint64_t* out_nnz);
+KW_API kw_status kw_offgrid_ptr(kw_ctx* ctx, const kw_offgrid* h, uint64_t* out_ptr);
+KW_API kw_status kw_offgrid_entries(kw_ctx* ctx, const kw_offgrid* h, uint64_t* out_index, float* out_weight);
+KW_API kw_status kw_offgrid_free(kw_ctx* ctx, kw_offgrid* h);
 
 #ifdef __cplusplus
 }

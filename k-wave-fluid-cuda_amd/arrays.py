@@ -13,15 +13,183 @@ The solver takes the array in this weighted form (include/kwave_host.h):
 Elements are given as `[(flat grid indices, weights), ...]`, one pair per element, with 0-based linear grid indices in
 the x-fastest order of `sensor_mask_index` (`np.ravel` of a `[nz][ny][nx]` array).  Weights are used as given: any
 element-area normalisation belongs in them.
+
+`offgrid_elements` builds those pairs from geometry, on the GPU (kw_offgrid_build): an element is a set of integration
+points on its surface, its weights their band-limited interpolant.  `line_element`, `rect_element`, `disc_element` and
+`bowl_element` place the points of the usual shapes; any (P, 3) array of points in metres serves as well.
 """
 from __future__ import annotations
 
-from typing import Dict, Sequence, Tuple
+import math
+from typing import Dict, List, NamedTuple, Sequence, Tuple
 
 import numpy as np
 
 U64 = np.uint64
 Element = Tuple[Sequence[int], Sequence[float]]
+Shape = Tuple[np.ndarray, float, int]     # (points (P, 3) float64 in metres, measure in m^dim, dim)
+GOLDEN_ANGLE = math.pi * (3.0 - math.sqrt(5.0))
+
+
+class Grid(NamedTuple):
+    """The grid an array sits on.  Point i of an axis of N points lies at (i - N // 2) * d (k-Wave's kgrid.x_vec); a 2-D
+    grid has nz == 1."""
+    nx: int
+    ny: int
+    nz: int
+    dx: float
+    dy: float
+    dz: float
+
+
+# ---- element shapes: integration points, pure NumPy in float64 ---------------------------------------------------------------
+def _vec3(v, what: str) -> np.ndarray:
+    v = np.asarray(v, dtype=np.float64).reshape(-1)
+    if v.size == 2:
+        v = np.append(v, 0.0)
+    if v.size != 3 or not np.all(np.isfinite(v)):
+        raise ValueError(f"{what} must be 2 or 3 finite coordinates, got {v}")
+    return v
+
+
+def _spacing(grid: Grid) -> float:
+    """the one spacing the shape helpers count their points by"""
+    if grid.dx != grid.dy or (grid.nz > 1 and grid.dz != grid.dx):
+        raise ValueError("the shape helpers need dx == dy == dz; pass your own points on other grids")
+    return float(grid.dx)
+
+
+def _count(measure: float, d: float, dim: int, upsampling: float) -> int:
+    if not (measure > 0.0 and math.isfinite(measure)):
+        raise ValueError(f"an element needs a positive size, got a measure of {measure}")
+    return int(math.ceil(upsampling * measure / d ** dim))
+
+
+def _plane_basis(normal: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """unit vectors (e1, e2, n) with e1 x e2 = n: e1 is the coordinate axis least aligned with n, made normal to it"""
+    length = np.linalg.norm(normal)
+    if not length > 0.0:
+        raise ValueError("the normal / axis of an element must not be zero")
+    n = normal / length
+    e1 = np.zeros(3)
+    e1[int(np.argmin(np.abs(n)))] = 1.0
+    e1 -= n * (e1 @ n)
+    e1 /= np.linalg.norm(e1)
+    return e1, np.cross(n, e1), n
+
+
+def _rotation(rotation) -> np.ndarray:
+    r = np.asarray(rotation, dtype=np.float64)
+    if r.ndim == 0:                                        # an angle in radians about z
+        c, s = math.cos(float(r)), math.sin(float(r))
+        return np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
+    if r.shape != (3, 3) or not np.allclose(r @ r.T, np.eye(3), atol=1e-12):
+        raise ValueError("rotation is an angle about z in radians or a 3 x 3 rotation matrix")
+    return r
+
+
+def line_element(grid: Grid, a, b, upsampling: float = 10.0) -> Shape:
+    """The segment from a to b: the midpoints of P = ceil(upsampling * |b - a| / dx) equal pieces; measure |b - a|, dim 1."""
+    a, b = _vec3(a, "a"), _vec3(b, "b")
+    length = float(np.linalg.norm(b - a))
+    p = _count(length, _spacing(grid), 1, upsampling)
+    t = (np.arange(p) + 0.5) / p
+    return a + t[:, None] * (b - a), length, 1
+
+
+def rect_element(grid: Grid, centre, Lx: float, Ly: float, rotation=0.0, upsampling: float = 10.0) -> Shape:
+    """The Lx x Ly rectangle about `centre`, in the xy-plane turned by `rotation` (an angle about z in radians, or a 3 x 3
+    rotation matrix): the centres of an n_x x n_y lattice of equal cells, n_x = ceil(sqrt(P Lx / Ly)) and
+    n_y = ceil(sqrt(P Ly / Lx)) with P = ceil(upsampling * Lx Ly / dx^2), so n_x n_y >= P; measure Lx Ly, dim 2."""
+    centre, rot = _vec3(centre, "centre"), _rotation(rotation)
+    area = float(Lx) * float(Ly)
+    p = _count(area, _spacing(grid), 2, upsampling)
+    n_x = max(1, int(math.ceil(math.sqrt(p * Lx / Ly))))
+    n_y = max(1, int(math.ceil(math.sqrt(p * Ly / Lx))))
+    x = ((np.arange(n_x) + 0.5) / n_x - 0.5) * Lx
+    y = ((np.arange(n_y) + 0.5) / n_y - 0.5) * Ly
+    local = np.zeros((n_y, n_x, 3))
+    local[..., 0], local[..., 1] = x[None, :], y[:, None]
+    return centre + local.reshape(-1, 3) @ rot.T, area, 2
+
+
+def disc_element(grid: Grid, centre, radius: float, normal=(0.0, 0.0, 1.0), upsampling: float = 10.0) -> Shape:
+    """The disc of `radius` about `centre` in the plane normal to `normal`: the sunflower set r_k = radius
+    sqrt((k + 1/2) / P), theta_k = k pi (3 - sqrt 5), P = ceil(upsampling * pi radius^2 / dx^2) points of equal area;
+    measure pi radius^2, dim 2."""
+    centre = _vec3(centre, "centre")
+    e1, e2, _ = _plane_basis(_vec3(normal, "normal"))
+    area = math.pi * float(radius) ** 2
+    p = _count(area, _spacing(grid), 2, upsampling)
+    k = np.arange(p)
+    r, theta = radius * np.sqrt((k + 0.5) / p), k * GOLDEN_ANGLE
+    return centre + (r * np.cos(theta))[:, None] * e1 + (r * np.sin(theta))[:, None] * e2, area, 2
+
+
+def bowl_element(grid: Grid, apex, radius_of_curvature: float, diameter: float, focus, upsampling: float = 10.0) -> Shape:
+    """The spherical cap with its rear point at `apex`, opening towards `focus` (which only gives the direction of the
+    axis): radius of curvature Rc, aperture `diameter` <= 2 Rc, height h = Rc - sqrt(Rc^2 - (diameter / 2)^2).  The
+    golden-angle set of the disc with equal steps in the height above the apex, t_k = h (k + 1/2) / P — equal areas on a
+    sphere; measure 2 pi Rc h, dim 2.  3-D grids only."""
+    if grid.nz == 1:
+        raise ValueError("a bowl needs a 3-D grid")
+    apex = _vec3(apex, "apex")
+    e1, e2, axis = _plane_basis(_vec3(focus, "focus") - apex)
+    rc, half = float(radius_of_curvature), 0.5 * float(diameter)
+    if not 0.0 < half <= rc:
+        raise ValueError(f"a bowl needs 0 < diameter <= 2 * radius_of_curvature, got {diameter} and {rc}")
+    h = rc - math.sqrt(rc * rc - half * half)
+    area = 2.0 * math.pi * rc * h
+    p = _count(area, _spacing(grid), 2, upsampling)
+    k = np.arange(p)
+    t, theta = h * (k + 0.5) / p, k * GOLDEN_ANGLE
+    rho = np.sqrt(t * (2.0 * rc - t))                      # distance from the axis at height t: sqrt(Rc^2 - (Rc - t)^2)
+    return apex + t[:, None] * axis + (rho * np.cos(theta))[:, None] * e1 + (rho * np.sin(theta))[:, None] * e2, area, 2
+
+
+def grid_units(grid: Grid, points) -> np.ndarray:
+    """points (P, 3) in metres -> grid units, u = x / d + N // 2 per axis, float64"""
+    pts = np.asarray(points, dtype=np.float64)
+    if pts.ndim != 2 or pts.shape[1] not in (2, 3):
+        raise ValueError(f"points must be (P, 3), got {pts.shape}")
+    if pts.shape[1] == 2:
+        pts = np.concatenate([pts, np.zeros((pts.shape[0], 1))], axis=1)
+    return pts / np.array([grid.dx, grid.dy, grid.dz]) + np.array([grid.nx // 2, grid.ny // 2, grid.nz // 2], dtype=np.float64)
+
+
+def offgrid_elements(device, grid: Grid, elements: Sequence[Shape], bli_tolerance: float = 0.05,
+                     normalise: bool = False, scratch_bytes: int = 0) -> List[Element]:
+    """Elements from geometry, their weights computed on the GPU (capi.offgrid_build): the list weighted_source,
+    weighted_velocity_source and weighted_sensor take.
+
+    device: a capi.Device, or None to open one for the call.  grid: a Grid (or anything with nx .. dz).  elements: one
+    (points (P, 3) float64 in metres, measure, dim) per element, as the shape helpers return.  Each point carries
+    scale = m_grid / P with m_grid = measure / dx^dim, k-Wave's source convention; normalise=True divides by m_grid, which
+    gives the element average that kWaveArray.combineSensorData forms (for sensors)."""
+    from . import capi
+    grid = Grid(*(getattr(grid, n) for n in Grid._fields))
+    coords, counts, scale = [], [], []
+    for e, (pts, measure, dim) in enumerate(elements):
+        u = grid_units(grid, pts) if len(pts) else np.zeros((0, 3))
+        if dim not in (1, 2, 3):
+            raise ValueError(f"element {e}: dim must be 1, 2 or 3, got {dim}")
+        m_grid = float(measure) / grid.dx ** dim
+        coords.append(u)
+        counts.append(u.shape[0])
+        scale.append((1.0 if normalise else m_grid) / u.shape[0] if u.shape[0] else 0.0)
+    point_ptr = np.zeros(len(counts) + 1, dtype=U64)
+    point_ptr[1:] = np.cumsum(counts)
+    coords = np.concatenate(coords) if coords else np.zeros((0, 3))
+    own = device is None
+    dev = capi.Device() if own else device
+    try:
+        ptr, index, weight = capi.offgrid_build(dev, coords, point_ptr, scale, (grid.nx, grid.ny, grid.nz), bli_tolerance,
+                                                scratch_bytes)
+    finally:
+        if own:
+            dev.close()
+    ptr = ptr.astype(np.int64)
+    return [(index[ptr[e]:ptr[e + 1]].astype(np.int64), weight[ptr[e]:ptr[e + 1]]) for e in range(len(counts))]
 
 
 def _check(elements: Sequence[Element]):

@@ -181,6 +181,11 @@ _SIG: Dict[str, list] = {
     "kw_sample_elements": [_P, _P, _P, _P, _P, C.c_uint32, _U64, _P, C.c_uint32, _P],
     "kw_element_source_rows": [_P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _U64],
     "kw_sample_elements_multi": [_P, C.c_uint32, _P, _P, _P, _P, C.c_uint32, _U64, _P, C.c_uint32, _P],
+    "kw_offgrid_build": [_P, _P, _P, _P, _U64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, _U64, C.POINTER(_P)],
+    "kw_offgrid_size": [_P, _P, C.POINTER(_U64), C.POINTER(_U64)],
+    "kw_offgrid_ptr": [_P, _P, _P],
+    "kw_offgrid_entries": [_P, _P, _P, _P],
+    "kw_offgrid_free": [_P, _P],
 }
 
 ELEMENT_CHUNK = 1024  # KW_ELEMENT_CHUNK
@@ -331,6 +336,35 @@ class Device:
             pass
 
 
+def offgrid_build(dev: Device, coords, point_ptr, scale, dims, bli_tolerance: float = 0.05, scratch_bytes: int = 0):
+    """kw_offgrid_build: the CSR of the elements' band-limited-interpolant weights, (ptr, index, weight) as uint64 (E + 1),
+    uint64 (nnz, 0-based linear grid index, x fastest) and float32 (nnz) arrays.  coords: (P, 3) float64 in grid units;
+    point_ptr: E + 1 offsets of the elements' points; scale: one factor per element; dims = (nx, ny, nz).
+    scratch_bytes = 0 takes kw_tuning::offgrid_scratch_bytes."""
+    coords = np.ascontiguousarray(coords, dtype=np.float64).reshape(-1, 3)
+    point_ptr = np.ascontiguousarray(point_ptr, dtype=np.uint64).reshape(-1)
+    scale = np.ascontiguousarray(scale, dtype=np.float32).reshape(-1)
+    if point_ptr.size != scale.size + 1:
+        raise ValueError(f"point_ptr must have {scale.size + 1} entries for {scale.size} elements, got {point_ptr.size}")
+    if point_ptr.size and int(point_ptr.max()) > coords.shape[0]:
+        raise ValueError(f"point_ptr addresses {int(point_ptr.max())} points, coords holds {coords.shape[0]}")
+    h = _P()
+    check(dev.L.kw_offgrid_build(dev.ctx, coords.ctypes.data, point_ptr.ctypes.data, scale.ctypes.data, scale.size,
+                                 int(dims[0]), int(dims[1]), int(dims[2]), float(bli_tolerance), int(scratch_bytes),
+                                 C.byref(h)))
+    try:
+        n_el, nnz = _U64(), _U64()
+        check(dev.L.kw_offgrid_size(dev.ctx, h, C.byref(n_el), C.byref(nnz)))
+        ptr = np.empty(n_el.value + 1, dtype=np.uint64)
+        index = np.empty(nnz.value, dtype=np.uint64)
+        weight = np.empty(nnz.value, dtype=np.float32)
+        check(dev.L.kw_offgrid_ptr(dev.ctx, h, ptr.ctypes.data))
+        check(dev.L.kw_offgrid_entries(dev.ctx, h, index.ctypes.data, weight.ctypes.data))
+    finally:
+        dev.L.kw_offgrid_free(dev.ctx, h)
+    return ptr, index, weight
+
+
 COMM_ID_BYTES = 128
 COMM_P2P_BLOB_BYTES = 1024
 TRANSPORTS = {-1: "none", 0: "rccl", 1: "p2p (not connected)", 2: "p2p", 3: "p2p link model"}
@@ -340,12 +374,13 @@ class Tuning(C.Structure):
     """kw_tuning of include/kwave_hip.h: every schedule parameter of the device library"""
     _fields_ = [("struct_bytes", C.c_uint32), ("side_array", C.c_int32), ("tail_chunks", C.c_int32), ("split512", C.c_int32),
                 ("slab_pipeline", C.c_int32), ("slab_chunks", C.c_int32), ("slab_batch", C.c_int32),
-                ("p2p_blocks_per_peer", C.c_int32), ("p2p_timeout_s", C.c_float), ("plane_kernels", C.c_int32)]
+                ("p2p_blocks_per_peer", C.c_int32), ("p2p_timeout_s", C.c_float), ("plane_kernels", C.c_int32),
+                ("offgrid_scratch_bytes", C.c_uint64)]
 
 
 def default_tuning() -> Tuning:
     """the library's defaults (what a fresh context reports through kw_get_tuning)"""
-    return Tuning(C.sizeof(Tuning), 1, 0, 1, 1, 1, -1, 4, 20.0, 1)
+    return Tuning(C.sizeof(Tuning), 1, 0, 1, 1, 1, -1, 4, 20.0, 1, 256 << 20)
 
 
 def make_tuning(spec=None) -> Tuning:

@@ -209,6 +209,7 @@ kw_status kw_set_tuning(kw_ctx* ctx, const kw_tuning* tuning)
   t.struct_bytes = static_cast<uint32_t>(sizeof(kw_tuning));
   KW_REQUIRE(t.tail_chunks >= 0 && t.slab_chunks >= 1 && t.slab_chunks <= KW_XCHUNKS_MAX && t.slab_batch >= -1 && t.slab_batch <= 1);
   KW_REQUIRE(t.p2p_blocks_per_peer >= 1 && t.p2p_blocks_per_peer <= 8 && t.p2p_timeout_s > 0.f);
+  if (t.offgrid_scratch_bytes == 0) t.offgrid_scratch_bytes = kw_tuning_defaults().offgrid_scratch_bytes;
   ctx->tuning = t;
   return KW_OK;
 }

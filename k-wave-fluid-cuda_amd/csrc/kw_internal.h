@@ -34,6 +34,7 @@ inline kw_tuning kw_tuning_defaults()
   t.p2p_blocks_per_peer = 4;
   t.p2p_timeout_s       = 20.f;
   t.plane_kernels       = 1;
+  t.offgrid_scratch_bytes = 256ull << 20;
   return t;
 }
 #define KW_COMM_SLOTS 32 /* 2 directions x 3 arrays x KW_XCHUNKS_MAX plane chunks, + spare (z-shift staging) */
