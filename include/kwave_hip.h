@@ -516,6 +516,9 @@ KW_API kw_status kw_fused_shift_velocity(kw_ctx* ctx, int axis, const float* in,
 /* ------------------------------------------------------------------------------------------------------------------
  * Sampling kernels — replace namespace OutputStreamsCudaKernels (OutputStreams/OutputStreamsCudaKernels.cuh:47-106)
  * ---------------------------------------------------------------------------------------------------------------- */
+/* n_samples == 0 (for the post-processing entry points further down: n == 0) is KW_OK in every entry point of this
+ * section: nothing is launched and no pointer is looked at.  max / min are fmaxf / fminf as CUDA defines them: a NaN
+ * operand yields the other operand, +0 orders above -0. */
 /* sampleIndex<op> (.cuh:58-62, .cu:83-126) */
 KW_API kw_status kw_sample_index(kw_ctx* ctx, kw_reduce_op op, float* sampling_buffer, const float* source_data,
                                  const uint64_t* sensor_data, uint64_t n_samples);

@@ -174,7 +174,8 @@ kw_status kw_fft_create_plans_1d(kw_ctx* ctx, int axis)
 kw_status kw_time_shift_series(kw_ctx* ctx, float* series, const float* shift, uint64_t steps, uint64_t n)
 {
   KW_CHECK_CTX(ctx);
-  KW_REQUIRE(series != nullptr && shift != nullptr && steps >= 2 && n >= 1 && steps / 2 + 1 <= 65535u);
+  if (n == 0) return KW_OK; // no series: nothing to do, as in every other sampling entry point
+  KW_REQUIRE(series != nullptr && shift != nullptr && steps >= 2 && steps / 2 + 1 <= 65535u);
   KW_HIP(hipSetDevice(ctx->device));
   kw_status st = ensure_setup(ctx);
   if (st != KW_OK) return st;

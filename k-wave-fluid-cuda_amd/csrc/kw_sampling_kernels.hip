@@ -329,9 +329,9 @@ kw_status kw_sample_index_multi(kw_ctx* ctx, int n_ops, const kw_reduce_op* ops,
 {
   KW_CHECK_CTX(ctx);
   KW_PROF(ctx, "sample_index");
-  KW_REQUIRE(n_ops >= 1 && n_ops <= 4 && ops && bufs);
-  if (n == 0) return KW_OK;
-  KW_REQUIRE(src && mask);
+  KW_REQUIRE(n_ops >= 1 && n_ops <= 4);
+  if (n == 0) return KW_OK; // nothing to sample: no pointer is looked at, as in every other entry point
+  KW_REQUIRE(ops && bufs && src && mask);
   MultiSampleArgs a{};
   a.n_ops = n_ops;
   for (int o = 0; o < n_ops; o++)

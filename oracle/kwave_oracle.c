@@ -1071,14 +1071,31 @@ void kwo_step(kwo_sim* s)
 /* ------------------------------------------------------------------------------------------------
  * Sampling: OutputStreams/OutputStreamsCudaKernels.cu
  * ---------------------------------------------------------------------------------------------- */
+/* max() / min() of two floats in the reference's kernels are CUDA's fmaxf / fminf: a NaN operand yields the other operand
+ * (two NaNs: NaN), and zeros of unlike sign yield +0 for max and -0 for min.  Written out: C's fmaxf / fminf leave the
+ * zero ordering open, and (a > b) ? a : b returns b for (+0, -0) and for (x, NaN). */
+static inline float cuda_fmaxf(float a, float b)
+{
+  if (isnan(a)) return b;
+  if (isnan(b)) return a;
+  if (a == 0.0f && b == 0.0f) return signbit(a) ? b : a; /* +0 unless both are -0 */
+  return (a > b) ? a : b;
+}
+static inline float cuda_fminf(float a, float b)
+{
+  if (isnan(a)) return b;
+  if (isnan(b)) return a;
+  if (a == 0.0f && b == 0.0f) return signbit(a) ? a : b; /* -0 unless both are +0 */
+  return (a < b) ? a : b;
+}
 static inline void reduce_one(int op, float* b, float v)
 {
   switch (op)
   {
     case KWO_OP_NONE: *b = v; break;
     case KWO_OP_RMS: *b = fmaf(v, v, *b); break; /* nvcc default -fmad=true contracts buf += v*v (:91-93) into one FMA */
-    case KWO_OP_MAX: *b = (*b > v) ? *b : v; break; /* max(buf, v): :97-99 */
-    case KWO_OP_MIN: *b = (*b < v) ? *b : v; break;
+    case KWO_OP_MAX: *b = cuda_fmaxf(*b, v); break; /* max(buf, v): :97-99 */
+    case KWO_OP_MIN: *b = cuda_fminf(*b, v); break;
   }
 }
 void kwo_sample_index(int op, float* buf, const float* src, const uint64_t* mask, uint64_t n)

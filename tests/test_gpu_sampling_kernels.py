@@ -21,14 +21,12 @@ import pytest
 from conftest import ROOT
 
 sys.path.insert(0, ROOT)
-from gpu_buffers import Guarded  # noqa: E402
+from gpu_buffers import Guarded, check_bound, check_exact, report_worst, run  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-U = 2.0 ** -24
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 BIG_N = 600001  # > 524 288: past the grid-stride cap, ragged
-WORST = {}  # (family, k) -> worst |gpu - fp64| / (2^-24 M) seen, against its k + 1
 
 
 @pytest.fixture(scope="module")
@@ -37,10 +35,7 @@ def dev():
     from kwave_amd import capi
     d = capi.Device()
     yield d
-    if WORST:
-        print("\nworst |gpu - fp64| / (2^-24 M) per kernel (bound k + 1):")
-        for (fam, k), r in sorted(WORST.items()):
-            print(f"  {fam:34s} k = {k:2d}: {r:6.3f}  (bound {k + 1})")
+    report_worst(("sample_index_compress", "intensity_avg_c"))
     d.close()
 
 
@@ -66,52 +61,6 @@ def host_unpack(L, codes, e):
     out = np.zeros(codes.shape[:-1] + (2,), np.float32)
     assert L.kwh_unpack_complex_40b(codes.ctypes.data, codes.size // 5, out.ctypes.data, e) == 0
     return out
-
-
-def run(dev, entry, items):
-    """kw_<entry>(ctx, *args): (name, host array, read-only) tuples go through guarded buffers (None -> NULL), the rest
-    as they are; returns {name: array after the call} of the written buffers"""
-    bufs, conv = [], []
-    for it in items:
-        if isinstance(it, tuple):
-            name, h, ro = it
-            if h is None:
-                conv.append(None)
-                continue
-            g = Guarded(dev, h, 0, h.dtype)
-            bufs.append((name, g, h, ro))
-            conv.append(g.ptr)
-        else:
-            conv.append(it)
-    dev.call(entry, *conv)
-    out = {}
-    for name, g, h, ro in bufs:
-        v = g.read()
-        g.free()
-        if ro:
-            assert np.array_equal(v.view(np.uint8), h.view(np.uint8)), f"{entry}: read-only {name} changed"
-        else:
-            out[name] = v
-    return out
-
-
-def check_bound(family, label, got, ref, M, k):
-    got = got.astype(np.float64)
-    err = np.abs(got - ref)
-    ok = err <= (k + 1) * U * M
-    if not ok.all():
-        i = np.argwhere(~ok)[0]
-        raise AssertionError(f"{label}: {int((~ok).sum())} of {ok.size} elements outside (k+1) 2^-24 M, k = {k}; first at "
-                             f"{tuple(i)}: got {got[tuple(i)]!r}, fp64 {ref[tuple(i)]!r}, M {M[tuple(i)]!r}")
-    ratio = float(np.max(np.where(M > 0, err / np.where(M > 0, M, 1.0) / U, 0.0)))
-    WORST[(family, k)] = max(WORST.get((family, k), 0.0), ratio)
-
-
-def check_exact(label, got, want):
-    bad = got.view(np.uint8) != np.ascontiguousarray(want).view(np.uint8)
-    if bad.any():
-        i = np.argwhere(bad)[0]
-        raise AssertionError(f"{label}: {int(bad.sum())} of {bad.size} bytes differ; first at {tuple(i)}")
 
 
 def field_and_mask(rng, n, values=None):

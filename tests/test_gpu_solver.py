@@ -432,6 +432,79 @@ def test_cuboid_sensor_mask_streams(orc, syn):
     o.close()
 
 
+def rebuild_aggregates(raw):
+    """max, min and the RMS accumulator of a raw series, step by step with the operators of tests/sampling_reference.py
+    from the host's initial buffer values"""
+    from sampling_reference import INIT, reduce_ref
+    acc = {op: np.full(raw.shape[1], INIT[op], np.float32) for op in (1, 2, 3)}
+    for row in raw:
+        for op in acc:
+            acc[op] = reduce_ref(op, acc[op], row)
+    return acc
+
+
+def check_pressure_aggregates(g, raw, nt_file):
+    """p_max / p_min / p_rms of a finished run against its own raw series, bit for bit: the maximum and minimum over the
+    steps, and sqrtf(acc * scale) with acc the sum of squares in step order, one FMA per step, and scale the fp32 factor
+    of BaseOutputStream::postProcess, 1.0f / (Nt - sampling start) with the count converted to float first"""
+    from sampling_reference import check_bits, post_rms_ref
+    acc = rebuild_aggregates(raw)
+    check_bits("p_max", g.stream("p_max"), raw.max(axis=0))
+    check_bits("p_min", g.stream("p_min"), raw.min(axis=0))
+    check_bits("p_max against the step-wise operator", g.stream("p_max"), acc[2])
+    check_bits("p_min against the step-wise operator", g.stream("p_min"), acc[3])
+    scale = np.float32(1.0) / np.float32(nt_file)
+    check_bits("p_rms", g.stream("p_rms"), post_rms_ref(acc[1], scale))
+
+
+def test_cuboid_and_index_streams_are_pinned_to_the_raw_series(syn):
+    """(320, 16, 16) on the fused path, p0 source, 12 steps.  A corner mask of three cuboids: x 5..304 (300 wide: the
+    second 256-thread block of the cuboid kernel is partial), a single voxel, and 7 x 5 x 3, whose output starts at an odd
+    offset, 4 bytes off an 8-byte boundary.  Then an index mask of 1 031 points in random order with all four p streams,
+    which is the grouped sampleIndexMulti launch.  Raw rows are the gather of the device field; max, min and RMS are
+    rebuilt from the raw series bit for bit."""
+    nt = 12
+    pr = syn.make_problem(320, 16, 16, heterogeneous=True, nonlinear=True, absorbing=True, source="p0", nt=nt, pml_size=4)
+    nx, ny, nz = 320, 16, 16
+    rng = np.random.default_rng(1031)
+    index = rng.permutation(nx * ny * nz)[:1031]
+    corners = np.array([[6, 3, 2, 305, 6, 4], [9, 9, 9, 9, 9, 9], [150, 8, 10, 156, 12, 12]], dtype=np.uint64)  # 1-based
+    sizes = [300 * 4 * 3, 1, 7 * 5 * 3]
+
+    cub = {k: v for k, v in pr.items() if k != "sensor_mask_index"}
+    cub["sensor_mask_type"] = np.array([[[1]]], dtype=np.uint64)
+    cub["sensor_mask_corners"] = corners.reshape(1, 3, 6)
+    g = make_gpu(cub, p_raw=1, p_max=1, p_min=1, p_rms=1, u_max=1, u_min=1)
+    g.run(nt)
+    g.finish()
+    raw = g.stream("p")
+    assert raw.shape == (nt, sum(sizes))
+
+    def gather(field):
+        return np.concatenate([field[z0 - 1:z1, y0 - 1:y1, x0 - 1:x1].reshape(-1) for x0, y0, z0, x1, y1, z1 in corners.astype(int)])
+
+    assert np.array_equal(raw[-1].view(np.uint32), gather(g.field("p")).view(np.uint32))
+    assert np.abs(raw).max() > 0
+    check_pressure_aggregates(g, raw, nt)
+    for a, name in zip("xyz", ("ux", "uy", "uz")):  # no raw velocity series here: the last step lies between the extremes
+        last = gather(g.field(name))
+        assert np.all(g.stream(f"u{a}_max") >= last) and np.all(g.stream(f"u{a}_min") <= last), a
+        assert np.all(g.stream(f"u{a}_max") >= g.stream(f"u{a}_min")), a
+    g.close()
+
+    idx = dict(pr)
+    idx["sensor_mask_index"] = (index.astype(np.uint64) + np.uint64(1)).reshape(1, 1, -1)
+    g = make_gpu(idx, p_raw=1, p_max=1, p_min=1, p_rms=1)
+    g.run(nt)
+    g.finish()
+    raw = g.stream("p")
+    assert raw.shape == (nt, index.size)
+    assert np.array_equal(raw[-1].view(np.uint32), g.field("p").reshape(-1)[index].view(np.uint32))
+    assert np.abs(raw).max() > 0
+    check_pressure_aggregates(g, raw, nt)
+    g.close()
+
+
 def test_step_graph_replay_is_bit_identical(syn):
     """kwh_options::step_graph: the steady-state step replayed from a recorded graph (kw_graph_*) gives the same bits as eager
     launches, including across a source that stops mid-run (eager while it is active, graph afterwards)."""

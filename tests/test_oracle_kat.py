@@ -1,4 +1,4 @@
-"""Known-answer tests that pin the oracle (SURVEY.md §8c K1-K3, K7).  The reference ships no tests or
+"""Known-answer tests that pin the oracle (SURVEY.md §8c K1-K3, K5, K7).  The reference ships no tests or
 fixtures ("parity unpinned"), so the pins are analytic properties of the scheme it implements."""
 import math
 
@@ -7,6 +7,7 @@ import pytest
 
 from conftest import rel_l2
 from oracle.kwave_np import NumpySim, closed_form_pressure
+from sampling_reference import INIT, SPECIAL, SPECIAL_NO_NAN, check_bits, post_rms_ref, reduce_ref, special_field
 
 
 @pytest.fixture(scope="module")
@@ -108,3 +109,50 @@ def test_k7_pml_absorbs_energy(orc, syn):
     assert e1 < 0.02 * e0
     assert np.isfinite(e1)
     o.close()
+
+
+@pytest.mark.parametrize("op", [0, 1, 2, 3])
+def test_k5_sampling_on_special_values(orc, op):
+    """K5: the oracle's gather / RMS / max / min (index, cuboid and whole-domain entry points) against the NumPy
+    definition of tests/sampling_reference.py on fields of +-0, denormals, +-FLT_MIN, +-1, +-FLT_MAX, +-inf and NaN, three
+    steps each, from the host's initial values and from special values: max / min are CUDA's fmaxf / fminf (a NaN
+    operand yields the other operand, +0 orders above -0), the RMS step is one correctly rounded FMA."""
+    rng = np.random.default_rng(50 + op)
+    nx, ny, nz = 13, 7, 5
+    tl, br = (2, 1, 1), (10, 5, 3)
+    values = SPECIAL_NO_NAN if op == 1 else SPECIAL
+    mask = rng.permutation(nx * ny * nz)[:257].astype(np.uint64)
+    for start in ("host", "special"):
+        def first(n):
+            return np.full(n, INIT[op], np.float32) if start == "host" else special_field(rng, n)
+        b_idx, b_cub, b_all = first(mask.size), first(9 * 5 * 3), first(nx * ny * nz)
+        w_idx, w_cub, w_all = b_idx.copy(), b_cub.copy(), b_all.copy()
+        for step in range(3):
+            f = special_field(rng, (nz, ny, nx), values)
+            orc.sample_index(op, b_idx, f.reshape(-1), mask)
+            orc.sample_cuboid(op, b_cub, f.reshape(-1), tl, br, (nx, ny, nz))
+            orc.sample_all(op, b_all, f.reshape(-1))
+            w_idx = reduce_ref(op, w_idx, f.reshape(-1)[mask.astype(np.int64)])
+            w_cub = reduce_ref(op, w_cub, f[tl[2]:br[2] + 1, tl[1]:br[1] + 1, tl[0]:br[0] + 1].reshape(-1))
+            w_all = reduce_ref(op, w_all, f.reshape(-1))
+            check_bits(f"index {start} step {step}", b_idx, w_idx)
+            check_bits(f"cuboid {start} step {step}", b_cub, w_cub)
+            check_bits(f"all {start} step {step}", b_all, w_all)
+        if op == 1:
+            for scale in (1.0 / 3.0, 1.0, 2.0 ** -126):
+                got = b_all.copy()
+                orc.post_rms(got, scale)
+                check_bits(f"post_rms {start} scale {scale}", got, post_rms_ref(b_all, scale))
+
+
+def test_k5_rms_step_is_one_rounding(orc):
+    """the NumPy FMA of tests/sampling_reference.py against glibc's correctly rounded fmaf on white noise and on
+    accumulators far larger and far smaller than the squares: the two must agree bit for bit"""
+    rng = np.random.default_rng(5)
+    n = 200001
+    for scale_b in (1.0, 2.0 ** 24, 2.0 ** -24, 2.0 ** 48):
+        v = rng.standard_normal(n).astype(np.float32)
+        b = (rng.standard_normal(n) * scale_b).astype(np.float32)
+        want = reduce_ref(1, b, v)
+        orc.sample_all(1, b, v)
+        check_bits(f"fma, accumulator scale {scale_b}", b, want)
