@@ -612,6 +612,46 @@ KW_API kw_status kw_sample_elements_multi(kw_ctx* ctx, uint32_t n_fields, float*
                                           const uint32_t* ptr, const kw_csr_entry* entries, uint32_t n_elements,
                                           uint64_t nnz, const uint32_t* chunk_ptr, uint32_t n_chunks, float* partials);
 
+/* Per-entry time delays (new with this build): entry j of a CSR above may carry an integer delay d_j in time steps, at
+ * most KW_ELEMENT_MAX_DELAY, so that one signal drives a focused or steered array and a sensor delivers delay-and-sum
+ * series.  The delays travel beside the entries as uint32 values indexed like them; an entry stays one 8-byte load.
+ * kw_element_source_rows_delayed: rows[c][k] = sum over the entries j of row k, in CSR order, of
+ *     weight_j * element_inputs[c][(time_index - delays[j]) * n_elements + col_j],
+ * fp32 fma from 0 as in kw_element_source_row(s), for c = 0, 1, 2 in one launch.  element_inputs[c] is the start of
+ * component c's signals, signal_steps[c] rows of n_elements values; entry j is left out of component c's chain when
+ * time_index < delays[j] or time_index - delays[j] >= signal_steps[c].  (With every delay 0 and time_index below every
+ * signal_steps[c] the rows carry the bits of kw_element_source_rows; a time_index at or past the last row any entry can
+ * reach gives rows of +0.)  rows, element_inputs and signal_steps are host arrays of three; a component whose rows[c]
+ * is NULL is skipped and its other two values are never read.  With all three NULL nothing is launched. */
+#define KW_ELEMENT_MAX_DELAY 65535u
+KW_API kw_status kw_element_source_rows_delayed(kw_ctx* ctx, float* const rows[3], const float* const element_inputs[3],
+                                                const uint64_t signal_steps[3], const uint32_t* ptr,
+                                                const kw_csr_entry* entries, const uint32_t* delays, uint32_t n_points,
+                                                uint32_t n_elements, uint64_t time_index);
+/* kw_sample_elements_delayed: step n = rows_emitted of the delayed sensor,
+ *     out_n[e] = sum over the entries j of element e of weight_j * field^(n - d_j)[col_j],
+ * where field^(m) is what `fields` held at the call with rows_emitted == m and terms with n - d_j < 0 are dropped.
+ * The caller has regrouped each element's entries by delay, stably (CSR order inside a group); a group is the set of
+ * entries of one element with one delay.  entries holds the regrouped entries, group_ptr[0..n_groups] the groups'
+ * offsets into it, group_delay[g] a group's delay, element_group_ptr[0..n_elements] the elements' offsets into the
+ * groups, chunk_ptr[0..n_groups] the prefix sums of ceil(group length / KW_ELEMENT_CHUNK) (n_chunks in all) and
+ * partials n_fields * n_chunks floats of workspace.  rings[f] holds ring_rows x n_elements floats, ring_rows above the
+ * largest delay, zeroed by the caller before the call with rows_emitted == 0 and otherwise left to the calls; calls are
+ * made with rows_emitted = 0, 1, 2, ... on one stream.
+ * Two launches: the groups' chunk partials, with the device code of kw_sample_elements_multi on the groups as rows, so
+ * a group's sum carries the bits kw_sample_elements gives for it as a row of its own; then one thread per element adds
+ * each of its groups' sums, chunk partials in chunk order from 0, to ring row (rows_emitted + d) mod ring_rows in fp32,
+ * writes row rows_emitted mod ring_rows to outs[f] and clears it to +0.  Column e of a ring belongs to one thread: no
+ * atomics, and outs[f][e] is the sum of the element's group sums in descending delay order from +0 — the bits of
+ * kw_sample_elements(_multi) when every delay is 0.  outs, fields and rings are host arrays of n_fields (1 .. 3) device
+ * pointers.  A delay at or above ring_rows is folded into the ring (no access outside it) and gives wrong sums. */
+KW_API kw_status kw_sample_elements_delayed(kw_ctx* ctx, uint32_t n_fields, float* const outs[],
+                                            const float* const fields[], const uint32_t* group_ptr,
+                                            const kw_csr_entry* entries, const uint32_t* group_delay,
+                                            const uint32_t* element_group_ptr, uint32_t n_elements, uint32_t n_groups,
+                                            uint64_t nnz, const uint32_t* chunk_ptr, uint32_t n_chunks, float* partials,
+                                            float* const rings[], uint32_t ring_rows, uint64_t rows_emitted);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Off-grid elements (new with this build): the weights of the arrays above from the elements' geometry — what k-Wave's
  * kWaveArray computes with getArrayGridWeights / offGridPoints.  An element is a set of integration points on its

@@ -46,7 +46,27 @@ typedef struct kwh_dataset
  *   ux_ / uy_ / uz_source_element_input float (1, u?_source_flag, E)  one signal per element, per component
  * A component is active when its flag is above 0; the active components are all weighted or all plain, share E, and
  * may have different flags (a component stops when its own flag runs out).  u?_source_input must be absent,
- * u_source_many, if given, 1, and transducer_source_flag 0.  u_source_mode applies as to a u_source_many = 1 source. */
+ * u_source_many, if given, 1, and transducer_source_flag 0.  u_source_mode applies as to a u_source_many = 1 source.
+ *
+ * Per-entry time delays (optional; absent = all 0 and the undelayed kernels run), uint64 (1, 1, nnz), in time steps, one
+ * value per entry of the CSR beside it, at most KW_ELEMENT_MAX_DELAY (kwave_hip.h):
+ *   p_source_element_delay  point k receives v_k(t) = sum_j weight_j * signal[t - delay_j][element_j]; an entry is left
+ *                           out while t < delay_j or once t - delay_j >= p_source_flag.  The source acts while
+ *                           t < p_source_flag + the largest delay (capped by Nt).
+ *   u_source_element_delay  the same for u_source_element_*, shared by the components; each component acts for its own
+ *                           flag + the largest delay.
+ *   sensor_element_delay    for sensor_element_* (p_elements, u*_elements, u*_non_staggered_elements alike):
+ *                           out[t][e] = sum_j weight_j * field^(t - delay_j)[index_j] for t >= s, the sampling start; terms
+ *                           with t - delay_j < s are dropped.  The entries of an element are regrouped by delay (stably)
+ *                           and the group sums travel through a ring of (largest delay + 1) rows of E floats per field
+ *                           (kw_sample_elements_delayed), which is part of the stream's checkpoint state ("Temp_<stream>"
+ *                           in the reference-layout checkpoint file, behind the series in the file-less form).
+ * kwh_create refuses, naming the dataset, a delay dataset whose length differs from its CSR's entry count, a delay above
+ * the maximum, and a delay dataset without its CSR.  A slab rank's input may also hold the scalars
+ * p_source_element_delay_max / u_source_element_delay_max (uint64): the largest delay of the whole array, not below the
+ * rank's own, so that all ranks keep the source active for the same steps (dist.partition_problem writes them).  They are
+ * read wherever they are present: in the input of a single-GPU run they lengthen the source's window in the same way (the
+ * extra steps add rows of zeros), so leave them out there. */
 
 /* what the reference takes from the command line for the loop (CommandLineParameters.cpp:264-292) */
 typedef struct kwh_options

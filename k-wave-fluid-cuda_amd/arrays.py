@@ -10,6 +10,11 @@ The solver takes the array in this weighted form (include/kwave_host.h):
 * sensor (`--p_elements`): an element-major CSR matrix (`sensor_element_ptr`, `sensor_element_index`,
   `sensor_element_weight`) whose rows give one value per element and step, `p_elements[t][e] = sum_j w_j p[index_j]`.
 
+Every entry of the three CSR matrices may carry an integer time delay in steps (`p_source_element_delay`,
+`u_source_element_delay`, `sensor_element_delay`, built from the `delays=` argument of the three builders): point k gets
+`sum_j w_j s[t - d_j][e_j]`, element e records `sum_j w_j p^(t - d_j)[index_j]`.  `focus_delays` gives the delays that
+focus an array at a point.
+
 Elements are given as `[(flat grid indices, weights), ...]`, one pair per element, with 0-based linear grid indices in
 the x-fastest order of `sensor_mask_index` (`np.ravel` of a `[nz][ny][nx]` array).  Weights are used as given: any
 element-area normalisation belongs in them.
@@ -29,6 +34,7 @@ U64 = np.uint64
 Element = Tuple[Sequence[int], Sequence[float]]
 Shape = Tuple[np.ndarray, float, int]     # (points (P, 3) float64 in metres, measure in m^dim, dim)
 GOLDEN_ANGLE = math.pi * (3.0 - math.sqrt(5.0))
+MAX_DELAY = 65535                         # KW_ELEMENT_MAX_DELAY of include/kwave_hip.h
 
 
 class Grid(NamedTuple):
@@ -205,8 +211,46 @@ def _check(elements: Sequence[Element]):
     return out
 
 
-def weighted_source(elements: Sequence[Element], signals: np.ndarray) -> Dict[str, np.ndarray]:
+def _check_delays(els, delays):
+    """one integer array per element, aligned with its points -> the concatenated uint64 delays"""
+    if len(delays) != len(els):
+        raise ValueError(f"delays must hold one array per element ({len(els)}), got {len(delays)}")
+    out = []
+    for e, ((idx, _), d) in enumerate(zip(els, delays)):
+        d = np.asarray(d).reshape(-1)
+        if d.shape != idx.shape:
+            raise ValueError(f"element {e}: {idx.size} indices but {d.size} delays")
+        if d.size and (np.any(d != np.round(d)) or d.min() < 0 or d.max() > MAX_DELAY):
+            raise ValueError(f"element {e}: delays must be integers in 0..{MAX_DELAY}")
+        out.append(d.astype(np.int64))
+    return np.concatenate(out).astype(U64) if out else np.zeros(0, U64)
+
+
+def focus_delays(grid: Grid, elements: Sequence[Element], focus, sound_speed: float, dt: float,
+                 per_element: bool = False) -> List[np.ndarray]:
+    """Per-point delays that focus an array at `focus` (metres), one int64 array per element aligned with its points:
+    round((r_max - r_j) / (sound_speed * dt)), r_j the distance of grid point j from the focus.  r_max is the largest
+    distance over the whole array, so the farthest point fires first (delay 0) and all arrivals coincide; with
+    per_element=True it is taken inside each element, which focuses every element on its own (an elevation focus) and
+    leaves steering between elements to the signals."""
+    grid = Grid(*(getattr(grid, n) for n in Grid._fields))
+    f = _vec3(focus, "focus")
+    if not (sound_speed > 0.0 and dt > 0.0):
+        raise ValueError("sound_speed and dt must be positive")
+    dist = []
+    for idx, _ in _check(elements):
+        pos = np.stack([(idx % grid.nx - grid.nx // 2) * grid.dx, (idx // grid.nx % grid.ny - grid.ny // 2) * grid.dy,
+                        (idx // (grid.nx * grid.ny) - grid.nz // 2) * grid.dz], axis=1).astype(np.float64)
+        dist.append(np.sqrt(((pos - f) ** 2).sum(axis=1)))
+    whole = max((float(r.max()) for r in dist if r.size), default=0.0)
+    return [np.round(((float(r.max()) if per_element and r.size else whole) - r) / (sound_speed * dt)).astype(np.int64)
+            for r in dist]
+
+
+def weighted_source(elements: Sequence[Element], signals: np.ndarray, delays=None) -> Dict[str, np.ndarray]:
     """Datasets of a weighted pressure source.  signals: (Nt_src, E) array, row t = the element signals of step t.
+    delays: None, or one integer array per element aligned with its points (time steps, e.g. focus_delays); they follow
+    their entries through the transpose into p_source_element_delay, and the source then acts for Nt_src + max delay steps.
 
     The source points are the union of the elements' points in ascending grid order; point k's CSR row holds one entry
     per element that covers it, in element order (the point-major transpose of the element lists).  Sets
@@ -223,7 +267,9 @@ def weighted_source(elements: Sequence[Element], signals: np.ndarray) -> Dict[st
     points, counts = np.unique(pts, return_counts=True)
     ptr = np.zeros(points.size + 1, dtype=U64)
     ptr[1:] = np.cumsum(counts)
+    extra = {} if delays is None else {"p_source_element_delay": _check_delays(els, delays)[order].reshape(1, 1, -1)}
     return {
+        **extra,
         "p_source_flag": np.array([[[sig.shape[0]]]], dtype=U64),
         "p_source_index": (points + 1).astype(U64).reshape(1, 1, -1),
         "p_source_element_input": np.ascontiguousarray(sig).reshape(1, sig.shape[0], sig.shape[1]),
@@ -233,11 +279,12 @@ def weighted_source(elements: Sequence[Element], signals: np.ndarray) -> Dict[st
     }
 
 
-def weighted_velocity_source(elements: Sequence[Element], signals_x=None, signals_y=None, signals_z=None
+def weighted_velocity_source(elements: Sequence[Element], signals_x=None, signals_y=None, signals_z=None, delays=None
                              ) -> Dict[str, np.ndarray]:
     """Datasets of a weighted velocity source.  signals_x / _y / _z: (Nt_src, E) arrays or None; a component left out is
     not driven (its flag is 0).  The components may differ in Nt_src.  The points and the CSR are those of
-    weighted_source and are shared by the components; u_source_many is 1 and u_source_mode is left to the caller."""
+    weighted_source and are shared by the components; u_source_many is 1 and u_source_mode is left to the caller.
+    delays: as in weighted_source, into u_source_element_delay, shared by the components."""
     given = {c: np.asarray(s, dtype=np.float32) for c, s in (("x", signals_x), ("y", signals_y), ("z", signals_z))
              if s is not None}
     if not given:
@@ -245,9 +292,9 @@ def weighted_velocity_source(elements: Sequence[Element], signals_x=None, signal
     for c, sig in given.items():
         if sig.ndim != 2 or sig.shape[1] != len(elements):
             raise ValueError(f"signals_{c} must be (Nt, E={len(elements)}), got {sig.shape}")
-    csr = weighted_source(elements, next(iter(given.values())))
+    csr = weighted_source(elements, next(iter(given.values())), delays)
     out = {"u_source_index": csr["p_source_index"], "u_source_many": np.array([[[1]]], dtype=U64)}
-    for part in ("ptr", "index", "weight"):
+    for part in ("ptr", "index", "weight") + (("delay",) if delays is not None else ()):
         out["u_source_element_" + part] = csr["p_source_element_" + part]
     for c in "xyz":
         out[f"u{c}_source_flag"] = np.array([[[given[c].shape[0] if c in given else 0]]], dtype=U64)
@@ -256,15 +303,18 @@ def weighted_velocity_source(elements: Sequence[Element], signals_x=None, signal
     return out
 
 
-def weighted_sensor(elements: Sequence[Element]) -> Dict[str, np.ndarray]:
+def weighted_sensor(elements: Sequence[Element], delays=None) -> Dict[str, np.ndarray]:
     """Datasets of a weighted sensor (record it with --p_elements / HostSolver(..., p_elements=1)): element e's row holds
-    its points and weights in the order given."""
+    its points and weights in the order given.  delays: None, or one integer array per element aligned with its points,
+    into sensor_element_delay: element e then records sum_j w_j p^(t - d_j)[index_j] (delay-and-sum on receive)."""
     els = _check(elements)
     ptr = np.zeros(len(els) + 1, dtype=U64)
     ptr[1:] = np.cumsum([i.size for i, _ in els])
     idx = np.concatenate([i for i, _ in els]) if els else np.zeros(0, np.int64)
     w = np.concatenate([w for _, w in els]) if els else np.zeros(0, np.float32)
+    extra = {} if delays is None else {"sensor_element_delay": _check_delays(els, delays).reshape(1, 1, -1)}
     return {
+        **extra,
         "sensor_element_ptr": ptr.reshape(1, 1, -1),
         "sensor_element_index": (idx + 1).astype(U64).reshape(1, 1, -1),
         "sensor_element_weight": w.astype(np.float32).reshape(1, 1, -1),
@@ -273,13 +323,23 @@ def weighted_sensor(elements: Sequence[Element]) -> Dict[str, np.ndarray]:
 
 def expand_source(ds: Dict[str, np.ndarray]) -> np.ndarray:
     """The expanded (p_source_many = 1) series of a weighted source, (1, Nt_src, Npts) float32: every point's series
-    summed in float64 from the element signals and weights, then rounded once."""
+    summed in float64 from the element signals and weights, then rounded once.  With p_source_element_delay the series
+    has Nt_src + max delay rows, row t = sum_j w_j s[t - d_j][e_j] over the entries whose signal row exists: the
+    expanded problem's p_source_flag is that row count (capped by Nt)."""
     sig = np.asarray(ds["p_source_element_input"], dtype=np.float64)
     sig = sig.reshape(sig.shape[-2], sig.shape[-1])
     ptr = np.asarray(ds["p_source_element_ptr"]).reshape(-1).astype(np.int64)
     col = np.asarray(ds["p_source_element_index"]).reshape(-1).astype(np.int64) - 1
     w = np.asarray(ds["p_source_element_weight"], dtype=np.float64).reshape(-1)
     rows = np.repeat(np.arange(ptr.size - 1), np.diff(ptr))
+    if "p_source_element_delay" in ds:
+        d = np.asarray(ds["p_source_element_delay"]).reshape(-1).astype(np.int64)
+        nt = sig.shape[0] + (int(d.max()) if d.size else 0)
+        out = np.zeros((nt, ptr.size - 1), dtype=np.float64)
+        for delay in np.unique(d):                        # entries in CSR order inside a delay, delays ascending
+            j = np.nonzero(d == delay)[0]
+            np.add.at(out[delay:delay + sig.shape[0]].T, rows[j], (w[j, None] * sig[:, col[j]].T))
+        return out.astype(np.float32).reshape(1, nt, -1)
     out = np.zeros((sig.shape[0], ptr.size - 1), dtype=np.float64)
     np.add.at(out.T, rows, (w[:, None] * sig[:, col].T))
     return out.astype(np.float32).reshape(1, sig.shape[0], -1)
@@ -287,23 +347,44 @@ def expand_source(ds: Dict[str, np.ndarray]) -> np.ndarray:
 
 def expand_velocity_source(ds: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
     """The expanded (u_source_many = 1) series of a weighted velocity source: {"ux_source_input": (1, Nt_src, Npts)
-    float32, ...} for the components that `ds` drives, each as expand_source gives it."""
+    float32, ...} for the components that `ds` drives, each as expand_source gives it (with u_source_element_delay:
+    its Nt_src + max delay rows)."""
     out = {}
     for c in "xyz":
         name = f"u{c}_source_element_input"
         if name in ds:
             one = {"p_source_element_input": ds[name]}
-            for part in ("ptr", "index", "weight"):
+            for part in ("ptr", "index", "weight") + (("delay",) if "u_source_element_delay" in ds else ()):
                 one["p_source_element_" + part] = ds["u_source_element_" + part]
             out[f"u{c}_source_input"] = expand_source(one)
     return out
 
 
 def sensor_matrix(ds: Dict[str, np.ndarray], n_grid: int) -> np.ndarray:
-    """The weighted sensor as a dense float64 (E, n_grid) matrix W (p_elements[t] = W @ p[t].ravel())."""
+    """The weighted sensor as a dense float64 (E, n_grid) matrix W (p_elements[t] = W @ p[t].ravel()).  A delayed sensor is
+    no single matrix: it is refused here, delayed_sensor_matrices gives one matrix per delay."""
+    if "sensor_element_delay" in ds:
+        raise ValueError("sensor_matrix: the sensor carries sensor_element_delay; use delayed_sensor_matrices")
     ptr = np.asarray(ds["sensor_element_ptr"]).reshape(-1).astype(np.int64)
     idx = np.asarray(ds["sensor_element_index"]).reshape(-1).astype(np.int64) - 1
     w = np.asarray(ds["sensor_element_weight"], dtype=np.float64).reshape(-1)
     W = np.zeros((ptr.size - 1, n_grid), dtype=np.float64)
     np.add.at(W, (np.repeat(np.arange(ptr.size - 1), np.diff(ptr)), idx), w)
     return W
+
+
+def delayed_sensor_matrices(ds: Dict[str, np.ndarray], n_grid: int) -> Dict[int, np.ndarray]:
+    """A delayed weighted sensor as {delay: dense float64 (E, n_grid) matrix W_d}: p_elements[t] = sum_d W_d @ p[t - d].ravel()
+    over the delays with t - d at or after the sampling start.  Without sensor_element_delay: {0: sensor_matrix(ds)}."""
+    ptr = np.asarray(ds["sensor_element_ptr"]).reshape(-1).astype(np.int64)
+    idx = np.asarray(ds["sensor_element_index"]).reshape(-1).astype(np.int64) - 1
+    w = np.asarray(ds["sensor_element_weight"], dtype=np.float64).reshape(-1)
+    d = np.asarray(ds["sensor_element_delay"]).reshape(-1).astype(np.int64) if "sensor_element_delay" in ds else np.zeros(idx.size, np.int64)
+    rows = np.repeat(np.arange(ptr.size - 1), np.diff(ptr))
+    out = {}
+    for delay in np.unique(d) if d.size else [0]:
+        j = np.nonzero(d == delay)[0]
+        W = np.zeros((ptr.size - 1, n_grid), dtype=np.float64)
+        np.add.at(W, (rows[j], idx[j]), w[j])
+        out[int(delay)] = W
+    return out

@@ -181,6 +181,9 @@ _SIG: Dict[str, list] = {
     "kw_sample_elements": [_P, _P, _P, _P, _P, C.c_uint32, _U64, _P, C.c_uint32, _P],
     "kw_element_source_rows": [_P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _U64],
     "kw_sample_elements_multi": [_P, C.c_uint32, _P, _P, _P, _P, C.c_uint32, _U64, _P, C.c_uint32, _P],
+    "kw_element_source_rows_delayed": [_P, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _U64],
+    "kw_sample_elements_delayed": [_P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _U64, _P, C.c_uint32, _P,
+                                   _P, C.c_uint32, _U64],
     "kw_offgrid_build": [_P, _P, _P, _P, _U64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, _U64, C.POINTER(_P)],
     "kw_offgrid_size": [_P, _P, C.POINTER(_U64), C.POINTER(_U64)],
     "kw_offgrid_ptr": [_P, _P, _P],

@@ -193,6 +193,103 @@ __global__ __launch_bounds__(256) void k_sample_elements_multi_sum(ElementFields
   }
 }
 
+// ---- per-entry time delays -------------------------------------------------------------------------------------------
+struct ElementDelayedRows
+{
+  float*       row[3];    // nullptr: the component is not written ...
+  const float* signal[3]; // ... and its signals (steps[c] rows of n_elements values) are not read
+  uint64_t     steps[3];
+};
+
+// element_source_rows_body with entry j reading signal row t - delays[j]: the same fma chain from 0 in CSR order, an entry
+// whose row lies before the signal's start or past its end is left out of the chain
+template<bool X, bool Y, bool Z>
+__device__ __forceinline__ void element_source_rows_delayed_body(const ElementDelayedRows& a, const uint32_t* __restrict__ ptr,
+                                                                 const uint2* __restrict__ entries,
+                                                                 const uint32_t* __restrict__ delays, uint32_t n_points,
+                                                                 uint32_t n_elements, uint64_t t)
+{
+  for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < n_points; k += gridDim.x * blockDim.x)
+  {
+    const uint32_t end = ptr[k + 1];
+    float ax = 0.0f, ay = 0.0f, az = 0.0f;
+    for (uint32_t j = ptr[k]; j < end; j++)
+    {
+      const uint2    e = entries[j];
+      const uint64_t d = delays[j];
+      if (d > t) continue;
+      const uint64_t s   = t - d;
+      const size_t   at  = static_cast<size_t>(s) * n_elements + e.x;
+      const float    w   = __uint_as_float(e.y);
+      if (X && s < a.steps[0]) ax = __fmaf_rn(w, a.signal[0][at], ax);
+      if (Y && s < a.steps[1]) ay = __fmaf_rn(w, a.signal[1][at], ay);
+      if (Z && s < a.steps[2]) az = __fmaf_rn(w, a.signal[2][at], az);
+    }
+    if (X) a.row[0][k] = ax;
+    if (Y) a.row[1][k] = ay;
+    if (Z) a.row[2][k] = az;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_element_source_rows_delayed(ElementDelayedRows a, const uint32_t* __restrict__ ptr,
+                                                                     const uint2* __restrict__ entries,
+                                                                     const uint32_t* __restrict__ delays, uint32_t n_points,
+                                                                     uint32_t n_elements, uint64_t t)
+{
+  const uint32_t mask = (a.row[0] ? 1u : 0u) | (a.row[1] ? 2u : 0u) | (a.row[2] ? 4u : 0u);
+  switch (mask)
+  {
+    case 1: element_source_rows_delayed_body<true, false, false>(a, ptr, entries, delays, n_points, n_elements, t); break;
+    case 2: element_source_rows_delayed_body<false, true, false>(a, ptr, entries, delays, n_points, n_elements, t); break;
+    case 3: element_source_rows_delayed_body<true, true, false>(a, ptr, entries, delays, n_points, n_elements, t); break;
+    case 4: element_source_rows_delayed_body<false, false, true>(a, ptr, entries, delays, n_points, n_elements, t); break;
+    case 5: element_source_rows_delayed_body<true, false, true>(a, ptr, entries, delays, n_points, n_elements, t); break;
+    case 6: element_source_rows_delayed_body<false, true, true>(a, ptr, entries, delays, n_points, n_elements, t); break;
+    case 7: element_source_rows_delayed_body<true, true, true>(a, ptr, entries, delays, n_points, n_elements, t); break;
+    default: break;
+  }
+}
+
+struct ElementRings
+{
+  float* out[3];
+  float* ring[3]; // ring_rows x n_elements floats per field
+};
+
+// one thread per element: each of its groups' chunk partials in chunk order from 0, added to the ring row the group's
+// delay points at; then the row of this step is emitted and cleared.  Column e of every ring row belongs to this thread
+// alone, so the additions need no atomics and arrive in a fixed order.
+__global__ __launch_bounds__(256) void k_sample_elements_ring(ElementRings a, uint32_t n_fields,
+                                                              const float* __restrict__ partials,
+                                                              const uint32_t* __restrict__ element_group_ptr,
+                                                              const uint32_t* __restrict__ group_delay,
+                                                              const uint32_t* __restrict__ chunk_ptr, uint32_t n_elements,
+                                                              uint32_t n_chunks, uint32_t ring_rows, uint32_t row_now)
+{
+  const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n_elements) return;
+  const uint32_t g_begin = element_group_ptr[e], g_end = element_group_ptr[e + 1];
+#pragma unroll
+  for (uint32_t f = 0; f < 3; f++) // unrolled: a.ring[f] and a.out[f] stay kernel arguments
+  {
+    if (f >= n_fields) break;
+    float* ring = a.ring[f];
+    for (uint32_t g = g_begin; g < g_end; g++)
+    {
+      const uint32_t end = chunk_ptr[g + 1];
+      float acc = 0.0f;
+      for (uint32_t c = chunk_ptr[g]; c < end; c++) acc += partials[f * n_chunks + c];
+      // row_now < ring_rows and the remainder of the delay keep the row inside the ring whatever the delay holds
+      const uint32_t r = static_cast<uint32_t>((static_cast<uint64_t>(row_now) + group_delay[g]) % ring_rows);
+      const size_t  at = static_cast<size_t>(r) * n_elements + e;
+      ring[at] += acc;
+    }
+    const size_t now = static_cast<size_t>(row_now) * n_elements + e;
+    a.out[f][e] = ring[now];
+    ring[now]   = 0.0f;
+  }
+}
+
 extern "C" {
 
 kw_status kw_element_source_rows(kw_ctx* ctx, float* const rows[3], const float* const element_inputs[3],
@@ -295,6 +392,80 @@ kw_status kw_sample_elements(kw_ctx* ctx, float* out, const float* p, const uint
   }
   hipLaunchKernelGGL(k_sample_elements_sum, dim3((n_elements + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, out,
                      partials, chunk_ptr, n_elements);
+  KW_LAUNCH_CHECK();
+  return KW_OK;
+}
+
+kw_status kw_element_source_rows_delayed(kw_ctx* ctx, float* const rows[3], const float* const element_inputs[3],
+                                         const uint64_t signal_steps[3], const uint32_t* ptr, const kw_csr_entry* entries,
+                                         const uint32_t* delays, uint32_t n_points, uint32_t n_elements, uint64_t time_index)
+{
+  KW_CHECK_CTX(ctx);
+  KW_PROF(ctx, "element_source_rows_delayed");
+  KW_REQUIRE(rows && element_inputs && signal_steps);
+  ElementDelayedRows a{};
+  bool any = false;
+  for (int c = 0; c < 3; c++)
+  {
+    if (rows[c] == nullptr) continue; // skipped: element_inputs[c] and signal_steps[c] are not looked at
+    KW_REQUIRE(element_inputs[c] != nullptr);
+    a.row[c]    = rows[c];
+    a.signal[c] = element_inputs[c];
+    a.steps[c]  = signal_steps[c];
+    any         = true;
+  }
+  if (n_points == 0 || !any) return KW_OK;
+  KW_REQUIRE(ptr && entries && delays && n_elements > 0);
+  uint32_t grid = (n_points + kBlock - 1) / kBlock;
+  const uint32_t cap = static_cast<uint32_t>(ctx->cu_count) * 8;
+  if (grid > cap) grid = cap;
+  hipLaunchKernelGGL(k_element_source_rows_delayed, dim3(grid), dim3(kBlock), 0, ctx->stream, a, ptr,
+                     reinterpret_cast<const uint2*>(entries), delays, n_points, n_elements, time_index);
+  KW_LAUNCH_CHECK();
+  return KW_OK;
+}
+
+kw_status kw_sample_elements_delayed(kw_ctx* ctx, uint32_t n_fields, float* const outs[], const float* const fields[],
+                                     const uint32_t* group_ptr, const kw_csr_entry* entries, const uint32_t* group_delay,
+                                     const uint32_t* element_group_ptr, uint32_t n_elements, uint32_t n_groups, uint64_t nnz,
+                                     const uint32_t* chunk_ptr, uint32_t n_chunks, float* partials, float* const rings[],
+                                     uint32_t ring_rows, uint64_t rows_emitted)
+{
+  KW_CHECK_CTX(ctx);
+  KW_PROF(ctx, "sample_elements_delayed");
+  KW_REQUIRE(n_fields >= 1 && n_fields <= 3 && outs && fields && rings);
+  if (n_elements == 0) return KW_OK;
+  KW_REQUIRE(ring_rows >= 1 && element_group_ptr && nnz <= 0xFFFFFFFFull);
+  KW_REQUIRE(static_cast<uint64_t>(n_fields) * n_chunks <= 0xFFFFFFFFull);
+  KW_REQUIRE(n_groups == 0 || (group_ptr && group_delay && chunk_ptr));
+  KW_REQUIRE(n_chunks == 0 || (n_groups > 0 && entries && partials));
+  ElementFields a{};
+  ElementRings  r{};
+  for (uint32_t f = 0; f < n_fields; f++)
+  {
+    KW_REQUIRE(outs[f] && rings[f] && (n_chunks == 0 || fields[f]));
+    a.field[f] = fields[f];
+    r.out[f]   = outs[f];
+    r.ring[f]  = rings[f];
+  }
+  if (n_chunks > 0)
+  {
+    // the groups as rows of k_sample_elements_multi: a group's partials carry the bits its row would
+    const uint2* e = reinterpret_cast<const uint2*>(entries);
+    if (n_fields == 1)
+      hipLaunchKernelGGL(k_sample_elements_multi<1>, dim3(n_chunks), dim3(kBlock), 0, ctx->stream, partials, a, group_ptr, e,
+                         chunk_ptr, n_groups, n_chunks);
+    else if (n_fields == 2)
+      hipLaunchKernelGGL(k_sample_elements_multi<2>, dim3(n_chunks), dim3(kBlock), 0, ctx->stream, partials, a, group_ptr, e,
+                         chunk_ptr, n_groups, n_chunks);
+    else
+      hipLaunchKernelGGL(k_sample_elements_multi<3>, dim3(n_chunks), dim3(kBlock), 0, ctx->stream, partials, a, group_ptr, e,
+                         chunk_ptr, n_groups, n_chunks);
+    KW_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(k_sample_elements_ring, dim3((n_elements + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, r,
+                     n_fields, partials, element_group_ptr, group_delay, chunk_ptr, n_elements, n_chunks, ring_rows,
+                     static_cast<uint32_t>(rows_emitted % ring_rows));
   KW_LAUNCH_CHECK();
   return KW_OK;
 }

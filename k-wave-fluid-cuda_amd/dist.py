@@ -84,13 +84,23 @@ def partition_problem(pr: Dict[str, np.ndarray], rank: int, nranks: int, arrays_
         out["sensor_element_index"] = loc.reshape(1, 1, -1)
         out["sensor_element_weight"] = np.ascontiguousarray(
             np.asarray(pr["sensor_element_weight"]).reshape(-1)[sel], dtype=np.float32).reshape(1, 1, -1)
+        if "sensor_element_delay" in pr:   # the delays follow their entries; every rank keeps a ring of its own
+            out["sensor_element_delay"] = np.ascontiguousarray(
+                np.asarray(pr["sensor_element_delay"]).reshape(-1)[sel], dtype=U64).reshape(1, 1, -1)
+    # delayed sources: a rank's own entries may lack the largest delay, but every rank has to keep the source active for
+    # the same steps (the additive modes' k-space correction is a transform over all slabs)
+    for q in ("p", "u"):
+        if q + "_source_element_delay" in pr:
+            d = np.asarray(pr[q + "_source_element_delay"]).reshape(-1)
+            out[q + "_source_element_delay_max"] = np.array([[[int(d.max()) if d.size else 0]]], dtype=U64)
 
     for name, a in pr.items():
         a = np.asarray(a)
         if name in ("p_source_element_ptr", "u_source_element_ptr", "sensor_element_ptr", "sensor_element_index",
-                    "sensor_element_weight"):
+                    "sensor_element_weight", "sensor_element_delay", "p_source_element_delay_max",
+                    "u_source_element_delay_max"):
             continue  # built above
-        if name[1:] in ("_source_element_index", "_source_element_weight") and name[0] in src_rows:
+        if name[1:] in ("_source_element_index", "_source_element_weight", "_source_element_delay") and name[0] in src_rows:
             out[name] = np.ascontiguousarray(a.reshape(-1)[src_rows[name[0]]]).reshape(1, 1, -1)
             continue
         if name == "Nz":

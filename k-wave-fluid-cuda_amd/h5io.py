@@ -129,7 +129,10 @@ INPUT_DATASETS = (
     "p_source_element_input", "p_source_element_ptr", "p_source_element_index", "p_source_element_weight",
     "sensor_element_ptr", "sensor_element_index", "sensor_element_weight",
     "u_source_element_ptr", "u_source_element_index", "u_source_element_weight",
-    "ux_source_element_input", "uy_source_element_input", "uz_source_element_input")
+    "ux_source_element_input", "uy_source_element_input", "uz_source_element_input",
+    # per-entry time delays of the three CSRs, and the horizon dist.partition_problem gives the ranks of a slab run
+    "p_source_element_delay", "u_source_element_delay", "sensor_element_delay",
+    "p_source_element_delay_max", "u_source_element_delay_max")
 
 
 def dataset_exists(path: str, name: str) -> bool:

@@ -52,11 +52,24 @@ void KSpaceFirstOrderSolver::loadInputData(const InputProvider& input)
 {
   PhaseTimer timer(mPhaseTime[0]);
   mMatrixContainer.loadDataFromInputFile(input);
-  if (mParameters.getPressureSourceElementFlag())
+  if (mParameters.getPressureSourceElementFlag() && mParameters.getPressureSourceElementDelayFlag())
+    mSourceElements.uploadWithDelays(index(MI::kPressureSourceElementPtr).getHostData(), mParameters.getPressureSourceIndexSize(),
+                                     index(MI::kPressureSourceElementIndex).getHostData(),
+                                     real(MI::kPressureSourceElementWeight).getHostData(),
+                                     index(MI::kPressureSourceElementDelay).getHostData(),
+                                     mParameters.getPressureSourceElementNnz());
+  else if (mParameters.getPressureSourceElementFlag())
     mSourceElements.upload(index(MI::kPressureSourceElementPtr).getHostData(), mParameters.getPressureSourceIndexSize(),
                            index(MI::kPressureSourceElementIndex).getHostData(),
                            real(MI::kPressureSourceElementWeight).getHostData(), mParameters.getPressureSourceElementNnz(), false);
-  if (mParameters.getVelocitySourceElementFlag())
+  if (mParameters.getVelocitySourceElementFlag() && mParameters.getVelocitySourceElementDelayFlag())
+    mVelocitySourceElements.uploadWithDelays(index(MI::kVelocitySourceElementPtr).getHostData(),
+                                             mParameters.getVelocitySourceIndexSize(),
+                                             index(MI::kVelocitySourceElementIndex).getHostData(),
+                                             real(MI::kVelocitySourceElementWeight).getHostData(),
+                                             index(MI::kVelocitySourceElementDelay).getHostData(),
+                                             mParameters.getVelocitySourceElementNnz());
+  else if (mParameters.getVelocitySourceElementFlag())
     mVelocitySourceElements.upload(index(MI::kVelocitySourceElementPtr).getHostData(), mParameters.getVelocitySourceIndexSize(),
                                    index(MI::kVelocitySourceElementIndex).getHostData(),
                                    real(MI::kVelocitySourceElementWeight).getHostData(),
@@ -247,15 +260,16 @@ void KSpaceFirstOrderSolver::runTimeSteps(size_t nSteps)
     const size_t timeIndex = mParameters.getTimeIndex();
     // fused pipeline: the velocity stage may hand the x-spectra of u straight to the density stage when no velocity /
     // transducer source writes u in between this step
-    mVelocityChained = mFused && !(mParameters.getVelocityXSourceFlag() > timeIndex) &&
-                       !(mParameters.getVelocityYSourceFlag() > timeIndex) &&
-                       !(mParameters.getVelocityZSourceFlag() > timeIndex) &&
+    // (a delayed weighted source acts for its largest delay past its flag: the lengths, not the flags, decide)
+    mVelocityChained = mFused && !(mParameters.getVelocityXSourceLength() > timeIndex) &&
+                       !(mParameters.getVelocityYSourceLength() > timeIndex) &&
+                       !(mParameters.getVelocityZSourceLength() > timeIndex) &&
                        !(mParameters.getTransducerSourceFlag() > timeIndex);
     // steady state of the fused pipeline: no source writes a field this step and the step starts from the chained
     // spectrum of p — then the step is the same sequence of launches with the same arguments every time, and its host
     // and pipeline state on exit equals that on entry: it can be replayed from a recorded graph
     const bool steady = mUseStepGraph && !mStepGraphFailed && mVelocityChained && mPressureInScratch && (timeIndex > 0) &&
-                        !(mParameters.getPressureSourceFlag() > timeIndex) &&
+                        !(mParameters.getPressureSourceLength() > timeIndex) &&
                         !kw_profile_enabled(mParameters.getHipParameters().getContext());
     auto stages = [&]() {
       computeVelocity<SD::k3D>();
@@ -585,7 +599,7 @@ void KSpaceFirstOrderSolver::fusedDensity(bool nonlinear)
   const MatrixContainer& c = mMatrixContainer;
   const bool absorbing     = mParameters.getAbsorbingFlag() != 0;
   const bool stokes        = mParameters.isStokesAbsorption();
-  const bool pSourceActive = mParameters.getPressureSourceFlag() > mParameters.getTimeIndex();
+  const bool pSourceActive = mParameters.getPressureSourceLength() > mParameters.getTimeIndex();
   mTermsFused              = absorbing && !stokes && !pSourceActive;
   // lossless media and Stokes absorption: the equation of state (computePressure*'s element-wise branches) is part of the
   // density kernel, and the spectrum of the new p is chained unless p is about to be overwritten by the initial pressure
@@ -785,11 +799,13 @@ template<SD sd> void KSpaceFirstOrderSolver::computePressureLinear()
 void KSpaceFirstOrderSolver::addVelocitySource()
 { // :2252-2303
   const size_t timeIndex = mParameters.getTimeIndex();
-  struct Comp { size_t flag; MI u; MI input; MI elementInput; };
+  // flag: the rows of the component's signals; length: the steps it acts for (the flag, or with per-entry delays the flag
+  // plus the largest delay)
+  struct Comp { size_t flag; size_t length; MI u; MI input; MI elementInput; };
   const Comp comps[3] = {
-    {mParameters.getVelocityXSourceFlag(), MI::kUxSgx, MI::kVelocityXSourceInput, MI::kVelocityXSourceElementInput},
-    {mParameters.getVelocityYSourceFlag(), MI::kUySgy, MI::kVelocityYSourceInput, MI::kVelocityYSourceElementInput},
-    {mParameters.getVelocityZSourceFlag(), MI::kUzSgz, MI::kVelocityZSourceInput, MI::kVelocityZSourceElementInput}};
+    {mParameters.getVelocityXSourceFlag(), mParameters.getVelocityXSourceLength(), MI::kUxSgx, MI::kVelocityXSourceInput, MI::kVelocityXSourceElementInput},
+    {mParameters.getVelocityYSourceFlag(), mParameters.getVelocityYSourceLength(), MI::kUySgy, MI::kVelocityYSourceInput, MI::kVelocityYSourceElementInput},
+    {mParameters.getVelocityZSourceFlag(), mParameters.getVelocityZSourceLength(), MI::kUzSgz, MI::kVelocityZSourceInput, MI::kVelocityZSourceElementInput}};
   // weighted source: this step's rows v_c(t) = W s_c(t) of the components still running go into their one-row series
   // buffers in one launch; the kernels below then read row 0 of a u_source_many = 1 source (as addPressureSource does)
   size_t seriesRow = timeIndex;
@@ -797,15 +813,23 @@ void KSpaceFirstOrderSolver::addVelocitySource()
   {
     float*       rows[3]   = {nullptr, nullptr, nullptr};
     const float* inputs[3] = {nullptr, nullptr, nullptr};
+    uint64_t     steps[3]  = {0, 0, 0};
     bool any = false;
     for (int c = 0; c < 3; c++)
     {
-      if (!(comps[c].flag > timeIndex)) continue;
+      if (!(comps[c].length > timeIndex)) continue;
       rows[c]   = real(comps[c].input).getDeviceData();
       inputs[c] = real(comps[c].elementInput).getDeviceData();
+      steps[c]  = comps[c].flag;
       any       = true;
     }
-    if (any)
+    if (any && mParameters.getVelocitySourceElementDelayFlag())
+      kwCheck(kw_element_source_rows_delayed(mParameters.getHipParameters().getContext(), rows, inputs, steps,
+                                             mVelocitySourceElements.ptr(), mVelocitySourceElements.entries(),
+                                             mVelocitySourceElements.entryDelays(),
+                                             static_cast<uint32_t>(mParameters.getVelocitySourceIndexSize()),
+                                             static_cast<uint32_t>(mParameters.getVelocitySourceElementCount()), timeIndex));
+    else if (any)
       kwCheck(kw_element_source_rows(mParameters.getHipParameters().getContext(), rows, inputs, mVelocitySourceElements.ptr(),
                                      mVelocitySourceElements.entries(),
                                      static_cast<uint32_t>(mParameters.getVelocitySourceIndexSize()),
@@ -814,7 +838,7 @@ void KSpaceFirstOrderSolver::addVelocitySource()
   }
   for (const Comp& c : comps)
   {
-    if (!(c.flag > timeIndex)) continue;
+    if (!(c.length > timeIndex)) continue;
     if (mParameters.getVelocitySourceMode() != Parameters::SourceMode::kAdditive)
     {
       SolverHipKernels::addVelocitySource(real(c.u), real(c.input), index(MI::kVelocitySourceIndex), seriesRow);
@@ -830,12 +854,23 @@ void KSpaceFirstOrderSolver::addVelocitySource()
 
 template<SD sd> void KSpaceFirstOrderSolver::addPressureSource()
 { // :2310-2332
-  if (mParameters.getPressureSourceFlag() > mParameters.getTimeIndex())
+  if (mParameters.getPressureSourceLength() > mParameters.getTimeIndex())
   {
     // weighted source: this step's row v(t) = W s(t) goes into the one-row series buffer, which the kernels below then
     // read as row 0 of a p_source_many = 1 source
     size_t seriesRow = mParameters.getTimeIndex();
-    if (mParameters.getPressureSourceElementFlag())
+    if (mParameters.getPressureSourceElementFlag() && mParameters.getPressureSourceElementDelayFlag())
+    { // per-entry delays: the one-component form of the delayed kernel, reading signal rows seriesRow - d_j
+      float* const       rows[3]   = {real(MI::kPressureSourceInput).getDeviceData(), nullptr, nullptr};
+      const float* const inputs[3] = {real(MI::kPressureSourceElementInput).getDeviceData(), nullptr, nullptr};
+      const uint64_t     steps[3]  = {mParameters.getPressureSourceFlag(), 0, 0};
+      kwCheck(kw_element_source_rows_delayed(mParameters.getHipParameters().getContext(), rows, inputs, steps,
+                                             mSourceElements.ptr(), mSourceElements.entries(), mSourceElements.entryDelays(),
+                                             static_cast<uint32_t>(mParameters.getPressureSourceIndexSize()),
+                                             static_cast<uint32_t>(mParameters.getPressureSourceElementCount()), seriesRow));
+      seriesRow = 0;
+    }
+    else if (mParameters.getPressureSourceElementFlag())
     {
       kwCheck(kw_element_source_row(mParameters.getHipParameters().getContext(), real(MI::kPressureSourceInput).getDeviceData(),
                                     real(MI::kPressureSourceElementInput).getDeviceData(), mSourceElements.ptr(),

@@ -79,6 +79,9 @@ bool pSourceWeighted(const P& p) { return pSource(p) && p.getPressureSourceEleme
 bool pSourceExpanded(const P& p) { return pSource(p) && !p.getPressureSourceElementFlag(); }
 bool sensorElements(const P& p) { return p.getStoreAnyElementsFlag(); }
 bool uWeighted(const P& p) { return p.getVelocitySourceElementFlag(); }
+bool pSourceDelayed(const P& p) { return pSourceWeighted(p) && p.getPressureSourceElementDelayFlag(); }
+bool uSourceDelayed(const P& p) { return uWeighted(p) && p.getVelocitySourceElementDelayFlag(); }
+bool sensorDelayed(const P& p) { return sensorElements(p) && p.getSensorElementDelayFlag(); }
 bool uxSourceWeighted(const P& p) { return uxSource(p) && uWeighted(p); }
 bool uySourceWeighted(const P& p) { return uySource(p) && uWeighted(p); }
 bool uzSourceWeighted(const P& p) { return uzSource(p) && uWeighted(p); }
@@ -222,6 +225,9 @@ const Row kSchema[] = {
   { MI::kVelocitySourceElementPtr, MT::kIndex, Extent::kByRule, dimsVelocityElementPtr, kFromFile, kVelocitySourceElementPtrName, uWeighted },
   { MI::kVelocitySourceElementIndex, MT::kIndex, Extent::kByRule, dimsVelocityElementEntries, kFromFile, kVelocitySourceElementIndexName, uWeighted },
   { MI::kVelocitySourceElementWeight, MT::kReal, Extent::kByRule, dimsVelocityElementEntries, kFromFile, kVelocitySourceElementWeightName, uWeighted },
+  { MI::kPressureSourceElementDelay, MT::kIndex, Extent::kByRule, dimsPressureElementEntries, kFromFile, kPressureSourceElementDelayName, pSourceDelayed },
+  { MI::kVelocitySourceElementDelay, MT::kIndex, Extent::kByRule, dimsVelocityElementEntries, kFromFile, kVelocitySourceElementDelayName, uSourceDelayed },
+  { MI::kSensorElementDelay, MT::kIndex, Extent::kByRule, dimsSensorElementEntries, kFromFile, kSensorElementDelayName, sensorDelayed },
   // non-staggered velocity (MatrixContainer.cpp:330-385); z lines and z_shift_neg_r keep their global length on a slab
   { MI::kTempHipFftShift, MT::kFft, Extent::kByRule, dimsShiftTemp, 0, "hipfft_shift_temp", shifted },
   GRID(kUxShifted, 0, "ux_shifted", shifted),

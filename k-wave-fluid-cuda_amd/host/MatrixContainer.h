@@ -44,7 +44,9 @@ class MatrixContainer
     kSensorElementPtr, kSensorElementIndex, kSensorElementWeight,
     // weighted velocity source: one CSR over u_source_index, element signals per component
     kVelocitySourceElementPtr, kVelocitySourceElementIndex, kVelocitySourceElementWeight,
-    kVelocityXSourceElementInput, kVelocityYSourceElementInput, kVelocityZSourceElementInput
+    kVelocityXSourceElementInput, kVelocityYSourceElementInput, kVelocityZSourceElementInput,
+    // per-entry time delays of the three CSRs (present with their datasets only)
+    kPressureSourceElementDelay, kVelocitySourceElementDelay, kSensorElementDelay
   };
 
   MatrixContainer() = default;

@@ -47,6 +47,13 @@ MatrixName kVelocitySourceElementPtrName = "u_source_element_ptr", kVelocitySour
 MatrixName kVelocityXSourceElementInputName = "ux_source_element_input",
            kVelocityYSourceElementInputName = "uy_source_element_input",
            kVelocityZSourceElementInputName = "uz_source_element_input";
+// per-entry time delays of the three CSRs (uint64, time steps, one value per entry; absent = all 0)
+MatrixName kPressureSourceElementDelayName = "p_source_element_delay", kVelocitySourceElementDelayName = "u_source_element_delay",
+           kSensorElementDelayName = "sensor_element_delay";
+// optional scalars beside the source delays: the largest delay of the whole array where this input holds a part of it (a
+// rank of a slab run), so that all parts keep the source active for the same steps
+MatrixName kPressureSourceElementDelayMaxName = "p_source_element_delay_max",
+           kVelocitySourceElementDelayMaxName = "u_source_element_delay_max";
 // output / state names
 MatrixName kPElementsName = "p_elements", kElementsSuffix = "_elements"; // ux_elements ..., ux_non_staggered_elements ...
 MatrixName kPName = "p", kPRmsName = "p_rms", kPMaxName = "p_max", kPMinName = "p_min", kPMaxAllName = "p_max_all",

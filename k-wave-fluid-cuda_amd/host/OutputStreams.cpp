@@ -448,11 +448,25 @@ void ElementOutputStream::create()
   mSize = mPtr.size() - 1;
   allocateMemory();
   // the CSR as loaded from the input (1-based grid indices); Parameters::init has checked it against the grid
-  mCsr.upload(mPtr.getHostData(), mSize, mIndex.getHostData(), mWeight.getHostData(), mIndex.size(), true);
+  if (mDelay)
+    mCsr.uploadDelayed(mPtr.getHostData(), mSize, mIndex.getHostData(), mWeight.getHostData(), mDelay->getHostData(),
+                       mIndex.size(), 1);
+  else mCsr.upload(mPtr.getHostData(), mSize, mIndex.getHostData(), mWeight.getHostData(), mIndex.size(), true);
 }
 void ElementOutputStream::sample()
 {
   const int b = mSampledSteps & 1;
+  if (mDelay)
+  {
+    float* const       outs[1]   = {mDeviceRaw[b]};
+    const float* const fields[1] = {mSourceMatrix.getDeviceData()};
+    float* const       rings[1]  = {mCsr.ring(0)};
+    kwCheck(kw_sample_elements_delayed(ctx(), 1, outs, fields, mCsr.groupPtr(), mCsr.entries(), mCsr.groupDelays(),
+                                       mCsr.elementGroupPtr(), static_cast<uint32_t>(mSize), mCsr.groups(), mCsr.nnz(),
+                                       mCsr.groupChunkPtr(), mCsr.groupChunks(), mCsr.partials(), rings, mCsr.ringRows(),
+                                       mSampledSteps));
+  }
+  else
   kwCheck(kw_sample_elements(ctx(), mDeviceRaw[b], mSourceMatrix.getDeviceData(), mCsr.ptr(), mCsr.entries(),
                              static_cast<uint32_t>(mSize), mCsr.nnz(), mCsr.chunkPtr(), mCsr.chunks(), mCsr.partials()));
   rawSampleTail(ctx(), mDeviceRaw[b], mPinned[b], mEvent[b], mSize);
@@ -467,20 +481,61 @@ void ElementOutputStream::flushRaw()
   mFlushedSteps++;
 }
 
+void ElementOutputStream::checkpointRing(std::vector<float>& out)
+{
+  out.clear();
+  if (!mDelay) return;
+  const size_t rows = ringOwner().ringRows();
+  std::vector<float> ring(rows * mSize);
+  if (!ring.empty()) kwCheck(kw_memcpy_d2h(ctx(), ring.data(), ringOwner().ring(ringField()), ring.size() * sizeof(float)));
+  for (size_t i = 0; i < rows; i++) // the row of step mSampledSteps first
+  {
+    const float* row = ring.data() + ((mSampledSteps + i) % rows) * mSize;
+    out.insert(out.end(), row, row + mSize);
+  }
+}
+void ElementOutputStream::checkpointState(std::vector<float>& state, size_t& sampledSteps)
+{
+  BaseOutputStream::checkpointState(state, sampledSteps);
+  std::vector<float> ring;
+  checkpointRing(ring);
+  state.insert(state.end(), ring.begin(), ring.end());
+}
+void ElementOutputStream::restoreState(const float* state, size_t n, size_t sampledSteps)
+{
+  if (!mDelay) return BaseOutputStream::restoreState(state, n, sampledSteps);
+  const size_t rows = ringOwner().ringRows(), floats = rows * mSize;
+  if (n < floats) throw std::invalid_argument("checkpoint of stream " + mName + " lacks the ring of its delayed sums");
+  BaseOutputStream::restoreState(state, n - floats, sampledSteps);
+  std::vector<float> ring(floats);
+  for (size_t i = 0; i < rows; i++)
+    std::copy_n(state + (n - floats) + i * mSize, mSize, ring.data() + ((sampledSteps + i) % rows) * mSize);
+  if (floats) kwCheck(kw_memcpy_h2d(ctx(), ringOwner().ring(ringField()), ring.data(), floats * sizeof(float)));
+}
+
 // ---- VelocityElementOutputStream ------------------------------------------------------------------------------------
 VelocityElementOutputStream::VelocityElementOutputStream(const std::string& name, const RealMatrix& source,
                                                          const IndexMatrix& ptr, const IndexMatrix& index,
-                                                         const RealMatrix& weight, VelocityElementOutputStream* leader)
-  : ElementOutputStream(name, source, ptr, index, weight), mLeader(leader)
+                                                         const RealMatrix& weight, VelocityElementOutputStream* leader,
+                                                         const IndexMatrix* delay)
+  : ElementOutputStream(name, source, ptr, index, weight, delay), mLeader(leader)
 {
   (leader ? leader : this)->mGroup.push_back(this);
+}
+size_t VelocityElementOutputStream::ringField() const
+{
+  const std::vector<VelocityElementOutputStream*>& group = (mLeader ? mLeader : this)->mGroup;
+  return static_cast<size_t>(std::find(group.begin(), group.end(), this) - group.begin());
 }
 void VelocityElementOutputStream::create()
 {
   mSize = mPtr.size() - 1;
   allocateMemory();
   // the group is complete by now (the container is set up before the input is read): partials for every field of it
-  if (mLeader == nullptr)
+  if (mLeader == nullptr && mDelay)
+    mCsr.uploadDelayed(mPtr.getHostData(), mSize, mIndex.getHostData(), mWeight.getHostData(), mDelay->getHostData(),
+                       mIndex.size(), mGroup.size());
+  else if (mLeader == nullptr)
     mCsr.upload(mPtr.getHostData(), mSize, mIndex.getHostData(), mWeight.getHostData(), mIndex.size(), true, mGroup.size());
 }
 void VelocityElementOutputStream::sample()
@@ -498,6 +553,16 @@ void VelocityElementOutputStream::sample()
     outs[f]   = mGroup[f]->mDeviceRaw[mGroup[f]->mSampledSteps & 1];
     fields[f] = mGroup[f]->mSourceMatrix.getDeviceData();
   }
+  if (mDelay)
+  { // the components still share one pass over the (regrouped) entries; each has its own ring
+    float* rings[3] = {nullptr, nullptr, nullptr};
+    for (uint32_t f = 0; f < nFields; f++) rings[f] = mCsr.ring(f);
+    kwCheck(kw_sample_elements_delayed(ctx(), nFields, outs, fields, mCsr.groupPtr(), mCsr.entries(), mCsr.groupDelays(),
+                                       mCsr.elementGroupPtr(), static_cast<uint32_t>(mSize), mCsr.groups(), mCsr.nnz(),
+                                       mCsr.groupChunkPtr(), mCsr.groupChunks(), mCsr.partials(), rings, mCsr.ringRows(),
+                                       mSampledSteps));
+  }
+  else
   kwCheck(kw_sample_elements_multi(ctx(), nFields, outs, fields, mCsr.ptr(), mCsr.entries(), static_cast<uint32_t>(mSize),
                                    mCsr.nnz(), mCsr.chunkPtr(), mCsr.chunks(), mCsr.partials()));
   for (VelocityElementOutputStream* s : mGroup)
@@ -640,11 +705,14 @@ void OutputStreamContainer::init(MatrixContainer& mc)
         mContainer[OI::kQTermC] = new PostProcessedOutputStream("Q_term_c", mc.getMatrix<RealMatrix>(MI::kP), RO::kQTermC, mask, false);
     }
   }
+  // sensor_element_delay, shared by every element stream; absent: today's path through kw_sample_elements(_multi)
+  const IndexMatrix* elementDelay = (params.getStoreAnyElementsFlag() && params.getSensorElementDelayFlag())
+                                      ? &mc.getMatrix<IndexMatrix>(MI::kSensorElementDelay) : nullptr;
   if (params.getStorePressureElementsFlag())
     mContainer[OI::kPressureElements] = new ElementOutputStream(kPElementsName, mc.getMatrix<RealMatrix>(MI::kP),
                                                                 mc.getMatrix<IndexMatrix>(MI::kSensorElementPtr),
                                                                 mc.getMatrix<IndexMatrix>(MI::kSensorElementIndex),
-                                                                mc.getMatrix<RealMatrix>(MI::kSensorElementWeight));
+                                                                mc.getMatrix<RealMatrix>(MI::kSensorElementWeight), elementDelay);
   // --u_elements / --u_non_staggered_elements: the x stream leads its group, y and (3-D) z follow (enum order = sampling order)
   auto velocityElements = [&](const std::string& infix, const MI (&fields)[3], const OI (&ids)[3]) {
     const std::string names[3] = {kUxName, kUyName, kUzName};
@@ -654,7 +722,7 @@ void OutputStreamContainer::init(MatrixContainer& mc)
       auto* s = new VelocityElementOutputStream(names[a] + infix + kElementsSuffix, mc.getMatrix<RealMatrix>(fields[a]),
                                                 mc.getMatrix<IndexMatrix>(MI::kSensorElementPtr),
                                                 mc.getMatrix<IndexMatrix>(MI::kSensorElementIndex),
-                                                mc.getMatrix<RealMatrix>(MI::kSensorElementWeight), leader);
+                                                mc.getMatrix<RealMatrix>(MI::kSensorElementWeight), leader, elementDelay);
       if (leader == nullptr) leader = s;
       mContainer[ids[a]] = s;
     }

@@ -75,6 +75,11 @@ class BaseOutputStream
   /// device accumulator (rms / max / min) — and the number of sampled steps.
   virtual void checkpointState(std::vector<float>& state, size_t& sampledSteps);
   virtual void restoreState(const float* state, size_t n, size_t sampledSteps);
+  /// State a series stream carries beside its rows (a delayed element stream: the ring of its sums still to come, the
+  /// next row to emit first).  checkpointState appends it to the series and restoreState takes it from there; where the
+  /// series lives in the output file it goes to the checkpoint file on its own, as "Temp_<name>".  Empty / 0 otherwise.
+  virtual void   checkpointRing(std::vector<float>& ring) { ring.clear(); }
+  virtual size_t ringFloats() const { return 0; }
 
  protected:
   void allocateMemory();
@@ -221,16 +226,28 @@ class CuboidOutputStream : public BaseOutputStream
 class ElementOutputStream : public BaseOutputStream
 {
  public:
+  /// delay: sensor_element_delay, or nullptr without it.  With it out[t][e] = sum_j w_j p^(t - d_j)[index_j] over the
+  /// sampled steps (kw_sample_elements_delayed): the entries are regrouped by delay and a ring of (largest delay + 1) rows of
+  /// E floats on the device holds the sums of the rows still to come.  The ring is part of the stream's state.
   ElementOutputStream(const std::string& name, const RealMatrix& source, const IndexMatrix& ptr, const IndexMatrix& index,
-                      const RealMatrix& weight)
-    : BaseOutputStream(name, source, ReduceOperator::kNone), mPtr(ptr), mIndex(index), mWeight(weight) {}
+                      const RealMatrix& weight, const IndexMatrix* delay = nullptr)
+    : BaseOutputStream(name, source, ReduceOperator::kNone), mPtr(ptr), mIndex(index), mWeight(weight), mDelay(delay) {}
   void create() override;
   void sample() override;
   void flushRaw() override;
+  /// a delayed stream appends its ring to the series, normalised so that row 0 is the next row to emit
+  void checkpointState(std::vector<float>& state, size_t& sampledSteps) override;
+  void restoreState(const float* state, size_t n, size_t sampledSteps) override;
+  void   checkpointRing(std::vector<float>& ring) override;
+  size_t ringFloats() const override { return mDelay ? static_cast<size_t>(ringOwner().ringRows()) * mSize : 0; }
  protected:
+  /// where this stream's ring lives: its own CSR, or for a velocity component the leader's, at the component's place
+  virtual const ElementCsr& ringOwner() const { return mCsr; }
+  virtual size_t            ringField() const { return 0; }
   const IndexMatrix& mPtr;
   const IndexMatrix& mIndex;
   const RealMatrix&  mWeight;
+  const IndexMatrix* mDelay;
   ElementCsr         mCsr;
 };
 
@@ -243,9 +260,13 @@ class VelocityElementOutputStream : public ElementOutputStream
  public:
   /// leader == nullptr: this stream leads; else it is sampled by `leader` (created before it, sampled before it)
   VelocityElementOutputStream(const std::string& name, const RealMatrix& source, const IndexMatrix& ptr,
-                              const IndexMatrix& index, const RealMatrix& weight, VelocityElementOutputStream* leader);
+                              const IndexMatrix& index, const RealMatrix& weight, VelocityElementOutputStream* leader,
+                              const IndexMatrix* delay = nullptr);
   void create() override;
   void sample() override;
+ protected:
+  const ElementCsr& ringOwner() const override { return (mLeader ? mLeader : this)->mCsr; }
+  size_t            ringField() const override;
  private:
   VelocityElementOutputStream*              mLeader;
   std::vector<VelocityElementOutputStream*> mGroup; // leader: itself and its followers, in component order

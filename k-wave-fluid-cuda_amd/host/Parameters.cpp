@@ -227,6 +227,8 @@ void Parameters::readElementArrays(const InputProvider& in)
   mPressureSourceElementCount = mPressureSourceElementNnz = 0;
   mVelocitySourceElementCount = mVelocitySourceElementNnz = 0;
   mSensorElementCount = mSensorElementNnz = 0;
+  mPressureSourceElementDelayed = mVelocitySourceElementDelayed = mSensorElementDelayed = false;
+  mPressureSourceElementMaxDelay = mVelocitySourceElementMaxDelay = mSensorElementMaxDelay = 0;
   const size_t gridPoints = mFullDimensionSizes.nElements();
   constexpr size_t kMax32 = 0xFFFFFFFFull;
   // ptr: rows + 1 non-decreasing 0-based offsets ending at nnz; columns: 1-based, 1 .. limit
@@ -258,6 +260,40 @@ void Parameters::readElementArrays(const InputProvider& in)
     return nnz;
   };
 
+  // the delays of a CSR's entries: one per entry, at most KW_ELEMENT_MAX_DELAY; sets the flag and the largest delay
+  auto checkDelays = [&](const std::string& delayName, const std::string& colName, size_t nnz, bool& delayed, size_t& maxDelay) {
+    if (!in.datasetExists(delayName)) return;
+    if (in.getDatasetSize(delayName) != nnz)
+      throw std::invalid_argument(delayName + ": has " + std::to_string(in.getDatasetSize(delayName)) + " entries, but " +
+                                  colName + " has " + std::to_string(nnz));
+    std::vector<size_t> d(nnz);
+    if (nnz > 0) in.readIndex(delayName, d.data(), d.size());
+    for (size_t j = 0; j < nnz; j++)
+    {
+      if (d[j] > KW_ELEMENT_MAX_DELAY)
+        throw std::invalid_argument(delayName + ": entry " + std::to_string(j) + " = " + std::to_string(d[j]) +
+                                    " lies above the largest delay " + std::to_string(KW_ELEMENT_MAX_DELAY));
+      maxDelay = std::max(maxDelay, d[j]);
+    }
+    delayed = true;
+  };
+  // the largest delay of the whole array, given where this input holds a part of its entries
+  auto readHorizon = [&](const std::string& maxName, const std::string& delayName, bool delayed, size_t& maxDelay) {
+    if (!in.datasetExists(maxName)) return;
+    if (!delayed) throw std::invalid_argument(maxName + ": present without " + delayName);
+    size_t horizon = 0;
+    in.readScalarValue(maxName, horizon);
+    if (horizon < maxDelay || horizon > KW_ELEMENT_MAX_DELAY)
+      throw std::invalid_argument(maxName + ": " + std::to_string(horizon) + " lies outside " + std::to_string(maxDelay) +
+                                  ".." + std::to_string(KW_ELEMENT_MAX_DELAY) + " (the largest delay of " + delayName + " and the limit)");
+    maxDelay = horizon;
+  };
+  // ... and a delay dataset whose CSR is not part of the input
+  auto refuseLoneDelays = [&](const std::string& delayName, const std::string& colName, const char* what) {
+    if (in.datasetExists(delayName))
+      throw std::invalid_argument(delayName + ": present without " + colName + " (the delays of a " + what + ")");
+  };
+
   // a weighted source's element signals: not beside the plain series, many = 1 if given, (1, flag, E) with E >= 1
   auto checkElementInput = [&](const std::string& elementName, const std::string& plainName, const std::string& manyName,
                                size_t flag, const std::string& flagName) {
@@ -287,7 +323,12 @@ void Parameters::readElementArrays(const InputProvider& in)
     mPressureSourceElementNnz = checkCsr(kPressureSourceElementPtrName, mPressureSourceIndexSize, kPressureSourceElementIndexName,
                                          kPressureSourceElementWeightName, elements, "weighted pressure source");
     mPressureSourceElementCount = elements;
+    checkDelays(kPressureSourceElementDelayName, kPressureSourceElementIndexName, mPressureSourceElementNnz,
+                mPressureSourceElementDelayed, mPressureSourceElementMaxDelay);
+    readHorizon(kPressureSourceElementDelayMaxName, kPressureSourceElementDelayName, mPressureSourceElementDelayed,
+                mPressureSourceElementMaxDelay);
   }
+  else refuseLoneDelays(kPressureSourceElementDelayName, kPressureSourceElementIndexName, "weighted pressure source");
 
   // velocity: the components share u_source_index and so one CSR; a component is active when its flag is above 0, and
   // the active ones are all weighted or all plain
@@ -328,7 +369,12 @@ void Parameters::readElementArrays(const InputProvider& in)
     mVelocitySourceElementNnz = checkCsr(kVelocitySourceElementPtrName, mVelocitySourceIndexSize, kVelocitySourceElementIndexName,
                                          kVelocitySourceElementWeightName, velocityElements, "weighted velocity source");
     mVelocitySourceElementCount = velocityElements;
+    checkDelays(kVelocitySourceElementDelayName, kVelocitySourceElementIndexName, mVelocitySourceElementNnz,
+                mVelocitySourceElementDelayed, mVelocitySourceElementMaxDelay);
+    readHorizon(kVelocitySourceElementDelayMaxName, kVelocitySourceElementDelayName, mVelocitySourceElementDelayed,
+                mVelocitySourceElementMaxDelay);
   }
+  else refuseLoneDelays(kVelocitySourceElementDelayName, kVelocitySourceElementIndexName, "weighted velocity source");
   if (getStoreAnyElementsFlag())
   {
     const char* flag = mOptions.storePressureElements ? "--p_elements" : mOptions.storeVelocityElements ? "--u_elements" : "--u_non_staggered_elements";
@@ -343,7 +389,11 @@ void Parameters::readElementArrays(const InputProvider& in)
     mSensorElementNnz   = checkCsr(kSensorElementPtrName, rows - 1, kSensorElementIndexName, kSensorElementWeightName,
                                    gridPoints, "weighted sensor");
     mSensorElementCount = rows - 1;
+    checkDelays(kSensorElementDelayName, kSensorElementIndexName, mSensorElementNnz, mSensorElementDelayed,
+                mSensorElementMaxDelay);
   }
+  else if (!in.datasetExists(kSensorElementIndexName))
+    refuseLoneDelays(kSensorElementDelayName, kSensorElementIndexName, "weighted sensor");
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

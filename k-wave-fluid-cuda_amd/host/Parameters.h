@@ -6,6 +6,7 @@
 // which replaces Parameters/CudaParameters.{h,cpp}.
 #ifndef KW_HOST_PARAMETERS_H
 #define KW_HOST_PARAMETERS_H
+#include <algorithm>
 #include <cstddef>
 #include <memory>
 #include <string>
@@ -217,6 +218,19 @@ class Parameters
   bool   getVelocitySourceElementFlag() const { return mVelocitySourceElementCount != 0; }
   size_t getVelocitySourceElementCount() const { return mVelocitySourceElementCount; }
   size_t getVelocitySourceElementNnz() const { return mVelocitySourceElementNnz; }
+  /// per-entry time delays (p_source_element_delay / u_source_element_delay / sensor_element_delay present): the flag
+  /// and the largest delay, at most KW_ELEMENT_MAX_DELAY.  A delayed source acts while t < flag + its largest delay
+  /// (capped by Nt): every decision on a source's activity takes these lengths, which without delays are the flags.
+  bool   getPressureSourceElementDelayFlag() const { return mPressureSourceElementDelayed; }
+  bool   getVelocitySourceElementDelayFlag() const { return mVelocitySourceElementDelayed; }
+  bool   getSensorElementDelayFlag() const { return mSensorElementDelayed; }
+  size_t getPressureSourceElementMaxDelay() const { return mPressureSourceElementMaxDelay; }
+  size_t getVelocitySourceElementMaxDelay() const { return mVelocitySourceElementMaxDelay; }
+  size_t getSensorElementMaxDelay() const { return mSensorElementMaxDelay; }
+  size_t getPressureSourceLength() const { return sourceLength(mPressureSourceFlag, mPressureSourceElementDelayed, mPressureSourceElementMaxDelay); }
+  size_t getVelocityXSourceLength() const { return sourceLength(mVelocityXSourceFlag, mVelocitySourceElementDelayed, mVelocitySourceElementMaxDelay); }
+  size_t getVelocityYSourceLength() const { return sourceLength(mVelocityYSourceFlag, mVelocitySourceElementDelayed, mVelocitySourceElementMaxDelay); }
+  size_t getVelocityZSourceLength() const { return sourceLength(mVelocityZSourceFlag, mVelocitySourceElementDelayed, mVelocitySourceElementMaxDelay); }
   /// weighted sensor (--p_elements, --u_elements, --u_non_staggered_elements): E rows of sensor_element_* over the grid
   size_t getSensorElementCount() const { return mSensorElementCount; }
   size_t getSensorElementNnz() const { return mSensorElementNnz; }
@@ -305,5 +319,11 @@ class Parameters
   size_t mVelocitySourceElementCount = 0, mVelocitySourceElementNnz = 0;
   size_t mSensorElementCount = 0, mSensorElementNnz = 0;
   void   readElementArrays(const InputProvider& in);
+  bool   mPressureSourceElementDelayed = false, mVelocitySourceElementDelayed = false, mSensorElementDelayed = false;
+  size_t mPressureSourceElementMaxDelay = 0, mVelocitySourceElementMaxDelay = 0, mSensorElementMaxDelay = 0;
+  size_t sourceLength(size_t flag, bool delayed, size_t maxDelay) const
+  {
+    return (flag == 0 || !delayed) ? flag : std::min(mNt, flag + maxDelay);
+  }
 };
 #endif

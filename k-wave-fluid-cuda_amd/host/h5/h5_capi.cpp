@@ -396,6 +396,13 @@ void kwh_checkpoint_write_impl(kwh_solver* s, const std::string& path)
     std::vector<float> state;
     size_t steps = 0;
     st->checkpointState(state, steps); // raw: flushes what is still in flight; aggregates: the accumulator as it stands
+    // a delayed element stream: its series is in the output file, the ring of its sums still to come goes beside I_avg_c's
+    if (st->ringFloats() > 0)
+    {
+      std::vector<float> ring;
+      st->checkpointRing(ring);
+      f.writeMatrix("Temp_" + name, DimensionSizes(ring.size(), 1, 1), ring.data(), Hdf5File::MatrixDomainType::kReal);
+    }
     if (!isAggregate(op)) continue;
     if (op == RO::kIAvgC) f.writeMatrix("Temp_" + name, DimensionSizes(state.size(), 1, 1), state.data(), Hdf5File::MatrixDomainType::kReal);
     if (st->doNotSave()) continue;
@@ -492,7 +499,13 @@ void kwh_checkpoint_read_impl(kwh_solver* s, const std::string& path)
         if (!st->hasSink() && steps > 0)
           throw std::invalid_argument("the series of stream " + name + " is not in the output file: this run cannot be resumed from a "
                                       "checkpoint in the reference's layout");
-        st->restoreState(nullptr, 0, steps);
+        if (st->ringFloats() > 0)
+        { // the ring of a delayed element stream (all +0 before the first sampled step)
+          std::vector<float> ring(st->ringFloats(), 0.0f);
+          if (steps > 0) f.readCompleteDataset("Temp_" + name, ring.size(), ring.data());
+          st->restoreState(ring.data(), ring.size(), steps);
+        }
+        else st->restoreState(nullptr, 0, steps);
       }
       else if (isAggregate(op) && steps > 0)
       {
