@@ -691,6 +691,31 @@ KW_API kw_status kw_offgrid_ptr(kw_ctx* ctx, const kw_offgrid* h, uint64_t* out_
 KW_API kw_status kw_offgrid_entries(kw_ctx* ctx, const kw_offgrid* h, uint64_t* out_index, float* out_weight);
 KW_API kw_status kw_offgrid_free(kw_ctx* ctx, kw_offgrid* h);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Bioheat (new with this build; what k-Wave's kWaveDiffusion computes): the element-wise kernels of the explicit k-space
+ * time stepping of the Pennes equation  rho C dT/dt = div(K grad T) - rho_b C_b W_b (T - T_a) + Q  (csrc/kw_thermal.hip).
+ * The FFT stages are the entry points above driven with thermal operators (host/ThermalSolver.cpp):
+ * kw_fused_scale_source / kw_fused_initial_velocity / kw_fused_velocity_gradient, or kw_fft_r2c_3d / kw_fft_c2r_3d with
+ * kw_compute_source_gradient / _pressure_gradient / _initial_velocity / _velocity_gradient.
+ * n == 0 is KW_OK in both: nothing is launched and no pointer is looked at.
+ *
+ * kw_thermal_update: per point, with a = 1 / (rho C), P = rho_b C_b W_b a, in this fp32 order
+ *     s = d0                      (d1 == d2 == NULL: Laplacian form, d0 = Laplacian of T, diff_scale = K)
+ *       = (d0 + d1) + d2          (flux form: the three terms of div(K grad T), diff_scale = 1)
+ *     r = (diff_scale * a) * s;   r = fma(-P, T - T_a, r);   r = fma(a, Q, r)  [Q != NULL and heat_on != 0]
+ *     T = fma(dt, r, T)
+ *   then on the updated T:  cem43 += (dt / 60) * R^(43 - T),  R = 0.5 for T >= 43, 0.25 for 37 <= T < 43, no increment
+ *   below 37 (R^(43 - T) = exp2f(s (T - 43)), s = 1 or 2), and T_max = fmaxf(T_max, T) when T_max != NULL.
+ *   a / P / T_a: an array, or NULL with the scalar beside it (a_s / P_s / T_a_s).  16-byte loads and stores when every
+ *   pointer is 16-byte aligned (n % 4 tail element by element), element by element otherwise; at most CU count x 8 blocks
+ *   of 256 threads stride over the array.
+ * kw_thermal_dose: the dose increment alone, cem43[i] += (dt / 60) * R^(43 - T[i]), for callers that step T themselves.
+ * ---------------------------------------------------------------------------------------------------------------- */
+KW_API kw_status kw_thermal_update(kw_ctx* ctx, float* T, float* cem43, float* T_max, const float* d0, const float* d1,
+                                   const float* d2, float diff_scale, const float* a, float a_s, const float* P, float P_s,
+                                   const float* T_a, float T_a_s, const float* Q, float dt, int heat_on, uint64_t n);
+KW_API kw_status kw_thermal_dose(kw_ctx* ctx, float* cem43, const float* T, float dt, uint64_t n);
+
 #ifdef __cplusplus
 }
 #endif

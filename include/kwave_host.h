@@ -176,6 +176,49 @@ KWH_API int      kwh_stream_checkpoint(kwh_solver* s, const char* name, float* d
 KWH_API int      kwh_stream_restore(kwh_solver* s, const char* name, const float* src, uint64_t n_floats,
                                     uint64_t sampled_steps);
 
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Bioheat solver (new with this build; what k-Wave's kWaveDiffusion computes): explicit k-space time stepping of the
+ * Pennes equation  rho C dT/dt = div(K grad T) - rho_b C_b W_b (T - T_a) + Q  on a periodic 3-D grid (no PML), with the
+ * CEM43 thermal dose accumulated on the GPU — the consumer of the acoustic solver's Q_term / Q_term_c.  A thermal solver
+ * owns its own device context; acoustic and thermal solvers can share a process.  The scheme is in DESIGN.md.
+ * Datasets (float unless noted; every medium dataset is a scalar or an Nx * Ny * Nz array):
+ *   Nx Ny Nz (uint64), dx dy dz dt                  required; Nz == 1 (2-D) is refused
+ *   T0                                              initial temperature [degC]
+ *   thermal_conductivity, density, specific_heat    K [W/(m K)], rho [kg/m^3], C [J/(kg K)]; a scalar K selects the
+ *                                                   Laplacian form of the diffusion term, an array the flux form
+ *   thermal_conductivity_sgx / _sgy / _sgz          optional (all or none, arrays): K on the staggered grids; default: the
+ *                                                   mean of each point and its +1 neighbour, the last point its own value
+ *   blood_density, blood_specific_heat, blood_perfusion_rate, blood_ambient_temperature     all four or none, or
+ *   perfusion_coeff [1/s] with blood_ambient_temperature
+ *   Q                                               optional: volume rate of heat deposition [W/m^3]
+ *   diffusion_coeff_ref                             optional: reference diffusivity of the k-space correction (default
+ *                                                   max K / (rho C))
+ *   sensor_mask_index (uint64, 1-based)             optional: T at those points after every step, stream "T_raw"
+ * Of kwh_options the call reads device_idx, fused_kernels (1: the hand-written FFT pipeline where the grid is supported,
+ * rocFFT elsewhere; 0: rocFFT); slab_ranks > 1 is refused.  A refusal names the dataset.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct kwh_thermal kwh_thermal;
+KWH_API int      kwh_thermal_create(const kwh_dataset* datasets, size_t n_datasets, const kwh_options* options, kwh_thermal** out);
+KWH_API int      kwh_thermal_destroy(kwh_thermal* s);
+/* n_steps steps; heat_on == 0 leaves Q out (cooling) */
+KWH_API int      kwh_thermal_run(kwh_thermal* s, uint64_t n_steps, int heat_on);
+KWH_API uint64_t kwh_thermal_time_index(const kwh_thermal* s);
+/* "T", "cem43" [equivalent minutes at 43 degC], "T_max", "Q"; n = Nx * Ny * Nz (checked).  Setting "Q" on a solver created
+ * without one gives it a heat source.  The running maximum is optional: setting "T_max" (to the current T, say) switches
+ * it on, and from then on every step updates it; reading it before that is an error. */
+KWH_API int      kwh_thermal_get_matrix(kwh_thermal* s, const char* name, float* dst, uint64_t n);
+KWH_API int      kwh_thermal_set_matrix(kwh_thermal* s, const char* name, const float* src, uint64_t n);
+/* volume [m^3] of the points whose cem43 is at least threshold_minutes (240 is the usual lesion threshold) */
+KWH_API int      kwh_thermal_lesion_volume(kwh_thermal* s, float threshold_minutes, double* out_m3);
+/* "T_raw": steps x points floats; dst == NULL returns the sizes alone */
+KWH_API int      kwh_thermal_stream_read(kwh_thermal* s, const char* name, float* dst, uint64_t cap, uint64_t* size,
+                                         uint64_t* steps);
+/* "fused_pipeline": 1 on the hand-written FFT pipeline, 0 on the rocFFT path */
+KWH_API int      kwh_thermal_get_scalar(kwh_thermal* s, const char* name, float* out);
+/* the underlying kw_ctx* (include/kwave_hip.h) */
+KWH_API void*    kwh_thermal_context(kwh_thermal* s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -189,6 +189,9 @@ _SIG: Dict[str, list] = {
     "kw_offgrid_ptr": [_P, _P, _P],
     "kw_offgrid_entries": [_P, _P, _P, _P],
     "kw_offgrid_free": [_P, _P],
+    "kw_thermal_update": [_P, _P, _P, _P, _P, _P, _P, C.c_float, _P, C.c_float, _P, C.c_float, _P, C.c_float, _P, C.c_float,
+                          C.c_int, _U64],
+    "kw_thermal_dose": [_P, _P, _P, C.c_float, _U64],
 }
 
 ELEMENT_CHUNK = 1024  # KW_ELEMENT_CHUNK

@@ -10,6 +10,7 @@
 #include "HostSolverHandle.h"
 #include "MatrixNames.h"
 #include "KSpaceFirstOrderSolver.h"
+#include "ThermalSolver.h"
 #include "kwave_host.h"
 
 static thread_local std::string g_err;
@@ -85,6 +86,14 @@ void kwh_build_solver(kwh_solver& s, const InputProvider& fileInput, const Param
   catch (const std::exception& e) { g_err = e.what(); return 1; }                                                      \
   catch (...) { g_err = "unknown exception"; return 1; }                                                               \
   return 0;
+
+/// a thermal solver with the input it was created from
+struct kwh_thermal
+{
+  MemoryInput                    input;
+  ThermalParameters              params;
+  std::unique_ptr<ThermalSolver> solver;
+};
 
 extern "C" {
 
@@ -355,6 +364,96 @@ int kwh_unpack_complex_40b(const uint8_t* packed, uint64_t n, float* v, int32_t 
     v[2 * i]     = c.real();
     v[2 * i + 1] = c.imag();
   }
+  KWH_CATCH
+}
+
+// ---- bioheat solver --------------------------------------------------------------------------------------------------
+int kwh_thermal_create(const kwh_dataset* datasets, size_t n, const kwh_options* o, kwh_thermal** out)
+{
+  KWH_TRY
+  if (!datasets || !o || !out) throw std::invalid_argument("kwh_thermal_create: NULL argument");
+  *out = nullptr;
+  std::unique_ptr<kwh_thermal> s(new kwh_thermal());
+  for (size_t i = 0; i < n; i++)
+  {
+    const kwh_dataset& d = datasets[i];
+    s->input.add(d.name, d.data, d.dtype == 0 ? InputProvider::DataType::kFloat : InputProvider::DataType::kLong,
+                 DimensionSizes(d.nx, d.ny, d.nz));
+  }
+  ThermalOptions opt;
+  opt.deviceIdx    = o->device_idx;
+  opt.fusedKernels = o->fused_kernels != 0;
+  opt.slabRanks    = o->slab_ranks ? o->slab_ranks : 1;
+  s->params.init(s->input, opt);
+  s->solver.reset(new ThermalSolver(s->params));
+  *out = s.release();
+  KWH_CATCH
+}
+
+int kwh_thermal_destroy(kwh_thermal* s)
+{
+  KWH_TRY
+  delete s;
+  KWH_CATCH
+}
+
+int kwh_thermal_run(kwh_thermal* s, uint64_t n_steps, int heat_on)
+{
+  KWH_TRY
+  if (!s) throw std::invalid_argument("kwh_thermal_run: NULL solver");
+  s->solver->run(n_steps, heat_on != 0);
+  KWH_CATCH
+}
+
+uint64_t kwh_thermal_time_index(const kwh_thermal* s) { return s ? s->solver->timeIndex() : 0; }
+void*    kwh_thermal_context(kwh_thermal* s) { return s ? s->solver->context() : nullptr; }
+
+int kwh_thermal_get_matrix(kwh_thermal* s, const char* name, float* dst, uint64_t n)
+{
+  KWH_TRY
+  if (!s || !name || !dst) throw std::invalid_argument("kwh_thermal_get_matrix: NULL argument");
+  s->solver->getMatrix(name, dst, n);
+  KWH_CATCH
+}
+
+int kwh_thermal_set_matrix(kwh_thermal* s, const char* name, const float* src, uint64_t n)
+{
+  KWH_TRY
+  if (!s || !name || !src) throw std::invalid_argument("kwh_thermal_set_matrix: NULL argument");
+  s->solver->setMatrix(name, src, n);
+  KWH_CATCH
+}
+
+int kwh_thermal_lesion_volume(kwh_thermal* s, float threshold_minutes, double* out_m3)
+{
+  KWH_TRY
+  if (!s || !out_m3) throw std::invalid_argument("kwh_thermal_lesion_volume: NULL argument");
+  *out_m3 = s->solver->lesionVolume(threshold_minutes);
+  KWH_CATCH
+}
+
+int kwh_thermal_stream_read(kwh_thermal* s, const char* name, float* dst, uint64_t cap, uint64_t* size, uint64_t* steps)
+{
+  KWH_TRY
+  if (!s || !name) throw std::invalid_argument("kwh_thermal_stream_read: NULL argument");
+  const std::vector<float>& series = s->solver->series(name);
+  const size_t ns = s->solver->sensorSize();
+  if (size) *size = ns;
+  if (steps) *steps = series.size() / ns;
+  if (dst != nullptr)
+  {
+    if (cap < series.size()) throw std::invalid_argument(std::string("kwh_thermal_stream_read: buffer too small for ") + name);
+    std::memcpy(dst, series.data(), series.size() * sizeof(float));
+  }
+  KWH_CATCH
+}
+
+int kwh_thermal_get_scalar(kwh_thermal* s, const char* name, float* out)
+{
+  KWH_TRY
+  if (!s || !name || !out) throw std::invalid_argument("kwh_thermal_get_scalar: NULL argument");
+  if (std::string(name) == "fused_pipeline") *out = s->solver->usesFusedPipeline() ? 1.f : 0.f;
+  else throw std::invalid_argument(std::string("unknown scalar ") + name);
   KWH_CATCH
 }
 }
