@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """bench.py — time-steps/s of the k-space first-order loop on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--size n] [--no-cpu] [--no-512] [--weak | --strong]
-                  [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--size n] [--dump-outputs DIR] [--weak | --strong]
+                  [--full [--no-cpu] [--no-512] [--no-p2p] [--profile-steps P]]
 
 N=1 workload: BASELINE config 3 — 256^3 heterogeneous (c0, rho0, BonA, alpha_coeff as arrays), power-law absorption +
 nonlinear term, p0 source, p_raw + p_max sampled on one xy plane (the manual's benchmark setup).
@@ -10,13 +10,18 @@ A "step" is one pass of the per-step loop (KSpaceFirstOrderSolver.cpp:885-935) o
 resident in HBM before the timed region.  The C++ host loop (libkwave_host) drives libkwave_hip; there is no CPU
 fallback.  One JSON line is printed by rank 0.
 
-N>1 (python -m torch.distributed.run ... bench.py --gpus N): the same 256^3 workload as Z-slabs over N GPUs (strong
-scaling: one curve with the N=1 line), with BASELINE config 4 (512^3: N GPUs vs one) in config.c4_512; see
-run_distributed().
+A plain run does what the headline figure needs and nothing else: set up, warm up, time the K steps, write the outputs
+when --dump-outputs is given, print the line ("roofline" then holds the whole-step figure, which takes no run of its
+own).  --full adds every other measurement to the same line, each after the timed steps: the per-kernel pass and the
+copy-bandwidth probe behind "roofline", the 512^3 points, the P2P leg at N>1 and "cpu_baseline".
 
-Extra objects: "roofline" (dominant kernel: algorithmic bytes per launch / HIP-event duration, vs the 8 TB/s HBM spec
-peak, with this box's measured copy bandwidth beside it; "step" carries the whole-step figure with B_alg of SURVEY.md
-§8d) and "cpu_baseline" (the CPU oracle on the host cores for a bounded number of steps of the same workload).
+N>1 (python -m torch.distributed.run ... bench.py --gpus N): the same 256^3 workload as Z-slabs over N GPUs (strong
+scaling: one curve with the N=1 line); with --full, BASELINE config 4 (512^3: N GPUs vs one) in config.c4_512 and the
+P2P transport's figures in config.p2p; see run_distributed().
+
+Extra objects of --full at N=1: "roofline" (dominant kernel: algorithmic bytes per launch / HIP-event duration, vs the
+8 TB/s HBM spec peak, with the device's measured copy bandwidth beside it; "step" carries the whole-step figure with
+B_alg of SURVEY.md §8d) and "cpu_baseline" (the CPU oracle on the host cores for a bounded number of steps of the same workload).
 """
 from __future__ import annotations
 
@@ -235,17 +240,17 @@ def run_distributed(args):
     """N>1: one process per GPU (torch.distributed.run), Z-slab decomposition, one all-to-all transpose per 3-D FFT.
 
     Default = strong scaling on the metric's own grid: `value` = time-steps/s of the 256^3 config-3 workload on N GPUs
-    (same grid, unit and workload as the N=1 line, so the per-N values form one curve).  BASELINE config 4 rides along
-    in config.c4_512: time-steps/s of the 512^3 grid on the same N GPUs, on one GPU (rank 0 alone, same run) and their
-    ratio (north_star: >= 3.5x at 8 GPUs).  --weak: every GPU owns 256^3 voxels instead (N=8 is the 512^3 grid),
-    value = N x global time-steps/s.  --strong --size n: one fixed n^3 grid only.
+    (same grid, unit and workload as the N=1 line, so the per-N values form one curve).  The other legs need --full.
+    BASELINE config 4 rides along in config.c4_512: time-steps/s of the 512^3 grid on the same N GPUs, on one GPU
+    (rank 0 alone, same run) and their ratio (north_star: >= 3.5x at 8 GPUs).  --weak: every GPU owns 256^3 voxels
+    instead (N=8 is the 512^3 grid), value = N x global time-steps/s.  --strong --size n: one fixed n^3 grid only.
 
     The data path is the device library's own RCCL exchange (--exchange native: kw_comm_init, ncclSend/ncclRecv groups
     on a communication stream); the process group (gloo) only carries the communicator id, the barriers and the
-    max-over-ranks of the timings.  The same grids are then timed over the library's device-initiated transport
-    (kw_comm_init_p2p: mapped peer buffers, one store kernel per exchange) and reported beside it in config.p2p — a
-    failure there is reported, not fatal.  --exchange p2p: that transport only (ranks may share a GPU: rehearsal on a
-    one-GPU box).  --exchange torch: torch.distributed.all_to_all_single as a callback (nccl group)."""
+    max-over-ranks of the timings.  With --full the same grids are then timed over the library's device-initiated
+    transport (kw_comm_init_p2p: mapped peer buffers, one store kernel per exchange) and reported beside it in
+    config.p2p — a failure there is reported, not fatal.  --exchange p2p: that transport only (ranks may share a GPU:
+    rehearsal on one GPU).  --exchange torch: torch.distributed.all_to_all_single as a callback (nccl group)."""
     # the process-group and RCCL libraries print banners on stdout: everything but the result line goes to stderr
     sys.stdout.flush()
     result_fd = os.dup(1)
@@ -361,7 +366,7 @@ def run_distributed(args):
         grid = (args.size or 512,) * 3
     else:
         grid = (args.size or 256,) * 3
-        if not args.no_512 and world > 1:
+        if args.full and not args.no_512 and world > 1:
             k5, w5 = max(5, K // 5), max(2, W // 5)
             one = single_gpu_rate(512, k5, w5) if rank == 0 else 0.0
             dist.barrier()
@@ -377,7 +382,7 @@ def run_distributed(args):
     global_rate = K / sec
     # the same grids over the device-initiated transport, beside the default's numbers (never instead of them)
     p2p = None
-    if state["exchange"] == "native" and state["fallback"] is None and not args.no_p2p:
+    if args.full and state["exchange"] == "native" and state["fallback"] is None and not args.no_p2p:
         p2p = {"transport": "kw_comm_init_p2p: mapped peer buffers (hipIpc), one store kernel per exchange on the communication stream"}
         try:
             sec_p, ex_p = slab_run(grid, K, W, exchange="p2p")
@@ -424,19 +429,73 @@ def run_distributed(args):
     return 0
 
 
+def kernel_roofline(sim, args, n, K, P, ms):
+    """--full at N=1: the "roofline" object.  P more steps with HIP events around every entry point and kernel, the
+    dominant kernel's algorithmic bytes per launch over its duration, the committed PMC traffic of this build of the
+    kernels when there is one, and the device's copy bandwidth beside the spec peak."""
+    from kwave_amd import capi
+    hip = capi.load()
+    capi.check(hip.kw_profile_enable(sim.ctx, 1))
+    sim.run(P)
+    prof = capi.profile_collect(sim.ctx)
+    capi.check(hip.kw_profile_enable(sim.ctx, 0))
+    b_step, per = alg_bytes(n)
+    table = {}
+    for name, (calls, total_ms) in prof.items():
+        avg = total_ms / max(calls, 1)
+        ab = per.get(name)
+        table[name] = {"calls_per_step": calls / P, "avg_ms": round(avg, 4),
+                       "ms_per_step": round(total_ms / P, 4),
+                       "alg_gbs": round(ab / (avg * 1e-3) / 1e9, 1) if ab else None}
+        if name.startswith("fused_"):  # stage boundaries of the pipeline differ from the reference's (chained passes)
+            table[name]["alg_gbs"] = None
+    # dominant GPU kernel (fused pipeline: the "k_*" records; granular path: one kernel per entry point)
+    kernels = [k for k in table if per.get(k) and (k.startswith("k_") or args.granular)]
+    if not kernels:  # a grid the fused pipeline does not take (kw_fused_supported): the run used the rocFFT path
+        kernels = [k for k in table if per.get(k)]
+    dom = max(kernels, key=lambda k: table[k]["ms_per_step"])
+    achieved = per[dom] / (table[dom]["avg_ms"] * 1e-3) / 1e9
+    traffic, traffic_src, step_traffic = None, None, None
+    pmc_file, pmc = pmc_traffic_for_this_build()
+    if n == 256 and not args.granular and pmc is not None:
+        traffic = pmc.get("traffic_bytes_per_bench_kernel", {}).get(dom)
+        traffic_src = (f"profiles/{os.path.basename(pmc_file)}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) of "
+                       "this workload with this build of the kernels (source hash checked), 128-B read requests counted x2 "
+                       "(gfx950 correction, checked on probe kernels of known size)")
+        step_traffic = pmc.get("traffic_bytes_per_step")
+    # measured copy bandwidth of the device beside the spec peak (1 GiB buffers: four times the Infinity Cache)
+    copy_gbs = C.c_double()
+    capi.check(hip.kw_measure_copy_bandwidth(sim.ctx, 1 << 30, 10, C.byref(copy_gbs)))
+    return {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+            "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+            "measured_copy_gbs": round(copy_gbs.value, 1),
+            "frac_of_measured_copy": round(achieved / copy_gbs.value, 4),
+            "traffic_source": traffic_src,
+            "alg_bytes_per_launch": per[dom], "avg_ms": table[dom]["avg_ms"],
+            "step": {"alg_bytes": b_step, "achieved": round(b_step / (ms * 1e-3 / K) / 1e9, 1),
+                     "frac": round(b_step / (ms * 1e-3 / K) / 1e9 / HBM_PEAK_GBS, 4),
+                     "frac_of_measured_copy": round(b_step / (ms * 1e-3 / K) / 1e9 / copy_gbs.value, 4),
+                     "traffic": step_traffic},
+            "entry_points": {k: v for k, v in table.items() if not k.startswith("k_")},
+            "kernels": {k: v for k, v in table.items() if k.startswith("k_")}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--size", type=int, default=0, help="grid size n (n^3); default 256 at N=1, 512 at N>1")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--profile-steps", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline figure does not need: per-kernel and "
+                         "roofline figures, copy bandwidth, the 512^3 points, the P2P leg (N>1), the CPU baseline")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
+    ap.add_argument("--profile-steps", type=int, default=5, help="--full: steps of the per-kernel pass")
     ap.add_argument("--granular", action="store_true", help="one launch per reference kernel instead of fused kernels")
     ap.add_argument("--strong", action="store_true", help="N>1: one fixed --size^3 grid (default 512) only")
     ap.add_argument("--weak", action="store_true", help="N>1: 256^3 voxels per GPU (256x256x512 / 256x512x512 / 512^3)")
-    ap.add_argument("--no-512", action="store_true", help="N>1: skip the config-4 (512^3) block of the line")
-    ap.add_argument("--no-p2p", action="store_true", help="N>1: skip the P2P-transport leg of the line")
+    ap.add_argument("--no-512", action="store_true", help="--full: skip the config-4 (512^3) block of the line")
+    ap.add_argument("--no-p2p", action="store_true", help="--full, N>1: skip the P2P-transport leg of the line")
     ap.add_argument("--rccl-library", default=None, help="N>1: library the device layer's RCCL binding loads (default search otherwise)")
     ap.add_argument("--exchange", default=os.environ.get("KW_EXCHANGE", "native"), choices=("native", "p2p", "torch"),
                     help="N>1 data path: the device library's own RCCL exchange, or torch.distributed as a callback")
@@ -472,6 +531,7 @@ def main():
     n = args.size or 256
     K, W, P = args.steps, args.warmup, args.profile_steps
     t_gen = time.time()
+    # nt counts --full's P steps in a plain run too: the inputs of the timed steps do not depend on the mode
     pr = synthetic.make_problem(n, heterogeneous=True, nonlinear=True, absorbing=True, source="p0", nt=W + K + P + 8)
     t_gen = time.time() - t_gen
     sim = HostSolver(pr, p_raw=1, p_max=1, fused_kernels=not args.granular)
@@ -484,57 +544,20 @@ def main():
     steps_per_s = K / (ms * 1e-3)
     dumped = dump_outputs(sim, args.dump_outputs) if args.dump_outputs else None
 
-    # --- per entry point timing (live, same process, same workload) ---
+    if args.full:
+        roofline = kernel_roofline(sim, args, n, K, P, ms)
+    else:  # the whole step's algorithmic bytes over the timed steps: no run of its own
+        b_step, _ = alg_bytes(n)
+        achieved = b_step / (ms * 1e-3 / K) / 1e9
+        roofline = {"bound": "hbm", "kernel": "step", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None, "alg_bytes": b_step}
     hip = capi.load()
-    capi.check(hip.kw_profile_enable(sim.ctx, 1))
-    sim.run(P)
-    prof = capi.profile_collect(sim.ctx)
-    capi.check(hip.kw_profile_enable(sim.ctx, 0))
-    b_step, per = alg_bytes(n)
-    table = {}
-    for name, (calls, total_ms) in prof.items():
-        avg = total_ms / max(calls, 1)
-        ab = per.get(name)
-        table[name] = {"calls_per_step": calls / P, "avg_ms": round(avg, 4),
-                       "ms_per_step": round(total_ms / P, 4),
-                       "alg_gbs": round(ab / (avg * 1e-3) / 1e9, 1) if ab else None}
-        if name.startswith("fused_"):  # stage boundaries of the pipeline differ from the reference's (chained passes)
-            table[name]["alg_gbs"] = None
-    # dominant GPU kernel (fused pipeline: the "k_*" records; granular path: one kernel per entry point)
-    kernels = [k for k in table if per.get(k) and (k.startswith("k_") or args.granular)]
-    if not kernels:  # a grid the fused pipeline does not take (kw_fused_supported): the run used the rocFFT path
-        kernels = [k for k in table if per.get(k)]
-    dom = max(kernels, key=lambda k: table[k]["ms_per_step"])
-    achieved = per[dom] / (table[dom]["avg_ms"] * 1e-3) / 1e9
-    traffic, traffic_src, step_traffic = None, None, None
-    pmc_file, pmc = pmc_traffic_for_this_build()
-    if n == 256 and not args.granular and pmc is not None:
-        traffic = pmc.get("traffic_bytes_per_bench_kernel", {}).get(dom)
-        traffic_src = (f"profiles/{os.path.basename(pmc_file)}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) of "
-                       "this workload with this build of the kernels (source hash checked), 128-B read requests counted x2 "
-                       "(gfx950 correction, checked on probe kernels of known size)")
-        step_traffic = pmc.get("traffic_bytes_per_step")
-    # measured copy bandwidth of this box beside the spec peak (1 GiB buffers: four times the Infinity Cache)
-    copy_gbs = C.c_double()
-    capi.check(hip.kw_measure_copy_bandwidth(sim.ctx, 1 << 30, 10, C.byref(copy_gbs)))
-    roofline = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                "measured_copy_gbs": round(copy_gbs.value, 1),
-                "frac_of_measured_copy": round(achieved / copy_gbs.value, 4),
-                "traffic_source": traffic_src,
-                "alg_bytes_per_launch": per[dom], "avg_ms": table[dom]["avg_ms"],
-                "step": {"alg_bytes": b_step, "achieved": round(b_step / (ms * 1e-3 / K) / 1e9, 1),
-                         "frac": round(b_step / (ms * 1e-3 / K) / 1e9 / HBM_PEAK_GBS, 4),
-                         "frac_of_measured_copy": round(b_step / (ms * 1e-3 / K) / 1e9 / copy_gbs.value, 4),
-                         "traffic": step_traffic},
-                "entry_points": {k: v for k, v in table.items() if not k.startswith("k_")},
-                "kernels": {k: v for k, v in table.items() if k.startswith("k_")}}
     info = capi.DeviceInfo()
     capi.check(hip.kw_device_info_get(sim.ctx, info))
     sim.close()
     del sim
     c4_one = None
-    if n == 256 and not args.granular and not args.no_512:
+    if args.full and n == 256 and not args.granular and not args.no_512:
         # BASELINE config 4's single-GPU point (the denominator of the >= 3.5x at 8 GPUs target), same process
         k5 = max(5, K // 5)
         c4_one = {"grid": [512, 512, 512], "steps": k5, "n_gpus": 1, "steps_per_s": round(single_gpu_rate(512, k5, 2), 3)}
@@ -556,7 +579,7 @@ def main():
         out["config"]["c4_512"] = c4_one
     if dumped is not None:
         out["dumped_outputs"] = {"dir": args.dump_outputs, "files": [f + ".npy" for f in dumped], "time_index": W + K}
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(pr, n)
     print(json.dumps(out))
     return 0

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Device-copy bandwidth of the box as bench.py reports it (kw_measure_copy_bandwidth: best of three float4 copy
+"""Device-copy bandwidth as bench.py --full reports it (kw_measure_copy_bandwidth: best of three float4 copy
 shapes) at a few buffer sizes:   python tools/copy_bandwidth.py"""
 import ctypes as C
 import os
