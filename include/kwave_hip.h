@@ -716,6 +716,51 @@ KW_API kw_status kw_thermal_update(kw_ctx* ctx, float* T, float* cem43, float* T
                                    const float* T_a, float T_a_s, const float* Q, float dt, int heat_on, uint64_t n);
 KW_API kw_status kw_thermal_dose(kw_ctx* ctx, float* cem43, const float* T, float dt, uint64_t n);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * CW field propagator (new with this build; what k-Wave's acousticFieldPropagator computes): the steady-state pressure
+ * of a continuous-wave source S(x) exp(i w t) in a homogeneous lossless medium, as the exact k-space solution of
+ * p_tt - c0^2 lap(p) = S exp(i w t), p = p_t = 0 at t = 0, on a periodic grid at one late time T (csrc/kw_cw.hip,
+ * host/CwPropagator.cpp).  Per bin, a = c0 |k|, d = a - w:
+ *     G(a) = i [ sin(a T)/a - T exp(i (a + w) T/2) sinc(d T/2) ] / (a + w),   sinc(x) = sin(x)/x, sin(a T)/a -> T at a = 0
+ * (the textbook (exp(i w T) - cos(a T) - i (w/a) sin(a T)) / (a^2 - w^2), regular at a = w and a = 0), and the complex
+ * amplitude P(x) = p(x, T) exp(-i w T) = ifftn(G exp(-i w T) fftn(S)).  The field is carried as two real arrays, S = re +
+ * i im: G depends on |k| only, so  Pr^ = Gr Sr^ - Gi Si^,  Pi^ = Gi Sr^ + Gr Si^  are Hermitian half-spectra.
+ *
+ * kw_cw_operator: g_re / g_im [nz][ny][nx/2+1] (the grid of kw_set_constants) <- Re / Im of G exp(-i w T) / (nx ny nz),
+ *   evaluated in float64 on the device and rounded once (a T reaches thousands of radians).  w = 2 pi f0 [rad/s], T [s],
+ *   dk? = 2 pi / (n? d?) [rad/m]; every scalar must be positive.  kw_fused_import_reduced moves each array into the
+ *   pipeline's layout for kw_fused_cw_pair; kw_cw_mix reads them as they are.
+ * kw_fused_cw_pair: re, im [nz][ny][nx], in place: (re + i im) <- ifftn((g_re + i g_im) fftn(re + i im)); the operators
+ *   (imported) carry the 1/N.  x-forward and y-forward of both arrays, one z-pass that transforms both, mixes them in
+ *   registers and transforms both back, y-inverse, x-inverse.  Single GPU, 3-D: KW_ERR_INVALID in slab mode or for Nz == 1.
+ * kw_cw_mix: the same mix on two spectra of kw_fft_r2c_3d (interleaved complex, n_bins bins each), in place, for
+ *   kw_fft_r2c_3d x 2 -> kw_cw_mix -> kw_fft_c2r_3d x 2 (grids off the fast path).  Per bin and per component (real and
+ *   imaginary alike), in this fp32 order without contraction into fma:
+ *     re' = (g_re * re) - (g_im * im),     im' = (g_im * re) + (g_re * im)
+ * kw_cw_embed: ex_re / ex_im [ez][ey][ex] <- 0, except the corner [0, nz) x [0, ny) x [0, nx), which receives the source
+ *   a, b [nz][ny][nx]: parts != 0: S = a + i b; parts == 0: S = a (cos b + i sin b) (amplitude, phase [rad]) — times the
+ *   complex source scale: re = (Sr * scale_re) - (Si * scale_im), im = (Sr * scale_im) + (Si * scale_re), no contraction;
+ *   with scale = (1, 0) the values are stored as they are (copies and zero fill are exact).
+ * kw_cw_extract: the corner of the expanded pair cropped back to [nz][ny][nx]; each output may be NULL: out_re, out_im
+ *   (copies), out_amp = sqrtf((re * re) + (im * im)), out_phase = atan2(im, re) evaluated in float64 and rounded once,
+ *   out_q = q * ((re * re) + (im * im)) with q per point, or NULL and q_scalar (plane wave: q = alpha / (rho0 c0), alpha
+ *   in Np/m, gives the volume rate of heat deposition).
+ * embed / extract: 16-byte accesses when ex and nx are multiples of 4 and every pointer is 16-byte aligned, element by
+ *   element otherwise; at most CU count x 8 blocks of 256 threads stride over the points.  A grid of 0 points (embed: of
+ *   the expanded grid, extract: of the domain) and kw_cw_mix with n_bins == 0 are KW_OK: nothing is launched and no
+ *   pointer is looked at.
+ * ---------------------------------------------------------------------------------------------------------------- */
+KW_API kw_status kw_cw_operator(kw_ctx* ctx, float* g_re, float* g_im, double c0, double w, double T, double dkx, double dky,
+                                double dkz);
+KW_API kw_status kw_fused_cw_pair(kw_ctx* ctx, float* re, float* im, const float* g_re_padded, const float* g_im_padded);
+KW_API kw_status kw_cw_mix(kw_ctx* ctx, float* spec_re, float* spec_im, const float* g_re, const float* g_im, uint64_t n_bins);
+KW_API kw_status kw_cw_embed(kw_ctx* ctx, float* ex_re, float* ex_im, const float* a, const float* b, int parts,
+                             float scale_re, float scale_im, uint32_t ex, uint32_t ey, uint32_t ez, uint32_t nx, uint32_t ny,
+                             uint32_t nz);
+KW_API kw_status kw_cw_extract(kw_ctx* ctx, const float* ex_re, const float* ex_im, uint32_t ex, uint32_t ey, uint32_t ez,
+                               uint32_t nx, uint32_t ny, uint32_t nz, float* out_re, float* out_im, float* out_amp,
+                               float* out_phase, float* out_q, const float* q, float q_scalar);
+
 #ifdef __cplusplus
 }
 #endif

@@ -219,6 +219,56 @@ KWH_API int      kwh_thermal_get_scalar(kwh_thermal* s, const char* name, float*
 /* the underlying kw_ctx* (include/kwave_hip.h) */
 KWH_API void*    kwh_thermal_context(kwh_thermal* s);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * CW field propagator (new with this build; what k-Wave's acousticFieldPropagator computes): the steady-state complex
+ * pressure amplitude P(x) of a continuous-wave source S(x) exp(i w t), w = 2 pi f0, in a homogeneous lossless medium, from
+ * ONE forward and one inverse 3-D FFT of the source on an expanded periodic grid (kwave_hip.h "CW field propagator",
+ * DESIGN.md) — instead of thousands of time steps.  A propagator owns its own device context and builds its operator
+ * once; every run reuses it.
+ *   T (0 = default): the evaluation time, by default the domain diagonal sqrt(sum (N_a d_a)^2) / c0.
+ *   E (all 0 = default): the expanded grid; every side at least N_a + ceil(c0 T / d_a), so that no periodic image reaches
+ *   the domain by T.  Default: the smallest fast-path line length of the fused pipeline at or above that; when an axis has
+ *   none (above 1024) or with fused_kernels off, the smallest even number on every axis, which runs on rocFFT.  Given
+ *   sides must be even and not below the rule.
+ *   source scale: a complex factor on the source; (0, 0) = 1.  source_scale_kwave = 1 sets 2 i w c0 / dx, with which an
+ *   amplitude p_s gives the steady state of the time loop's additive pressure source p_s sin(w t).
+ * Refused, naming the parameter: Nx Ny Nz (0; Nz == 1: 2-D is not built), dx dy dz, c0, f0 (not positive, or above the
+ * grid's Nyquist frequency c0 / (2 max d)), T, Ex Ey Ez (missing, odd, below the rule), E (2^32 points or more).
+ * Of kwh_options the calls read device_idx and fused_kernels.  kwh_cw_plan validates and completes T and E without a
+ * device; kwh_cw_create does the same and then needs one (its failure there is the device library's status, e.g.
+ * KW_ERR_NO_DEVICE = 6).  Not built: absorbing or heterogeneous media, 2-D, Z-slabs, HDF5 files and the command line.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct kwh_cw kwh_cw;
+typedef struct kwh_cw_config
+{
+  uint64_t nx, ny, nz;      /* domain */
+  double   dx, dy, dz;      /* [m] */
+  double   c0, f0;          /* [m/s], [Hz] */
+  double   t;               /* [s]; 0 = default */
+  uint64_t ex, ey, ez;      /* expanded grid; 0 0 0 = default */
+  double   source_scale_re, source_scale_im; /* 0 0 = 1 */
+  int32_t  source_scale_kwave;
+  int32_t  pad_;
+} kwh_cw_config;
+KWH_API int      kwh_cw_plan(const kwh_cw_config* config, const kwh_options* options, double* out_t, uint64_t out_expanded[3],
+                             int32_t* out_fast_path);
+KWH_API int      kwh_cw_create(const kwh_cw_config* config, const kwh_options* options, kwh_cw** out);
+KWH_API int      kwh_cw_destroy(kwh_cw* s);
+/* a, b: Nx * Ny * Nz floats each on the host ([Nz][Ny][Nx]); parts != 0: Re S, Im S; parts == 0: amplitude, phase [rad] */
+KWH_API int      kwh_cw_run(kwh_cw* s, const float* a, const float* b, int parts);
+/* the last run's result on the domain: "re", "im", "amplitude", "phase"; n = Nx * Ny * Nz (checked) */
+KWH_API int      kwh_cw_get(kwh_cw* s, const char* name, float* dst, uint64_t n);
+/* Q = q |P|^2 on the domain: q per point (n floats), or NULL and q_scalar.  Plane wave: q = alpha / (rho0 c0), alpha in
+ * Np/m, gives the volume rate of heat deposition [W/m^3] that kwh_thermal_* takes as "Q". */
+KWH_API int      kwh_cw_heat(kwh_cw* s, const float* q, float q_scalar, float* dst, uint64_t n);
+/* the FFT round trip alone on the expanded pair as it stands (timing: tools/bench_cw.py) */
+KWH_API int      kwh_cw_propagate(kwh_cw* s);
+/* "fused_pipeline" (1 on the hand-written FFT pipeline, 0 on rocFFT), "t", "Ex", "Ey", "Ez", "runs",
+ * "source_scale_re", "source_scale_im" */
+KWH_API int      kwh_cw_get_scalar(kwh_cw* s, const char* name, double* out);
+/* the underlying kw_ctx* (include/kwave_hip.h) */
+KWH_API void*    kwh_cw_context(kwh_cw* s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -192,6 +192,11 @@ _SIG: Dict[str, list] = {
     "kw_thermal_update": [_P, _P, _P, _P, _P, _P, _P, C.c_float, _P, C.c_float, _P, C.c_float, _P, C.c_float, _P, C.c_float,
                           C.c_int, _U64],
     "kw_thermal_dose": [_P, _P, _P, C.c_float, _U64],
+    "kw_cw_operator": [_P, _P, _P] + [C.c_double] * 6,
+    "kw_fused_cw_pair": [_P, _P, _P, _P, _P],
+    "kw_cw_mix": [_P, _P, _P, _P, _P, _U64],
+    "kw_cw_embed": [_P, _P, _P, _P, _P, C.c_int, C.c_float, C.c_float] + [C.c_uint32] * 6,
+    "kw_cw_extract": [_P, _P, _P] + [C.c_uint32] * 6 + [_P, _P, _P, _P, _P, _P, C.c_float],
 }
 
 ELEMENT_CHUNK = 1024  # KW_ELEMENT_CHUNK

@@ -168,6 +168,8 @@ kw_status xinv_other_tail(int epi, int chain, kw_ctx* ctx, int ncomp, const Xinv
 // whole-plane tiles (small grids, see k_xinv); with density-chain-short and other
 kw_status xinv_density_plane(int chain, int terms, kw_ctx* ctx, int ncomp, const XinvArgs& a, uint32_t plane0, uint32_t nplanes);
 kw_status xinv_other_plane(int epi, int chain, kw_ctx* ctx, int ncomp, const XinvArgs& a, uint32_t plane0, uint32_t nplanes);
+// the z-pass of kw_fused_cw_pair: two spectra forward along z, the 2x2 mix with two real operators, both inverses (kw_cw.hip)
+kw_status zfused_pair(kw_ctx* ctx, ZArgs a);
 // the tuning probes of kw_fused_probe that launch no pipeline kernel (kw_fused_probe.hip)
 kw_status probe_patterns(kw_ctx* ctx, int which, const float* op);
 

@@ -1352,6 +1352,36 @@ kw_status kw_fused_scale_source(kw_ctx* ctx, float* scaled, const float* source_
   return KW_OK;
 }
 
+// CW field propagator (kw_cw.hip): the complex field re + i im through one 3-D round trip with the complex operator
+// G = g_re + i g_im (real, reduced, imported: a function of |k|), as two real transforms —
+//   re <- ifftn(g_re fftn(re) - g_im fftn(im)),   im <- ifftn(g_im fftn(re) + g_re fftn(im)),   in place;
+// the operators carry the 1/N.  kw_fused_scale_source's schedule with two arrays and the pair kernel as its z-pass.
+kw_status kw_fused_cw_pair(kw_ctx* ctx, float* re, float* im, const float* g_re_padded, const float* g_im_padded)
+{
+  KW_FUSED_READY(ctx);
+  KW_PROF(ctx, "fused_cw_pair");
+  KW_REQUIRE(re && im && g_re_padded && g_im_padded && re != im);
+  if (ctx->fused.slab || ctx->fused.two_d)
+  {
+    kw_set_error("kw_fused_cw_pair: single GPU and 3-D only (no Z-slabs, no Nz == 1)");
+    return KW_ERR_INVALID;
+  }
+  float2** S = ctx->fused.s;
+  const float* in2[2] = { re, im };
+  KW_TRY(forward_xy(ctx, 2, in2));
+  ZArgs z{};
+  for (int i = 0; i < 2; i++) { z.in[i] = S[i]; z.out[i] = S[i]; }
+  z.op[0] = g_re_padded;
+  z.op[1] = g_im_padded;
+  KW_TRY(zfused_pair(ctx, z));
+  KW_TRY(inverse_y(ctx, 2));
+  XinvArgs x{};
+  x.in[0] = S[0]; x.in[1] = S[1];
+  x.out[0] = re;  x.out[1] = im;
+  KW_TRY(launch_xinv<EPI_STORE>(ctx, 2, x));
+  return KW_OK;
+}
+
 // Pass-level probe for tuning (tools/probe_passes.py): launches ONE pass over the scratch arrays, no physics.
 //   0: y-pass forward on s[0] (in place)          1: the same line kernel along z (stride ny*P) on s[0]
 //   2: z-fused (forward, x sourceKappa-style multiply with op, inverse) on s[0]   3: y-pass on s[0..2] (3 arrays)

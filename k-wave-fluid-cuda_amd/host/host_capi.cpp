@@ -11,6 +11,7 @@
 #include "MatrixNames.h"
 #include "KSpaceFirstOrderSolver.h"
 #include "ThermalSolver.h"
+#include "CwPropagator.h"
 #include "kwave_host.h"
 
 static thread_local std::string g_err;
@@ -94,6 +95,31 @@ struct kwh_thermal
   ThermalParameters              params;
   std::unique_ptr<ThermalSolver> solver;
 };
+
+/// a CW propagator with its completed parameters
+struct kwh_cw
+{
+  CwParameters                  params;
+  std::unique_ptr<CwPropagator> propagator;
+};
+
+static CwParameters kwh_cw_parameters(const kwh_cw_config* c, const kwh_options* o)
+{
+  if (c->source_scale_kwave != 0 && (c->source_scale_re != 0.0 || c->source_scale_im != 0.0))
+    throw std::invalid_argument("source_scale: give source_scale_kwave or a factor, not both");
+  CwParameters p;
+  p.nx = c->nx; p.ny = c->ny; p.nz = c->nz;
+  p.dx = c->dx; p.dy = c->dy; p.dz = c->dz;
+  p.c0 = c->c0; p.f0 = c->f0; p.t = c->t;
+  p.ex = c->ex; p.ey = c->ey; p.ez = c->ez;
+  if (c->source_scale_kwave != 0) p.kwaveScale();
+  else if (c->source_scale_re != 0.0 || c->source_scale_im != 0.0) { p.scaleRe = c->source_scale_re; p.scaleIm = c->source_scale_im; }
+  CwOptions opt;
+  opt.deviceIdx    = o->device_idx;
+  opt.fusedKernels = o->fused_kernels != 0;
+  p.init(opt);
+  return p;
+}
 
 extern "C" {
 
@@ -456,4 +482,88 @@ int kwh_thermal_get_scalar(kwh_thermal* s, const char* name, float* out)
   else throw std::invalid_argument(std::string("unknown scalar ") + name);
   KWH_CATCH
 }
+
+// ---- CW field propagator ---------------------------------------------------------------------------------------------
+int kwh_cw_plan(const kwh_cw_config* config, const kwh_options* o, double* out_t, uint64_t out_expanded[3], int32_t* out_fast_path)
+{
+  KWH_TRY
+  if (!config || !o) throw std::invalid_argument("kwh_cw_plan: NULL argument");
+  const CwParameters p = kwh_cw_parameters(config, o);
+  if (out_t) *out_t = p.t;
+  if (out_expanded) { out_expanded[0] = p.ex; out_expanded[1] = p.ey; out_expanded[2] = p.ez; }
+  if (out_fast_path) *out_fast_path = p.fastPath ? 1 : 0;
+  KWH_CATCH
+}
+
+int kwh_cw_create(const kwh_cw_config* config, const kwh_options* o, kwh_cw** out)
+{
+  KWH_TRY
+  if (!config || !o || !out) throw std::invalid_argument("kwh_cw_create: NULL argument");
+  *out = nullptr;
+  std::unique_ptr<kwh_cw> s(new kwh_cw());
+  s->params = kwh_cw_parameters(config, o);
+  try { s->propagator.reset(new CwPropagator(s->params)); }
+  catch (const CwDeviceError& e) { g_err = e.what(); return static_cast<int>(e.status); } // KW_ERR_NO_DEVICE among them
+  *out = s.release();
+  KWH_CATCH
+}
+
+int kwh_cw_destroy(kwh_cw* s)
+{
+  KWH_TRY
+  delete s;
+  KWH_CATCH
+}
+
+int kwh_cw_run(kwh_cw* s, const float* a, const float* b, int parts)
+{
+  KWH_TRY
+  if (!s || !a || !b) throw std::invalid_argument("kwh_cw_run: NULL argument");
+  s->propagator->run(a, b, parts != 0);
+  KWH_CATCH
+}
+
+int kwh_cw_get(kwh_cw* s, const char* name, float* dst, uint64_t n)
+{
+  KWH_TRY
+  if (!s || !name || !dst) throw std::invalid_argument("kwh_cw_get: NULL argument");
+  s->propagator->get(name, dst, n);
+  KWH_CATCH
+}
+
+int kwh_cw_heat(kwh_cw* s, const float* q, float q_scalar, float* dst, uint64_t n)
+{
+  KWH_TRY
+  if (!s || !dst) throw std::invalid_argument("kwh_cw_heat: NULL argument");
+  s->propagator->heat(q, q_scalar, dst, n);
+  KWH_CATCH
+}
+
+int kwh_cw_propagate(kwh_cw* s)
+{
+  KWH_TRY
+  if (!s) throw std::invalid_argument("kwh_cw_propagate: NULL propagator");
+  s->propagator->propagate();
+  KWH_CATCH
+}
+
+int kwh_cw_get_scalar(kwh_cw* s, const char* name, double* out)
+{
+  KWH_TRY
+  if (!s || !name || !out) throw std::invalid_argument("kwh_cw_get_scalar: NULL argument");
+  const std::string n(name);
+  const CwParameters& p = s->propagator->parameters();
+  if (n == "fused_pipeline") *out = s->propagator->usesFusedPipeline() ? 1.0 : 0.0;
+  else if (n == "t") *out = p.t;
+  else if (n == "Ex") *out = static_cast<double>(p.ex);
+  else if (n == "Ey") *out = static_cast<double>(p.ey);
+  else if (n == "Ez") *out = static_cast<double>(p.ez);
+  else if (n == "runs") *out = static_cast<double>(s->propagator->runs());
+  else if (n == "source_scale_re") *out = p.scaleRe;
+  else if (n == "source_scale_im") *out = p.scaleIm;
+  else throw std::invalid_argument(std::string("unknown scalar ") + name);
+  KWH_CATCH
+}
+
+void* kwh_cw_context(kwh_cw* s) { return s ? s->propagator->context() : nullptr; }
 }
