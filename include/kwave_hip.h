@@ -761,6 +761,47 @@ KW_API kw_status kw_cw_extract(kw_ctx* ctx, const float* ex_re, const float* ex_
                                uint32_t nx, uint32_t ny, uint32_t nz, float* out_re, float* out_im, float* out_amp,
                                float* out_phase, float* out_q, const float* q, float q_scalar);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Angular-spectrum CW projector (what k-Wave's angularSpectrumCW computes): a complex pressure plane P0[y][x] carried to
+ * the planes z_j = z0 + j dz, j < n_planes, of a homogeneous medium with wavenumber k [rad/m] and absorption alpha [Np/m]
+ * (csrc/kw_angular.hip, host/AngularSpectrum.cpp).  Time factor exp(+i w t), outgoing waves exp(-i k r):
+ *     P(., ., z) = ifft2( fft2(P0 embedded in nx x ny) H(kx, ky, z) ),      kr^2 = kx^2 + ky^2,  q = |k^2 - kr^2|^(1/2)
+ *     kr^2 < k^2: H = exp(-i q z) exp(-alpha z k / q)     kr^2 = k^2: H = 1 (alpha = 0), 0 (alpha > 0)     kr^2 > k^2: H = exp(-q z)
+ *     restriction: H = 0 where kr > kc(z) = k sqrt(D^2/2 / (D^2/2 + z^2)),  D = min((nx - 1) dx, (ny - 1) dy)
+ * on the grid (nx, ny) of kw_set_constants; bins are counted k? = 2 pi / (n? d?) * min(i, n? - i).  No transform runs along
+ * z.  The field is two real arrays and H depends on kr only: the 2x2 mix of kw_cw_mix gives Hermitian half-spectra.
+ *
+ * kw_angular_operator: tables <- five arrays of (nx/2 + 1) * ny 4-byte words, [ky][kx] each, evaluated in float64:
+ *     a0, a1  uint32  round(frac(q z0 / 2 pi) 2^32), round(frac(q dz / 2 pi) 2^32) on kr^2 < k^2, else 0
+ *     b0, b1  float   alpha z0 k / q * log2(e) and the same of dz (kr^2 < k^2); q z0 log2(e), q dz log2(e) (kr^2 > k^2); else 0
+ *     alive   uint32  number of leading planes with kr <= kc(z_j) (n_planes without restriction); 0 on kr^2 = k^2, alpha > 0
+ *   H of plane j, every step in float32 without contraction:
+ *     angle = float(int32(a0 + j * a1)) * (2 pi 2^-32)      (the word wraps: exact phase, at most (j + 1) 2^-33 turns off)
+ *     m = exp2f(-(b0 + (float(j) * b1))) * divider, 0 where j >= alive;   Hr = m * cos(angle),  Hi = -(m * sin(angle))
+ *   (sincosf on the reduced argument; the hardware sine is not used).  n_planes <= 4096, z0 >= 0, dz > 0, alpha >= 0.
+ *   imported (may be NULL; needs kw_fused_create): the same five tables in the pipeline's plane layout,
+ *   kw_fused_angular_elems words each.
+ * kw_fused_angular_elems: complex values of one 2-D source spectrum = words of one imported table (rows of the pipeline's
+ *   pitch and, where the pipeline keeps it apart, the x-Nyquist column behind them).
+ * kw_fused_angular_forward: spec_re / spec_im <- the 2-D spectra of plane 0 of re / im [nz][ny][nx] (x-forward and the
+ *   forward y-pass on that plane; the leading planes that make up whole x tiles are read along with it).
+ * kw_fused_angular_planes: re, im [nz][ny][nx] <- planes j0 ... j0 + nz - 1, nz = the context's plane count (the chunk):
+ *   one launch k_yinv_angular (tile = (kx tile, plane): H of the plane from the table lines, the mix, both y-inverses over
+ *   one exchange buffer; divider = 1 / (nx ny)) and the x-inverse of the two arrays.  Single GPU, nz > 1: KW_ERR_INVALID in
+ *   slab mode or for Nz == 1.
+ * kw_angular_mix: the twin on plain spectra: out_re / out_im [n_planes][n_bins] interleaved complex <- the mix of the
+ *   source's spectra spec_re / spec_im [n_bins] with H of planes j0 ... from `tables` (natural order), for 2-D C2R
+ *   transforms of each plane (grids off the fast path).  n_bins == 0 or n_planes == 0: KW_OK, nothing launched.
+ * ---------------------------------------------------------------------------------------------------------------- */
+KW_API kw_status kw_angular_operator(kw_ctx* ctx, uint32_t* tables, uint32_t* imported, double dx, double dy, double k,
+                                     double alpha, double z0, double dz, uint32_t n_planes, int restriction);
+KW_API kw_status kw_fused_angular_elems(kw_ctx* ctx, size_t* out_elems);
+KW_API kw_status kw_fused_angular_forward(kw_ctx* ctx, const float* re, const float* im, float* spec_re, float* spec_im);
+KW_API kw_status kw_fused_angular_planes(kw_ctx* ctx, const float* spec_re, const float* spec_im,
+                                         const uint32_t* tables_imported, uint32_t j0, float* re, float* im);
+KW_API kw_status kw_angular_mix(kw_ctx* ctx, float* out_re, float* out_im, const float* spec_re, const float* spec_im,
+                                const uint32_t* tables, uint32_t n_bins, uint32_t n_planes, uint32_t j0, float divider);
+
 #ifdef __cplusplus
 }
 #endif

@@ -269,6 +269,56 @@ KWH_API int      kwh_cw_get_scalar(kwh_cw* s, const char* name, double* out);
 /* the underlying kw_ctx* (include/kwave_hip.h) */
 KWH_API void*    kwh_cw_context(kwh_cw* s);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Angular-spectrum CW projector (what k-Wave's angularSpectrumCW computes): a complex pressure plane P0 — a measured
+ * hologram, or the plane in front of a simulated array — carried to the planes z_j = z0 + j dz, j < planes, of a
+ * homogeneous medium that may absorb (alpha_np in Np/m at f0), by one 2-D FFT of the plane and one multiply and inverse
+ * 2-D FFT per output plane (kwave_hip.h "Angular-spectrum CW projector").  Nothing is transformed or expanded
+ * along z; the planes are computed in chunks of chunk_planes.
+ *   E (0 0 = default): the expanded sides; default the smallest fast-path line length of the fused pipeline at or above
+ *   2 N per axis; when an axis has none (above 1024) or with fused_kernels off, 2 N, which runs on rocFFT.  Given sides
+ *   must be even and not below N.
+ *   chunk_planes (0 = default): the smallest of 16, 32, 48, 64 that holds all the planes, 64 beyond that, reduced while the
+ *   chunk (16 bytes per expanded point and plane) exceeds 1 GiB, 16 at least; on a fast-path grid a given value must be a
+ *   fast-path length.
+ *   angular_restriction != 0: components beyond kc(z) = k sqrt(D^2/2 / (D^2/2 + z^2)) are dropped on plane z.
+ * Refused, naming the parameter: Nx Ny (0), dx dy, c0, f0 (not positive), z0 (< 0), dz (<= 0), planes (0, above 4096),
+ * alpha_np (< 0), Ex Ey (missing, odd, below N), chunk_planes, E (2^32 points or more per chunk).
+ * Of kwh_options the calls read device_idx and fused_kernels.  kwh_angular_plan validates and completes E and the chunk
+ * without a device.  Not built: heterogeneous media, reverse projection (z < 0), non-uniform plane spacing, the
+ * time-domain angularSpectrum, 2-D (line -> plane), Z-slabs, HDF5 files and the command line, graphs.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct kwh_angular kwh_angular;
+typedef struct kwh_angular_config
+{
+  uint64_t nx, ny;          /* the plane */
+  double   dx, dy;          /* [m] */
+  double   c0, f0;          /* [m/s], [Hz] */
+  double   z0, dz;          /* [m] */
+  uint64_t planes;          /* Nz */
+  double   alpha_np;        /* [Np/m]; 0 = lossless */
+  uint64_t ex, ey;          /* expanded sides; 0 0 = default */
+  uint64_t chunk_planes;    /* 0 = default */
+  int32_t  angular_restriction;
+  int32_t  pad_;
+} kwh_angular_config;
+KWH_API int      kwh_angular_plan(const kwh_angular_config* config, const kwh_options* options, uint64_t out_expanded[2],
+                                  uint64_t* out_chunk_planes, int32_t* out_fast_path);
+KWH_API int      kwh_angular_create(const kwh_angular_config* config, const kwh_options* options, kwh_angular** out);
+KWH_API int      kwh_angular_destroy(kwh_angular* s);
+/* a, b: Nx * Ny floats each on the host ([Ny][Nx]); parts != 0: Re P0, Im P0; parts == 0: amplitude, phase [rad] */
+KWH_API int      kwh_angular_run(kwh_angular* s, const float* a, const float* b, int parts);
+/* the last run's result [Nz][Ny][Nx]: "re", "im", "amplitude", "phase"; n = Nx * Ny * Nz (checked) */
+KWH_API int      kwh_angular_get(kwh_angular* s, const char* name, float* dst, uint64_t n);
+/* Q = q |P|^2: q per point (n floats), or NULL and q_scalar (kwh_cw_heat) */
+KWH_API int      kwh_angular_heat(kwh_angular* s, const float* q, float q_scalar, float* dst, uint64_t n);
+/* the chunks alone from the source spectra as they stand (timing: tools/bench_angular.py) */
+KWH_API int      kwh_angular_project(kwh_angular* s);
+/* "fused_pipeline", "Ex", "Ey", "chunk_planes", "planes", "runs" */
+KWH_API int      kwh_angular_get_scalar(kwh_angular* s, const char* name, double* out);
+/* the underlying kw_ctx* (include/kwave_hip.h) */
+KWH_API void*    kwh_angular_context(kwh_angular* s);
+
 #ifdef __cplusplus
 }
 #endif

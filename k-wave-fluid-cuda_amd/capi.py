@@ -197,6 +197,11 @@ _SIG: Dict[str, list] = {
     "kw_cw_mix": [_P, _P, _P, _P, _P, _U64],
     "kw_cw_embed": [_P, _P, _P, _P, _P, C.c_int, C.c_float, C.c_float] + [C.c_uint32] * 6,
     "kw_cw_extract": [_P, _P, _P] + [C.c_uint32] * 6 + [_P, _P, _P, _P, _P, _P, C.c_float],
+    "kw_angular_operator": [_P, _P, _P] + [C.c_double] * 6 + [C.c_uint32, C.c_int],
+    "kw_fused_angular_elems": [_P, C.POINTER(C.c_size_t)],
+    "kw_fused_angular_forward": [_P, _P, _P, _P, _P],
+    "kw_fused_angular_planes": [_P, _P, _P, _P, C.c_uint32, _P, _P],
+    "kw_angular_mix": [_P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float],
 }
 
 ELEMENT_CHUNK = 1024  # KW_ELEMENT_CHUNK

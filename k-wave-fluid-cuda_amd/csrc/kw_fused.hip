@@ -132,6 +132,19 @@ struct XinvArgs
                             // (the term is rho0 * sum du, its coefficient tau), 1 no_absorption (sum rho, eta)
 };
 
+// the y-inverse of the angular-spectrum projector (kw_angular.hip)
+struct AngArgs
+{
+  const float2*   in[2];  // the source's 2-D spectra Sr^, Si^ in the plane layout: rows [ky][P], side column at side_off2
+  float2*         out[2]; // scratch arrays of the chunk: planes [z][ky][P], side array at side_off
+  const uint32_t* tab;    // five tables (a0, a1, b0, b1, alive) of tab_elems words each, in the plane layout
+  const float2*   tw;
+  uint32_t        nxc, P, ny;
+  uint32_t        side_off, side_off2, tab_elems;
+  uint32_t        j0;     // plane index of the chunk's first plane
+  float           divider; // 1 / (Ex Ey)
+};
+
 struct XshiftArgs
 {
   const float*  in;
@@ -170,6 +183,8 @@ kw_status xinv_density_plane(int chain, int terms, kw_ctx* ctx, int ncomp, const
 kw_status xinv_other_plane(int epi, int chain, kw_ctx* ctx, int ncomp, const XinvArgs& a, uint32_t plane0, uint32_t nplanes);
 // the z-pass of kw_fused_cw_pair: two spectra forward along z, the 2x2 mix with two real operators, both inverses (kw_cw.hip)
 kw_status zfused_pair(kw_ctx* ctx, ZArgs a);
+// the y-inverse of kw_fused_angular_planes: H of each plane formed from the tables, the 2x2 mix, both inverses (kw_angular.hip)
+kw_status yinv_angular(kw_ctx* ctx, AngArgs a);
 // the tuning probes of kw_fused_probe that launch no pipeline kernel (kw_fused_probe.hip)
 kw_status probe_patterns(kw_ctx* ctx, int which, const float* op);
 

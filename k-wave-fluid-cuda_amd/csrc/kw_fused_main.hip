@@ -80,7 +80,8 @@ bool supported_len(uint32_t n)
 
 #define KW_TRY(call) KW_TRY_STATUS(call)
 
-kw_status launch_xfwd(kw_ctx* ctx, int narr, const float* const* in, float2* const* out)
+// nzc: planes 0 ... nzc - 1 only (0: the whole array)
+kw_status launch_xfwd(kw_ctx* ctx, int narr, const float* const* in, float2* const* out, uint32_t nzc = 0)
 {
   const kw_constants& c = ctx->c;
   static const char* const names[3] = { "k_xfwd[1]", "k_xfwd[2]", "k_xfwd[3]" };
@@ -91,7 +92,7 @@ kw_status launch_xfwd(kw_ctx* ctx, int narr, const float* const* in, float2* con
   a.nx = c.nx;
   a.P  = ctx->fused.P;
   a.side_off = ctx->fused.side_off;
-  a.nrows = c.ny * c.nz;
+  a.nrows = c.ny * (nzc ? nzc : c.nz);
   const uint32_t rows_per_tile = 2u * static_cast<uint32_t>(nl_x(c.nx)), full = a.nrows / rows_per_tile;
   if (full > 0)
   {
@@ -1381,6 +1382,80 @@ kw_status kw_fused_cw_pair(kw_ctx* ctx, float* re, float* im, const float* g_re_
   KW_TRY(launch_xinv<EPI_STORE>(ctx, 2, x));
   return KW_OK;
 }
+
+// Angular-spectrum projector (kw_angular.hip).  The source plane is transformed once: x-forward of the leading planes of
+// re / im that make whole x tiles (plane 0 holds the source; the others ride along and are dropped), the forward y-pass of
+// plane 0 alone, and a copy of that plane's rows and side column into the compact 2-D spectra
+// (kw_fused_angular_elems complex values each).
+kw_status kw_fused_angular_elems(kw_ctx* ctx, size_t* out)
+{
+  KW_FUSED_READY(ctx);
+  KW_REQUIRE(out != nullptr);
+  const auto& f = ctx->fused;
+  *out = static_cast<size_t>(f.P) * ctx->c.ny + (f.side_off != 0 ? ctx->c.ny : 0u);
+  return KW_OK;
+}
+
+#define KW_ANGULAR_3D(ctx, name)                                                                                       \
+  if ((ctx)->fused.slab || (ctx)->fused.two_d)                                                                         \
+  {                                                                                                                    \
+    kw_set_error(name ": single GPU and a chunk of planes only (no Z-slabs, no Nz == 1)");                             \
+    return KW_ERR_INVALID;                                                                                             \
+  }
+
+kw_status kw_fused_angular_forward(kw_ctx* ctx, const float* re, const float* im, float* spec_re, float* spec_im)
+{
+  KW_FUSED_READY(ctx);
+  KW_PROF(ctx, "fused_angular_forward");
+  KW_REQUIRE(re && im && spec_re && spec_im && spec_re != spec_im);
+  KW_ANGULAR_3D(ctx, "kw_fused_angular_forward")
+  const kw_constants& c = ctx->c;
+  const auto& f = ctx->fused;
+  const uint32_t rows_per_tile = 2u * static_cast<uint32_t>(nl_x(c.nx));
+  uint32_t np = 1;
+  while (np < c.nz && (c.ny * np) % rows_per_tile != 0) np++; // whole x tiles: no masked tile is ever needed
+  const float* in2[2] = { re, im };
+  KW_TRY(launch_xfwd(ctx, 2, in2, f.s, np));
+  KW_TRY(launch_ypass(ctx, -1, 2, f.s, f.s, false, false, 0, 1));
+  float* const spec[2] = { spec_re, spec_im };
+  const size_t main_elems = static_cast<size_t>(f.P) * c.ny;
+  for (int i = 0; i < 2; i++)
+  {
+    float2* dst = reinterpret_cast<float2*>(spec[i]);
+    KW_HIP(hipMemcpyAsync(dst, f.s[i], main_elems * sizeof(float2), hipMemcpyDeviceToDevice, ctx->stream));
+    if (f.side_off != 0)
+      KW_HIP(hipMemcpyAsync(dst + main_elems, f.s[i] + f.side_off, c.ny * sizeof(float2), hipMemcpyDeviceToDevice, ctx->stream));
+  }
+  return KW_OK;
+}
+
+// One chunk of planes: planes j0 ... j0 + Nz - 1 (Nz = the context's plane count) of
+//   re + i im <- ifft2( (spec_re^ + i spec_im^) H(., ., z_j) )
+// as k_yinv_angular (H from the imported tables, the 2x2 mix, both y-inverses) and the x-inverse of the two arrays.
+kw_status kw_fused_angular_planes(kw_ctx* ctx, const float* spec_re, const float* spec_im, const uint32_t* tables_imported,
+                                  uint32_t j0, float* re, float* im)
+{
+  KW_FUSED_READY(ctx);
+  KW_PROF(ctx, "fused_angular_planes");
+  KW_REQUIRE(spec_re && spec_im && tables_imported && re && im && re != im);
+  KW_REQUIRE(static_cast<uint64_t>(j0) + ctx->c.nz <= (1ull << 31));
+  KW_ANGULAR_3D(ctx, "kw_fused_angular_planes")
+  float2** S = ctx->fused.s;
+  AngArgs a{};
+  a.in[0]  = reinterpret_cast<const float2*>(spec_re);
+  a.in[1]  = reinterpret_cast<const float2*>(spec_im);
+  a.out[0] = S[0];
+  a.out[1] = S[1];
+  a.tab    = tables_imported;
+  a.j0     = j0;
+  KW_TRY(yinv_angular(ctx, a));
+  XinvArgs x{};
+  x.in[0] = S[0]; x.in[1] = S[1];
+  x.out[0] = re;  x.out[1] = im;
+  KW_TRY(launch_xinv<EPI_STORE>(ctx, 2, x));
+  return KW_OK;
+}
+#undef KW_ANGULAR_3D
 
 // Pass-level probe for tuning (tools/probe_passes.py): launches ONE pass over the scratch arrays, no physics.
 //   0: y-pass forward on s[0] (in place)          1: the same line kernel along z (stride ny*P) on s[0]

@@ -5,7 +5,8 @@ medium from one forward and one inverse 3-D FFT on an expanded grid — what k-W
 instead of a time loop run until steady.  It sits between the array builders (`arrays.offgrid_elements`) and the bioheat
 solver (`thermal.ThermalSolver`, whose `Q` is `heat()`).  No CPU fallback: a missing library or device raises.
 
-Not built: absorbing or heterogeneous media, 2-D, Z-slabs, HDF5 files and the command line, graphs.
+Not built: heterogeneous media, 2-D, Z-slabs, HDF5 files and the command line, graphs.  Absorbing media and sources given
+as a pressure plane: `angular.AngularSpectrum`.
 """
 from __future__ import annotations
 

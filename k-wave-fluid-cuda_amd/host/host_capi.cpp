@@ -11,6 +11,7 @@
 #include "MatrixNames.h"
 #include "KSpaceFirstOrderSolver.h"
 #include "ThermalSolver.h"
+#include "AngularSpectrum.h"
 #include "CwPropagator.h"
 #include "kwave_host.h"
 
@@ -115,6 +116,32 @@ static CwParameters kwh_cw_parameters(const kwh_cw_config* c, const kwh_options*
   if (c->source_scale_kwave != 0) p.kwaveScale();
   else if (c->source_scale_re != 0.0 || c->source_scale_im != 0.0) { p.scaleRe = c->source_scale_re; p.scaleIm = c->source_scale_im; }
   CwOptions opt;
+  opt.deviceIdx    = o->device_idx;
+  opt.fusedKernels = o->fused_kernels != 0;
+  p.init(opt);
+  return p;
+}
+
+/// an angular-spectrum projector with its completed parameters
+struct kwh_angular
+{
+  AngularParameters                params;
+  std::unique_ptr<AngularSpectrum> projector;
+};
+
+static AngularParameters kwh_angular_parameters(const kwh_angular_config* c, const kwh_options* o)
+{
+  AngularParameters p;
+  p.nx = c->nx; p.ny = c->ny;
+  p.dx = c->dx; p.dy = c->dy;
+  p.c0 = c->c0; p.f0 = c->f0;
+  p.z0 = c->z0; p.dz = c->dz;
+  p.planes = c->planes;
+  p.alphaNp = c->alpha_np;
+  p.restriction = c->angular_restriction != 0;
+  p.ex = c->ex; p.ey = c->ey;
+  p.chunkPlanes = c->chunk_planes;
+  AngularOptions opt;
   opt.deviceIdx    = o->device_idx;
   opt.fusedKernels = o->fused_kernels != 0;
   p.init(opt);
@@ -566,4 +593,87 @@ int kwh_cw_get_scalar(kwh_cw* s, const char* name, double* out)
 }
 
 void* kwh_cw_context(kwh_cw* s) { return s ? s->propagator->context() : nullptr; }
+
+// ---- angular-spectrum projector --------------------------------------------------------------------------------------
+int kwh_angular_plan(const kwh_angular_config* config, const kwh_options* o, uint64_t out_expanded[2], uint64_t* out_chunk_planes,
+                     int32_t* out_fast_path)
+{
+  KWH_TRY
+  if (!config || !o) throw std::invalid_argument("kwh_angular_plan: NULL argument");
+  const AngularParameters p = kwh_angular_parameters(config, o);
+  if (out_expanded) { out_expanded[0] = p.ex; out_expanded[1] = p.ey; }
+  if (out_chunk_planes) *out_chunk_planes = p.chunkPlanes;
+  if (out_fast_path) *out_fast_path = p.fastPath ? 1 : 0;
+  KWH_CATCH
+}
+
+int kwh_angular_create(const kwh_angular_config* config, const kwh_options* o, kwh_angular** out)
+{
+  KWH_TRY
+  if (!config || !o || !out) throw std::invalid_argument("kwh_angular_create: NULL argument");
+  *out = nullptr;
+  std::unique_ptr<kwh_angular> s(new kwh_angular());
+  s->params = kwh_angular_parameters(config, o);
+  try { s->projector.reset(new AngularSpectrum(s->params)); }
+  catch (const CwDeviceError& e) { g_err = e.what(); return static_cast<int>(e.status); } // KW_ERR_NO_DEVICE among them
+  *out = s.release();
+  KWH_CATCH
+}
+
+int kwh_angular_destroy(kwh_angular* s)
+{
+  KWH_TRY
+  delete s;
+  KWH_CATCH
+}
+
+int kwh_angular_run(kwh_angular* s, const float* a, const float* b, int parts)
+{
+  KWH_TRY
+  if (!s || !a || !b) throw std::invalid_argument("kwh_angular_run: NULL argument");
+  s->projector->run(a, b, parts != 0);
+  KWH_CATCH
+}
+
+int kwh_angular_get(kwh_angular* s, const char* name, float* dst, uint64_t n)
+{
+  KWH_TRY
+  if (!s || !name || !dst) throw std::invalid_argument("kwh_angular_get: NULL argument");
+  s->projector->get(name, dst, n);
+  KWH_CATCH
+}
+
+int kwh_angular_heat(kwh_angular* s, const float* q, float q_scalar, float* dst, uint64_t n)
+{
+  KWH_TRY
+  if (!s || !dst) throw std::invalid_argument("kwh_angular_heat: NULL argument");
+  s->projector->heat(q, q_scalar, dst, n);
+  KWH_CATCH
+}
+
+int kwh_angular_project(kwh_angular* s)
+{
+  KWH_TRY
+  if (!s) throw std::invalid_argument("kwh_angular_project: NULL projector");
+  s->projector->project();
+  KWH_CATCH
+}
+
+int kwh_angular_get_scalar(kwh_angular* s, const char* name, double* out)
+{
+  KWH_TRY
+  if (!s || !name || !out) throw std::invalid_argument("kwh_angular_get_scalar: NULL argument");
+  const std::string n(name);
+  const AngularParameters& p = s->projector->parameters();
+  if (n == "fused_pipeline") *out = s->projector->usesFusedPipeline() ? 1.0 : 0.0;
+  else if (n == "Ex") *out = static_cast<double>(p.ex);
+  else if (n == "Ey") *out = static_cast<double>(p.ey);
+  else if (n == "chunk_planes") *out = static_cast<double>(p.chunkPlanes);
+  else if (n == "planes") *out = static_cast<double>(p.planes);
+  else if (n == "runs") *out = static_cast<double>(s->projector->runs());
+  else throw std::invalid_argument(std::string("unknown scalar ") + name);
+  KWH_CATCH
+}
+
+void* kwh_angular_context(kwh_angular* s) { return s ? s->projector->context() : nullptr; }
 }
