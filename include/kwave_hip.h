@@ -802,6 +802,64 @@ KW_API kw_status kw_fused_angular_planes(kw_ctx* ctx, const float* spec_re, cons
 KW_API kw_status kw_angular_mix(kw_ctx* ctx, float* out_re, float* out_im, const float* spec_re, const float* spec_im,
                                 const uint32_t* tables, uint32_t n_bins, uint32_t n_planes, uint32_t j0, float divider);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Time-domain angular-spectrum projector (what k-Wave's angularSpectrum computes): a real pressure record p0[t][y][x] on a
+ * plane carried to a parallel plane at distance z >= 0 of a homogeneous medium (csrc/kw_angular_time.hip,
+ * host/AngularSpectrumTime.cpp).  Time factor exp(+i w t), outgoing waves exp(-i k r).  The grid of
+ * kw_set_constants is (nx, ny, nz) = (Ex, Ey, Lt): the time axis is where the pipeline has z; Ex and Lt even.
+ *     p(., ., .; z) = irfftn( rfftn(p0 embedded in Lt x Ey x Ex) H(kx, ky, m; z) )                     axes (t, y, x)
+ *     m' = min(m, Lt - m),  w = 2 pi m' / (Lt dt),  k = w / c0,  kr^2 = kx^2 + ky^2,  q = |k^2 - kr^2|^(1/2)
+ *     bins are counted k? = 2 pi / (n? d?) * min(i, n? - i)
+ *     m = 0 and m = Lt/2: H = 0 (the record's temporal mean is dropped)
+ *     kr^2 < k^2: H0 = exp(-i q z) exp(-alpha(m') z k / q)     kr^2 = k^2: H0 = 1 (alpha = 0), 0 (alpha > 0)
+ *     kr^2 > k^2: H0 = exp(-q z)
+ *     retarded:    H0 <- H0 exp(+i k z)                        (plane z is reported at the times t_n + z / c0)
+ *     restriction: H0 = 0 where kr^2 > k^2 (D^2/2) / (D^2/2 + z^2),  D = min((Ex - 1) dx, (Ey - 1) dy)
+ *     H = H0 for 0 < m < Lt/2, conj(H0) for m > Lt/2
+ * One real array is enough: H(-w) = conj H(w) and H depends on kr only, so the half-spectrum stays Hermitian.
+ *
+ * H per bin is ONE device function for the fused kernel and the twin, without contraction into fma:
+ *   float64: kx, ky from the bin counts;  kr2 = (kx*kx) + (ky*ky);  k = dk * m' with dk = 2 pi / (Lt dt c0);  k2 = k*k;
+ *            q = sqrt(fabs(k2 - kr2));  turns t = (qp - (retarded ? k : 0)) * z / 2 pi, qp = q when kr2 <= k2, 0 above;
+ *            word = uint32(rint((t - floor(t)) * 2^32));  restriction test kr2 > k2 * cfac, cfac = (D^2/2) / (D^2/2 + z^2)
+ *            computed once on the host
+ *   float32: angle = float(int32(word)) * (2 pi 2^-32), one sincosf (the hardware sine is not used);  q32 = float(q);
+ *            b = float(ak[m'] * z) / q32 (kr2 < k2, ak given), q32 * float(z log2(e)) (kr2 > k2), else 0;
+ *            mag = exp2f(-b) * divider, 0 for m' = 0, m' = Lt/2, on kr2 = k2 with ak[m'] > 0, and beyond the restriction;
+ *            Hr = mag * cos,  Hi = -(mag * sin), Hi negated for m > Lt/2;
+ *            out = ((Hr * x.x) - (Hi * x.y), (Hr * x.y) + (Hi * x.x))
+ *   A float32 product q z would be 3e-4 rad off a thousand wavelengths out; the phase word is exact to 2^-33 turns.
+ *
+ * kw_fused_angular_time_elems: complex values of one scratch array = the size of `kept`.
+ * kw_fused_angular_time_forward: kept <- the (kx, ky, t) half-spectrum of vol [nz][ny][nx]: x-forward and y-forward of the
+ *   one array, then a copy of scratch array 0, side array included.
+ * kw_fused_angular_time_plane: vol_out [nz][ny][nx] <- the record on plane op->z: one launch k_zfused_time (lines of `kept`
+ *   forward along t, H formed in registers — no operator array, no table in memory —, inverse along t into scratch array 0;
+ *   divider = 1 / (nx ny nz)), the y-inverse and the storing x-inverse.  `kept` is not written.  Both: single GPU, nz > 1:
+ *   KW_ERR_INVALID in slab mode or for Nz == 1.
+ * kw_angular_time_mix: the twin: out_spec <- spec H on the natural [nz][ny][nx/2 + 1] half-spectrum of kw_fft_r2c_3d, out of
+ *   place, for kw_fft_c2r_3d of each plane (grids off the fast path).  A context without bins: KW_OK, nothing launched.
+ * kw_angular_time_embed: vol [lt][ey][ex] <- src [nt][ny][nx] in the corner, zero elsewhere.
+ * kw_angular_time_reduce: p_max, p_min [ny][nx] <- max_t, min_t over t < nt of the corner of vol [lt][ey][ex]; series
+ *   [nt][ny][nx] <- the corner itself.  Each output may be NULL.  Exact and deterministic (no float atomics): a block takes 16
+ *   points and splits the record along t over its thread rows, so a small plane with a long record still fills the device.
+ *   Both use 16-byte accesses when ex and nx are multiples of 4 and the pointers are 16-byte aligned; zero points: KW_OK.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct kw_angular_time_op {   /* H of one plane */
+  double dx, dy, dt, c0, z;           /* [m], [m], [s], [m/s], [m]; z >= 0 */
+  const double* ak;                   /* device, nz/2 + 1 values alpha(m') k(m') log2(e); NULL = lossless */
+  int32_t restriction, retarded;
+} kw_angular_time_op;
+KW_API kw_status kw_fused_angular_time_elems(kw_ctx* ctx, size_t* out_elems);
+KW_API kw_status kw_fused_angular_time_forward(kw_ctx* ctx, const float* vol, float* kept);
+KW_API kw_status kw_fused_angular_time_plane(kw_ctx* ctx, const float* kept, const kw_angular_time_op* op, float* vol_out);
+KW_API kw_status kw_angular_time_mix(kw_ctx* ctx, float* out_spec, const float* spec, const kw_angular_time_op* op,
+                                     float divider);
+KW_API kw_status kw_angular_time_embed(kw_ctx* ctx, float* vol, const float* src, uint32_t ex, uint32_t ey, uint32_t lt,
+                                       uint32_t nx, uint32_t ny, uint32_t nt);
+KW_API kw_status kw_angular_time_reduce(kw_ctx* ctx, const float* vol, uint32_t ex, uint32_t ey, uint32_t lt, uint32_t nx,
+                                        uint32_t ny, uint32_t nt, float* p_max, float* p_min, float* series);
+
 #ifdef __cplusplus
 }
 #endif

@@ -285,8 +285,8 @@ KWH_API void*    kwh_cw_context(kwh_cw* s);
  * Refused, naming the parameter: Nx Ny (0), dx dy, c0, f0 (not positive), z0 (< 0), dz (<= 0), planes (0, above 4096),
  * alpha_np (< 0), Ex Ey (missing, odd, below N), chunk_planes, E (2^32 points or more per chunk).
  * Of kwh_options the calls read device_idx and fused_kernels.  kwh_angular_plan validates and completes E and the chunk
- * without a device.  Not built: heterogeneous media, reverse projection (z < 0), non-uniform plane spacing, the
- * time-domain angularSpectrum, 2-D (line -> plane), Z-slabs, HDF5 files and the command line, graphs.
+ * without a device.  Not built: heterogeneous media, reverse projection (z < 0), non-uniform plane spacing,
+ * 2-D (line -> plane), Z-slabs, HDF5 files and the command line, graphs.
  * ---------------------------------------------------------------------------------------------------------------- */
 typedef struct kwh_angular kwh_angular;
 typedef struct kwh_angular_config
@@ -318,6 +318,61 @@ KWH_API int      kwh_angular_project(kwh_angular* s);
 KWH_API int      kwh_angular_get_scalar(kwh_angular* s, const char* name, double* out);
 /* the underlying kw_ctx* (include/kwave_hip.h) */
 KWH_API void*    kwh_angular_context(kwh_angular* s);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Time-domain angular-spectrum projector (what k-Wave's angularSpectrum computes): a pressure record p0[t][y][x] on a plane
+ * — a pulsed hydrophone scan, or a cuboid of a time-loop run in front of an array — carried to the parallel planes at the
+ * distances z[j] >= 0, j < n_planes, of a homogeneous medium with optional power-law absorption alpha_coeff f^alpha_power
+ * (dB / (MHz^y cm), no dispersion).  The record is transformed once over (t, y, x); every plane costs one multiply by
+ * H(kx, ky, w; z) and one inverse transform (kwave_hip.h "Time-domain angular-spectrum projector").  Results:
+ * p_max = max_t p and p_min = min_t p per plane, and on request the record of one plane, all on the domain Nx x Ny (x Nt).
+ *   E (0 0 = default): as kwh_angular_config.
+ *   lt (0 = default): the expanded record length; default the smallest fast-path length at or above Nt, or Nt rounded up to
+ *   even when there is none (above 1024) or with fused_kernels off.  A given lt must be even and not below Nt.
+ *   angular_restriction != 0: on plane z the components with kr^2 > k^2 (D^2/2) / (D^2/2 + z^2) are dropped.
+ *   retarded_time != 0: plane z is reported at the times t_n + z / c0.
+ * The temporal mean and the temporal Nyquist bin of the record are dropped.
+ * Refused, naming the parameter: Nx Ny Nt (0), dx dy dt c0 (not positive), alpha_coeff alpha_power (< 0), n_planes (0, above
+ * 4096), z (NULL, an entry < 0), Ex Ey (missing, odd, below N), Lt (odd, below Nt), E (2^32 points or more).
+ * Of kwh_options the calls read device_idx and fused_kernels.  kwh_angular_time_plan validates and completes (Ex, Ey, Lt)
+ * without a device.  Not built: heterogeneous media, dispersion, reverse projection, 2-D, Z-slabs, HDF5 files and the
+ * command line, graphs; several output planes per z-pass; the x- and y-inverse restricted to the crop; band limits other
+ * than DC / Nyquist.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct kwh_angular_time kwh_angular_time;
+typedef struct kwh_angular_time_config
+{
+  uint64_t nx, ny, nt;      /* the record */
+  double   dx, dy, dt;      /* [m], [m], [s] */
+  double   c0;              /* [m/s] */
+  double   alpha_coeff;     /* [dB / (MHz^y cm)]; 0 = lossless */
+  double   alpha_power;     /* y */
+  uint64_t ex, ey;          /* expanded sides; 0 0 = default */
+  uint64_t lt;              /* expanded record length; 0 = default */
+  uint64_t n_planes;        /* 1 ... 4096 */
+  const double* z;          /* [m], n_planes distances */
+  int32_t  angular_restriction;
+  int32_t  retarded_time;
+} kwh_angular_time_config;
+KWH_API int      kwh_angular_time_plan(const kwh_angular_time_config* config, const kwh_options* options,
+                                       uint64_t out_expanded[3], int32_t* out_fast_path);
+KWH_API int      kwh_angular_time_create(const kwh_angular_time_config* config, const kwh_options* options,
+                                         kwh_angular_time** out);
+KWH_API int      kwh_angular_time_destroy(kwh_angular_time* s);
+/* p0: Nx * Ny * Nt floats on the host ([Nt][Ny][Nx]): embed, transform, keep */
+KWH_API int      kwh_angular_time_set_input(kwh_angular_time* s, const float* p0);
+/* set_input and every plane; p_max / p_min [n_planes][Ny][Nx] stay on the device */
+KWH_API int      kwh_angular_time_run(kwh_angular_time* s, const float* p0);
+/* "p_max" or "p_min" of the last run; n = Nx * Ny * n_planes (checked) */
+KWH_API int      kwh_angular_time_get(kwh_angular_time* s, const char* name, float* dst, uint64_t n);
+/* plane j recomputed alone: dst [Nt][Ny][Nx], n = Nx * Ny * Nt (checked) */
+KWH_API int      kwh_angular_time_series(kwh_angular_time* s, uint64_t j, float* dst, uint64_t n);
+/* the planes alone from the kept spectrum as it stands (timing: tools/bench_angular_time.py) */
+KWH_API int      kwh_angular_time_project(kwh_angular_time* s);
+/* "fused_pipeline", "Ex", "Ey", "Lt", "planes", "runs" */
+KWH_API int      kwh_angular_time_get_scalar(kwh_angular_time* s, const char* name, double* out);
+/* the underlying kw_ctx* (include/kwave_hip.h) */
+KWH_API void*    kwh_angular_time_context(kwh_angular_time* s);
 
 #ifdef __cplusplus
 }

@@ -202,7 +202,19 @@ _SIG: Dict[str, list] = {
     "kw_fused_angular_forward": [_P, _P, _P, _P, _P],
     "kw_fused_angular_planes": [_P, _P, _P, _P, C.c_uint32, _P, _P],
     "kw_angular_mix": [_P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float],
+    "kw_fused_angular_time_elems": [_P, C.POINTER(C.c_size_t)],
+    "kw_fused_angular_time_forward": [_P, _P, _P],
+    "kw_fused_angular_time_plane": [_P, _P, _P, _P],
+    "kw_angular_time_mix": [_P, _P, _P, _P, C.c_float],
+    "kw_angular_time_embed": [_P, _P, _P] + [C.c_uint32] * 6,
+    "kw_angular_time_reduce": [_P, _P] + [C.c_uint32] * 6 + [_P, _P, _P],
 }
+
+class AngularTimeOp(C.Structure):
+    """struct kw_angular_time_op: H of one plane of the time-domain angular-spectrum projector"""
+    _fields_ = [("dx", C.c_double), ("dy", C.c_double), ("dt", C.c_double), ("c0", C.c_double), ("z", C.c_double),
+                ("ak", C.c_void_p), ("restriction", C.c_int32), ("retarded", C.c_int32)]
+
 
 ELEMENT_CHUNK = 1024  # KW_ELEMENT_CHUNK
 

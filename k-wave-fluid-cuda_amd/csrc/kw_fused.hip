@@ -145,6 +145,21 @@ struct AngArgs
   float           divider; // 1 / (Ex Ey)
 };
 
+// the z-pass of the time-domain angular-spectrum projector (kw_angular_time.hip): H of one plane, formed per bin
+struct ZTimeArgs
+{
+  const float2* in;   // the kept (kx, ky, t) half-spectrum, scratch layout (rows [t][ky][P], side array at side_off)
+  float2*       out;  // scratch array 0
+  const float2* tw;
+  const double* ak;   // Lt/2 + 1 values alpha(m') k(m') log2(e), or NULL
+  double        dkx, dky, dk; // 2 pi / (Ex dx), 2 pi / (Ey dy), 2 pi / (Lt dt c0)
+  double        z, cfac;      // plane distance; D^2/2 / (D^2/2 + z^2)
+  float         zl2e;         // float(z log2(e))
+  float         divider;      // 1 / (Ex Ey Lt)
+  uint32_t      nxc, P, ex, ny, nz, side_off; // ex = Ex (the bin counts along x)
+  uint32_t      restriction, retarded;
+};
+
 struct XshiftArgs
 {
   const float*  in;
@@ -185,6 +200,9 @@ kw_status xinv_other_plane(int epi, int chain, kw_ctx* ctx, int ncomp, const Xin
 kw_status zfused_pair(kw_ctx* ctx, ZArgs a);
 // the y-inverse of kw_fused_angular_planes: H of each plane formed from the tables, the 2x2 mix, both inverses (kw_angular.hip)
 kw_status yinv_angular(kw_ctx* ctx, AngArgs a);
+// the z-pass of kw_fused_angular_time_plane: one spectrum forward along t, H of the plane formed in registers, the inverse
+// (kw_angular_time.hip): lines of `in` (the kept spectrum) to `out`
+kw_status zfused_time(kw_ctx* ctx, const float2* in, float2* out, const kw_angular_time_op* op);
 // the tuning probes of kw_fused_probe that launch no pipeline kernel (kw_fused_probe.hip)
 kw_status probe_patterns(kw_ctx* ctx, int which, const float* op);
 

@@ -1457,6 +1457,55 @@ kw_status kw_fused_angular_planes(kw_ctx* ctx, const float* spec_re, const float
 }
 #undef KW_ANGULAR_3D
 
+// Time-domain angular-spectrum projector (kw_angular_time.hip).  The record [Lt][Ey][Ex] is transformed along x and y once
+// and the (kx, ky, t) half-spectrum kept aside; every plane is kw_fused_scale_source's second half with k_zfused_time as
+// its z-pass, reading the kept spectrum.
+#define KW_ANGULAR_TIME_3D(ctx, name)                                                                                  \
+  if ((ctx)->fused.slab || (ctx)->fused.two_d)                                                                         \
+  {                                                                                                                    \
+    kw_set_error(name ": single GPU and 3-D only (no Z-slabs, no Nz == 1)");                                           \
+    return KW_ERR_INVALID;                                                                                             \
+  }
+
+kw_status kw_fused_angular_time_elems(kw_ctx* ctx, size_t* out)
+{
+  KW_FUSED_READY(ctx);
+  KW_REQUIRE(out != nullptr);
+  *out = static_cast<size_t>(ctx->fused.Palloc) * ctx->c.ny * ctx->c.nz;
+  return KW_OK;
+}
+
+kw_status kw_fused_angular_time_forward(kw_ctx* ctx, const float* vol, float* kept)
+{
+  KW_FUSED_READY(ctx);
+  KW_PROF(ctx, "fused_angular_time_forward");
+  KW_REQUIRE(vol && kept);
+  KW_ANGULAR_TIME_3D(ctx, "kw_fused_angular_time_forward")
+  const float* in1[1] = { vol };
+  KW_TRY(forward_xy(ctx, 1, in1));
+  const size_t elems = static_cast<size_t>(ctx->fused.Palloc) * ctx->c.ny * ctx->c.nz;
+  KW_HIP(hipMemcpyAsync(kept, ctx->fused.s[0], elems * sizeof(float2), hipMemcpyDeviceToDevice, ctx->stream));
+  return KW_OK;
+}
+
+kw_status kw_fused_angular_time_plane(kw_ctx* ctx, const float* kept, const kw_angular_time_op* op, float* vol_out)
+{
+  KW_FUSED_READY(ctx);
+  KW_PROF(ctx, "fused_angular_time_plane");
+  KW_REQUIRE(kept && op && vol_out);
+  KW_ANGULAR_TIME_3D(ctx, "kw_fused_angular_time_plane")
+  KW_REQUIRE(op->dx > 0.0 && op->dy > 0.0 && op->dt > 0.0 && op->c0 > 0.0 && op->z >= 0.0);
+  float2** S = ctx->fused.s;
+  KW_TRY(zfused_time(ctx, reinterpret_cast<const float2*>(kept), S[0], op));
+  KW_TRY(inverse_y(ctx, 1));
+  XinvArgs x{};
+  x.in[0]  = S[0];
+  x.out[0] = vol_out;
+  KW_TRY(launch_xinv<EPI_STORE>(ctx, 1, x));
+  return KW_OK;
+}
+#undef KW_ANGULAR_TIME_3D
+
 // Pass-level probe for tuning (tools/probe_passes.py): launches ONE pass over the scratch arrays, no physics.
 //   0: y-pass forward on s[0] (in place)          1: the same line kernel along z (stride ny*P) on s[0]
 //   2: z-fused (forward, x sourceKappa-style multiply with op, inverse) on s[0]   3: y-pass on s[0..2] (3 arrays)

@@ -12,6 +12,7 @@
 #include "KSpaceFirstOrderSolver.h"
 #include "ThermalSolver.h"
 #include "AngularSpectrum.h"
+#include "AngularSpectrumTime.h"
 #include "CwPropagator.h"
 #include "kwave_host.h"
 
@@ -141,6 +142,35 @@ static AngularParameters kwh_angular_parameters(const kwh_angular_config* c, con
   p.restriction = c->angular_restriction != 0;
   p.ex = c->ex; p.ey = c->ey;
   p.chunkPlanes = c->chunk_planes;
+  AngularOptions opt;
+  opt.deviceIdx    = o->device_idx;
+  opt.fusedKernels = o->fused_kernels != 0;
+  p.init(opt);
+  return p;
+}
+
+/// a time-domain angular-spectrum projector with its completed parameters
+struct kwh_angular_time
+{
+  AngularTimeParameters                params;
+  std::unique_ptr<AngularSpectrumTime> projector;
+};
+
+static AngularTimeParameters kwh_angular_time_parameters(const kwh_angular_time_config* c, const kwh_options* o)
+{
+  AngularTimeParameters p;
+  p.nx = c->nx; p.ny = c->ny; p.nt = c->nt;
+  p.dx = c->dx; p.dy = c->dy; p.dt = c->dt;
+  p.c0 = c->c0;
+  p.alphaCoeff = c->alpha_coeff;
+  p.alphaPower = c->alpha_power;
+  p.restriction = c->angular_restriction != 0;
+  p.retarded    = c->retarded_time != 0;
+  p.ex = c->ex; p.ey = c->ey; p.lt = c->lt;
+  if (c->n_planes > AngularRule::kMaxPlanes)
+    throw std::invalid_argument("n_planes: " + std::to_string(c->n_planes) + " is above " + std::to_string(AngularRule::kMaxPlanes));
+  if (c->n_planes != 0 && c->z == nullptr) throw std::invalid_argument("z: NULL with n_planes > 0");
+  p.z.assign(c->z, c->z + c->n_planes);
   AngularOptions opt;
   opt.deviceIdx    = o->device_idx;
   opt.fusedKernels = o->fused_kernels != 0;
@@ -676,4 +706,93 @@ int kwh_angular_get_scalar(kwh_angular* s, const char* name, double* out)
 }
 
 void* kwh_angular_context(kwh_angular* s) { return s ? s->projector->context() : nullptr; }
+
+// ---- time-domain angular-spectrum projector --------------------------------------------------------------------------
+int kwh_angular_time_plan(const kwh_angular_time_config* config, const kwh_options* o, uint64_t out_expanded[3], int32_t* out_fast_path)
+{
+  KWH_TRY
+  if (!config || !o) throw std::invalid_argument("kwh_angular_time_plan: NULL argument");
+  const AngularTimeParameters p = kwh_angular_time_parameters(config, o);
+  if (out_expanded) { out_expanded[0] = p.ex; out_expanded[1] = p.ey; out_expanded[2] = p.lt; }
+  if (out_fast_path) *out_fast_path = p.fastPath ? 1 : 0;
+  KWH_CATCH
+}
+
+int kwh_angular_time_create(const kwh_angular_time_config* config, const kwh_options* o, kwh_angular_time** out)
+{
+  KWH_TRY
+  if (!config || !o || !out) throw std::invalid_argument("kwh_angular_time_create: NULL argument");
+  *out = nullptr;
+  std::unique_ptr<kwh_angular_time> s(new kwh_angular_time());
+  s->params = kwh_angular_time_parameters(config, o);
+  try { s->projector.reset(new AngularSpectrumTime(s->params)); }
+  catch (const CwDeviceError& e) { g_err = e.what(); return static_cast<int>(e.status); } // KW_ERR_NO_DEVICE among them
+  *out = s.release();
+  KWH_CATCH
+}
+
+int kwh_angular_time_destroy(kwh_angular_time* s)
+{
+  KWH_TRY
+  delete s;
+  KWH_CATCH
+}
+
+int kwh_angular_time_set_input(kwh_angular_time* s, const float* p0)
+{
+  KWH_TRY
+  if (!s || !p0) throw std::invalid_argument("kwh_angular_time_set_input: NULL argument");
+  s->projector->setInput(p0);
+  KWH_CATCH
+}
+
+int kwh_angular_time_run(kwh_angular_time* s, const float* p0)
+{
+  KWH_TRY
+  if (!s || !p0) throw std::invalid_argument("kwh_angular_time_run: NULL argument");
+  s->projector->run(p0);
+  KWH_CATCH
+}
+
+int kwh_angular_time_get(kwh_angular_time* s, const char* name, float* dst, uint64_t n)
+{
+  KWH_TRY
+  if (!s || !name || !dst) throw std::invalid_argument("kwh_angular_time_get: NULL argument");
+  s->projector->get(name, dst, n);
+  KWH_CATCH
+}
+
+int kwh_angular_time_series(kwh_angular_time* s, uint64_t j, float* dst, uint64_t n)
+{
+  KWH_TRY
+  if (!s || !dst) throw std::invalid_argument("kwh_angular_time_series: NULL argument");
+  s->projector->series(j, dst, n);
+  KWH_CATCH
+}
+
+int kwh_angular_time_project(kwh_angular_time* s)
+{
+  KWH_TRY
+  if (!s) throw std::invalid_argument("kwh_angular_time_project: NULL projector");
+  s->projector->project();
+  KWH_CATCH
+}
+
+int kwh_angular_time_get_scalar(kwh_angular_time* s, const char* name, double* out)
+{
+  KWH_TRY
+  if (!s || !name || !out) throw std::invalid_argument("kwh_angular_time_get_scalar: NULL argument");
+  const std::string n(name);
+  const AngularTimeParameters& p = s->projector->parameters();
+  if (n == "fused_pipeline") *out = s->projector->usesFusedPipeline() ? 1.0 : 0.0;
+  else if (n == "Ex") *out = static_cast<double>(p.ex);
+  else if (n == "Ey") *out = static_cast<double>(p.ey);
+  else if (n == "Lt") *out = static_cast<double>(p.lt);
+  else if (n == "planes") *out = static_cast<double>(p.z.size());
+  else if (n == "runs") *out = static_cast<double>(s->projector->runs());
+  else throw std::invalid_argument(std::string("unknown scalar ") + name);
+  KWH_CATCH
+}
+
+void* kwh_angular_time_context(kwh_angular_time* s) { return s ? s->projector->context() : nullptr; }
 }
