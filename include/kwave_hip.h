@@ -860,6 +860,52 @@ KW_API kw_status kw_angular_time_embed(kw_ctx* ctx, float* vol, const float* src
 KW_API kw_status kw_angular_time_reduce(kw_ctx* ctx, const float* vol, uint32_t ex, uint32_t ey, uint32_t lt, uint32_t nx,
                                         uint32_t ny, uint32_t nt, float* p_max, float* p_min, float* series);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * k-space plane reconstruction (what k-Wave's kspacePlaneRecon computes): the record p[t][y][x] of a planar sensor to the
+ * initial pressure p0[z][y][x] that produced it, homogeneous medium (csrc/kw_plane_recon.hip, host/PlaneRecon.cpp, DESIGN.md
+ * "k-space plane reconstruction").  The grid of kw_set_constants is (nx, ny, nz) = (Ex, Ey, Lt), the time axis where the
+ * pipeline has z.  The record is embedded, mirrored in time, in a zero volume v [Lt][Ey][Ex], Lt >= 2 Nt - 1:
+ *     v[n] = p[n], 0 <= n < Nt;   v[Lt - n] = p[n], 1 <= n < Nt                     (even in t with period Lt)
+ *     out = crop( positivity( 2 irfftn(G) ) )          axes (t -> z, y, x);  plane j at z_j = j c0 dt,  j < planes <= Nt
+ *     S = fftn(v);  M = floor(Lt / 2);  m' = min(m, Lt - m);  bins are counted k? = 2 pi / (E? d?) * min(i, E? - i)
+ *     dk = 2 pi / (Lt dt c0);  rho2 = (kx^2 + ky^2) / dk^2
+ *     T[m'] = S[m'] w(m'):  w = sqrt(m'^2 - rho2) / m' where m'^2 >= rho2 and m' > 0;  w(0) = 1 if rho2 = 0;  else w = 0
+ *     f = sqrt(m'^2 + rho2),  i0 = floor(f),  a = f - i0
+ *     linear :  G[m] = T[i0] + a (T[min(i0 + 1, M)] - T[i0])          nearest:  G[m] = T[i0] if a < 1/2 else T[min(i0 + 1, M)]
+ *     G[m] = 0 where f > M
+ * The re-gridding from w to kz moves data between the bins of one (kx, ky) line; c0 enters through rho2 only.
+ *
+ * Per bin, TWO device functions shared by the fused kernel and the twin, without contraction into fma:
+ *   float64: kx, ky from the bin counts;  kr2 = (kx*kx) + (ky*ky);  rho2 = kr2 / (dk*dk);  mm = double(m') * double(m');
+ *            recon_w: d = mm - rho2, sqrt(d);   recon_f: f = sqrt(mm + rho2);   i0 = uint32(f);  f > M tested in float64
+ *   float32: w = (float(sqrt(d)) / float(m')) * scale (d >= 0, m' > 0), scale (m' = 0, rho2 = 0), else 0;  scale = 2 / (Lt Ey Ex);
+ *            T = (w * S.x, w * S.y);  a = float(f - double(i0));  G = (a * (T1 - T0)) + T0 per component, or the pick at a < 0.5f
+ *
+ * kw_fused_plane_recon: vol_out [nz][ny][nx] <- 2 irfftn(G) of vol_even [nz][ny][nx]: x-forward and y-forward of the one array,
+ *   ONE launch k_zfused_recon (lines forward along t; T written back into the exchange buffer; a barrier; every bin gathers
+ *   T[i0], T[i0 + 1] of its own line from LDS; inverse along t — no operator array, no index table in memory), the y-inverse
+ *   and the storing x-inverse.  vol_out may be vol_even.  Single GPU, nz > 1: KW_ERR_INVALID in slab mode or for Nz == 1.
+ *   The stage does NOT check that vol_even is even in t: for a volume that is not, S[m] != S[Lt - m], the spectrum handed to
+ *   the real inverse is not Hermitian and the result is not the inverse transform of G.
+ * kw_plane_recon_mix: the twin: out_spec <- G on the natural [nz][ny][nx/2 + 1] half-spectrum of kw_fft_r2c_3d, out of place
+ *   (it gathers), for kw_fft_c2r_3d (grids off the fast path; any nx, ny, nz, odd ones included).  A context without bins:
+ *   KW_OK, nothing launched.
+ * kw_plane_recon_embed: vol [lt][ey][ex] <- the mirrored embedding of src [nt][ny][nx], zero elsewhere; lt >= 2 nt - 1.
+ * kw_plane_recon_crop: out [planes][ny][nx] <- the corner of vol [lt][ey][ex], planes <= lt; positivity != 0: x > 0 ? x : 0.
+ *   Both exact; 16-byte accesses when ex and nx are multiples of 4 and the pointers are 16-byte aligned; zero points: KW_OK.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct kw_plane_recon_op {
+  double  dx, dy, dt, c0;             /* [m], [m], [s], [m/s] */
+  int32_t interp;                     /* 0 = linear, 1 = nearest */
+  int32_t reserved;                   /* 0 */
+} kw_plane_recon_op;
+KW_API kw_status kw_fused_plane_recon(kw_ctx* ctx, const float* vol_even, const kw_plane_recon_op* op, float* vol_out);
+KW_API kw_status kw_plane_recon_mix(kw_ctx* ctx, float* out_spec, const float* spec, const kw_plane_recon_op* op, float scale);
+KW_API kw_status kw_plane_recon_embed(kw_ctx* ctx, float* vol, const float* src, uint32_t ex, uint32_t ey, uint32_t lt,
+                                      uint32_t nx, uint32_t ny, uint32_t nt);
+KW_API kw_status kw_plane_recon_crop(kw_ctx* ctx, float* out, const float* vol, uint32_t ex, uint32_t ey, uint32_t lt,
+                                     uint32_t nx, uint32_t ny, uint32_t planes, int32_t positivity);
+
 #ifdef __cplusplus
 }
 #endif

@@ -374,6 +374,49 @@ KWH_API int      kwh_angular_time_get_scalar(kwh_angular_time* s, const char* na
 /* the underlying kw_ctx* (include/kwave_hip.h) */
 KWH_API void*    kwh_angular_time_context(kwh_angular_time* s);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * k-space plane reconstruction (what k-Wave's kspacePlaneRecon computes): the record p[t][y][x] of a planar sensor, sampled
+ * at t_n = n dt, to the initial pressure p0 on the planes z_j = j c0 dt, j < planes <= Nt, of a homogeneous medium: one 3-D
+ * FFT of the record mirrored in time, a re-gridding of every (kx, ky) line from w to kz with a weight, one inverse 3-D FFT
+ * (kwave_hip.h "k-space plane reconstruction").  The result is planes x Ny x Nx on the domain.
+ *   E (0 0 = default): the expanded sides; default (Nx, Ny), k-Wave's choice.  Given sides are not below N.
+ *   lt (0 = default): the length of the mirrored record; default the smallest fast-path length at or above 2 Nt - 1, or
+ *   2 Nt - 1 itself (odd, k-Wave's grid) when there is none (above 1024) or with fused_kernels off.  A given lt is not
+ *   below 2 Nt - 1.  The fused stage runs when Ex, Ey and Lt are all fast-path lengths, the rocFFT twin otherwise.
+ *   planes (0 = Nt).  interp: 0 linear, 1 nearest.  positivity != 0: the result is clamped at 0.
+ * Refused, naming the parameter: Nx Ny Nt (0), dx dy dt c0 (not positive), planes (above Nt), interp (neither), Ex Ey
+ * (missing, below N), Lt (below 2 Nt - 1), E (2^32 points or more).
+ * Of kwh_options the calls read device_idx and fused_kernels.  kwh_plane_recon_plan validates and completes (Ex, Ey, Lt)
+ * without a device.  Not built: 2-D (kspaceLineRecon), heterogeneous media, Z-slabs, HDF5 files and the command line,
+ * graphs, a half-length (DCT) time transform that would use the evenness, the x- and y-inverse restricted to the crop,
+ * other interpolants.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct kwh_plane_recon kwh_plane_recon;
+typedef struct kwh_plane_recon_config
+{
+  uint64_t nx, ny, nt;      /* the record */
+  double   dx, dy, dt;      /* [m], [m], [s] */
+  double   c0;              /* [m/s] */
+  uint64_t ex, ey;          /* expanded sides; 0 0 = default */
+  uint64_t lt;              /* length of the mirrored record; 0 = default */
+  uint64_t planes;          /* 1 ... Nt; 0 = Nt */
+  int32_t  interp;          /* 0 = linear, 1 = nearest */
+  int32_t  positivity;
+} kwh_plane_recon_config;
+KWH_API int      kwh_plane_recon_plan(const kwh_plane_recon_config* config, const kwh_options* options,
+                                      uint64_t out_expanded[3], int32_t* out_fast_path);
+KWH_API int      kwh_plane_recon_create(const kwh_plane_recon_config* config, const kwh_options* options,
+                                        kwh_plane_recon** out);
+KWH_API int      kwh_plane_recon_destroy(kwh_plane_recon* s);
+/* p: Nx * Ny * Nt floats on the host ([Nt][Ny][Nx]); the result [planes][Ny][Nx] stays on the device */
+KWH_API int      kwh_plane_recon_run(kwh_plane_recon* s, const float* p);
+/* "p0" of the last run; n = Nx * Ny * planes (checked) */
+KWH_API int      kwh_plane_recon_get(kwh_plane_recon* s, const char* name, float* dst, uint64_t n);
+/* "fused_pipeline", "Ex", "Ey", "Lt", "planes", "dz", "runs" */
+KWH_API int      kwh_plane_recon_get_scalar(kwh_plane_recon* s, const char* name, double* out);
+/* the underlying kw_ctx* (include/kwave_hip.h) */
+KWH_API void*    kwh_plane_recon_context(kwh_plane_recon* s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -208,7 +208,17 @@ _SIG: Dict[str, list] = {
     "kw_angular_time_mix": [_P, _P, _P, _P, C.c_float],
     "kw_angular_time_embed": [_P, _P, _P] + [C.c_uint32] * 6,
     "kw_angular_time_reduce": [_P, _P] + [C.c_uint32] * 6 + [_P, _P, _P],
+    "kw_fused_plane_recon": [_P, _P, _P, _P],
+    "kw_plane_recon_mix": [_P, _P, _P, _P, C.c_float],
+    "kw_plane_recon_embed": [_P, _P, _P] + [C.c_uint32] * 6,
+    "kw_plane_recon_crop": [_P, _P, _P] + [C.c_uint32] * 6 + [C.c_int32],
 }
+
+class PlaneReconOp(C.Structure):
+    """struct kw_plane_recon_op: the grid steps and the interpolant of the k-space plane reconstruction"""
+    _fields_ = [("dx", C.c_double), ("dy", C.c_double), ("dt", C.c_double), ("c0", C.c_double),
+                ("interp", C.c_int32), ("reserved", C.c_int32)]
+
 
 class AngularTimeOp(C.Structure):
     """struct kw_angular_time_op: H of one plane of the time-domain angular-spectrum projector"""

@@ -160,6 +160,17 @@ struct ZTimeArgs
   uint32_t      restriction, retarded;
 };
 
+// the z-pass of the k-space plane reconstruction (kw_plane_recon.hip): weight and gather along the line, formed per bin
+struct ZReconArgs
+{
+  float2*       s;    // scratch array 0, in place (rows [t][ky][P], side array at side_off)
+  const float2* tw;
+  double        dkx, dky, dk2; // 2 pi / (Ex dx), 2 pi / (Ey dy), (2 pi / (Lt dt c0))^2
+  float         scale;         // 2 / (Ex Ey Lt)
+  uint32_t      nxc, P, ex, ny, nz, side_off; // ex = Ex (the bin counts along x)
+  uint32_t      nearest;
+};
+
 struct XshiftArgs
 {
   const float*  in;
@@ -203,6 +214,9 @@ kw_status yinv_angular(kw_ctx* ctx, AngArgs a);
 // the z-pass of kw_fused_angular_time_plane: one spectrum forward along t, H of the plane formed in registers, the inverse
 // (kw_angular_time.hip): lines of `in` (the kept spectrum) to `out`
 kw_status zfused_time(kw_ctx* ctx, const float2* in, float2* out, const kw_angular_time_op* op);
+// the z-pass of kw_fused_plane_recon: lines of `s` forward along t, the weight, the gather from w to kz along each line,
+// the inverse, in place (kw_plane_recon.hip)
+kw_status zfused_recon(kw_ctx* ctx, float2* s, const kw_plane_recon_op* op);
 // the tuning probes of kw_fused_probe that launch no pipeline kernel (kw_fused_probe.hip)
 kw_status probe_patterns(kw_ctx* ctx, int which, const float* op);
 

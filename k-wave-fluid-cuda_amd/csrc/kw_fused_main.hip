@@ -1506,6 +1506,31 @@ kw_status kw_fused_angular_time_plane(kw_ctx* ctx, const float* kept, const kw_a
 }
 #undef KW_ANGULAR_TIME_3D
 
+// k-space plane reconstruction (kw_plane_recon.hip): kw_fused_scale_source's round trip with k_zfused_recon as its z-pass —
+// the weight and the gather from w to kz happen along the line the z-pass holds in LDS.
+kw_status kw_fused_plane_recon(kw_ctx* ctx, const float* vol_even, const kw_plane_recon_op* op, float* vol_out)
+{
+  KW_FUSED_READY(ctx);
+  KW_PROF(ctx, "fused_plane_recon");
+  KW_REQUIRE(vol_even && op && vol_out);
+  if (ctx->fused.slab || ctx->fused.two_d)
+  {
+    kw_set_error("kw_fused_plane_recon: single GPU and 3-D only (no Z-slabs, no Nz == 1)");
+    return KW_ERR_INVALID;
+  }
+  KW_REQUIRE(op->dx > 0.0 && op->dy > 0.0 && op->dt > 0.0 && op->c0 > 0.0 && (op->interp == 0 || op->interp == 1));
+  float2** S = ctx->fused.s;
+  const float* in1[1] = { vol_even };
+  KW_TRY(forward_xy(ctx, 1, in1));
+  KW_TRY(zfused_recon(ctx, S[0], op));
+  KW_TRY(inverse_y(ctx, 1));
+  XinvArgs x{};
+  x.in[0]  = S[0];
+  x.out[0] = vol_out;
+  KW_TRY(launch_xinv<EPI_STORE>(ctx, 1, x));
+  return KW_OK;
+}
+
 // Pass-level probe for tuning (tools/probe_passes.py): launches ONE pass over the scratch arrays, no physics.
 //   0: y-pass forward on s[0] (in place)          1: the same line kernel along z (stride ny*P) on s[0]
 //   2: z-fused (forward, x sourceKappa-style multiply with op, inverse) on s[0]   3: y-pass on s[0..2] (3 arrays)

@@ -1,0 +1,368 @@
+// kw_plane_recon.hip — device code of the k-space plane reconstruction (DESIGN.md "k-space plane reconstruction"): the
+// record p[t][y][x] of a planar sensor, embedded mirrored in time in a volume [Lt][Ey][Ex], to the initial pressure
+//   p0 = 2 irfftn(G),   G[m] = interpolation of T = S w at f = sqrt(m'^2 + rho2) along the temporal axis of S = fftn(v)
+// (kwave_hip.h documents the definition and the order of the arithmetic).  The re-gridding from w to kz moves data between
+// the bins of one (kx, ky) line — the line the z-pass of the fused pipeline holds in LDS.
+//
+//   recon_w / recon_f    weight and gather position of one bin: shared by the fused kernel and the twin
+//   k_zfused_recon       the z-pass of kw_fused_plane_recon (kw_fused_main.hip): lines of scratch array 0 forward along t,
+//                        T written back into the exchange buffer, the gather from LDS, inverse along t, in place — no
+//                        operator array and no index table in memory
+//   kw_plane_recon_mix   the same on the natural [Lt][Ey][Ex/2 + 1] spectrum of kw_fft_r2c_3d (rocFFT path, and the twin)
+//   kw_plane_recon_embed / _crop   the mirrored embedding of the record; the first planes of the domain crop, clamped on request
+#include "kw_fused.hip"
+
+namespace {
+
+constexpr int kBlocksPerCu = 8;
+
+inline unsigned capped_grid(const kw_ctx* ctx, uint64_t work)
+{
+  uint64_t       g   = (work + 255) / 256;
+  const uint64_t cap = static_cast<uint64_t>(ctx->cu_count) * kBlocksPerCu;
+  if (g > cap) g = cap;
+  if (g == 0) g = 1;
+  return static_cast<unsigned>(g);
+}
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+constexpr double kTwoPi = 6.283185307179586476925286766559;
+
+// (kx^2 + ky^2) / dk^2 of column ix (0 ... Ex/2) and row iy, float64
+__device__ __forceinline__ double recon_rho2(double dkx, double dky, double dk2, uint32_t ex, uint32_t ey, uint32_t ix, uint32_t iy)
+{
+#pragma clang fp contract(off)
+  const double kx = dkx * static_cast<double>(ix <= ex / 2 ? ix : ex - ix);
+  const double ky = dky * static_cast<double>(iy <= ey / 2 ? iy : ey - iy);
+  return ((kx * kx) + (ky * ky)) / dk2;
+}
+
+// w(rho2, m') * scale: sqrt(m'^2 - rho2) / m' on the propagating side, 1 at the origin, 0 elsewhere.  float64 up to the
+// square root, float32 from there; no contraction.  Real calls, not inlined, as time_h (kw_angular_time.hip): unrolled
+// over the R2 bins of a thread the float64 square roots would be scheduled side by side and cost the z-pass its registers.
+__device__ __attribute__((noinline)) float recon_w(double rho2, uint32_t mp, float scale)
+{
+#pragma clang fp contract(off)
+  const double md = static_cast<double>(mp);
+  const double d  = (md * md) - rho2;
+  if (mp == 0) return rho2 == 0.0 ? scale : 0.f;
+  if (d < 0.0) return 0.f;
+  return (static_cast<float>(sqrt(d)) / static_cast<float>(mp)) * scale;
+}
+
+// the gather position f = sqrt(m'^2 + rho2) of bin m', float64
+__device__ __attribute__((noinline)) double recon_f(double rho2, uint32_t mp)
+{
+#pragma clang fp contract(off)
+  const double md = static_cast<double>(mp);
+  return sqrt((md * md) + rho2);
+}
+
+__device__ __forceinline__ float2 recon_scale(const float2& x, float w)
+{
+#pragma clang fp contract(off)
+  return make_float2(w * x.x, w * x.y);
+}
+
+// G from the two neighbours T0 = T[i0], T1 = T[min(i0 + 1, M)] and a = f - i0
+__device__ __forceinline__ float2 recon_pick(const float2& t0, const float2& t1, float a, bool nearest)
+{
+#pragma clang fp contract(off)
+  if (nearest) return a < 0.5f ? t0 : t1;
+  return make_float2((a * (t1.x - t0.x)) + t0.x, (a * (t1.y - t0.y)) + t0.y);
+}
+
+// =====================================================================================================================
+// z-pass of the reconstruction: tile (ky = blockIdx.y, kx tile = blockIdx.x; the side array's blocks as in tile_coord) of
+// scratch array 0, in place.  k_zfused_time's geometry, addressing and exchange; between the forward and the inverse
+// transform, where thread (c, j) holds the bins m = j + R1 k2 of column c:
+//   1. it writes T[m] = w X[m] back into row j of the exchange buffer, at the cell of bin m
+//      (lds[(m % R1) SF + (m / R1) NL + c]) — the cells it read last itself, so no barrier is needed before the write
+//   2. a barrier
+//   3. it gathers T[i0] and T[min(i0 + 1, M)] of its own column for each of its bins and forms G; only cells of bins
+//      m' <= M are read (the cells of the upper half are written and never looked at: T[m'] is the lower half's)
+//   4. a second barrier, before inverse_from_regs overwrites the buffer
+// No LDS beyond Geo::LDSB, nothing read from memory but the lines.
+// =====================================================================================================================
+template<int L> __global__ __launch_bounds__((Geo<L, nl_z(L)>::THREADS)) void k_zfused_recon(ZReconArgs a)
+{
+  using G = Geo<L, nl_z(L)>;
+  constexpr int R1 = G::R1, R2 = G::R2;
+  constexpr bool WA = (R2 == G::TPL) || ((G::NL * R2) % 64 == 0 && 64 % G::NL == 0); // step-A participants: whole waves
+  constexpr uint32_t M = L / 2;
+  __shared__ float2 lds[G::LDSB];
+  __shared__ float2 twl[G::TWN];
+  load_twiddles<L>(twl, a.tw);
+  const int       c     = threadIdx.x % G::NL;
+  const int       j     = threadIdx.x / G::NL;
+  const TileCoord tc    = tile_coord<G::NL>(a.nxc, a.P, a.side_off, gridDim.y, c);
+  if (tc.dead) return;
+  const uint32_t ky     = tc.pos;
+  const bool     valid  = tc.valid;
+  const uint32_t zstr   = a.ny * tc.pitch;
+  const uint32_t base   = ky * tc.pitch + (tc.side ? 0u : tc.kx) + tc.off;
+  const uint32_t basel  = ky * tc.pitch + tc.col + tc.off;
+
+  float2 v[R1];
+  if (ACTW(R2, j))
+  {
+    const float2* in = a.s;
+    const uint32_t lb = (basel + static_cast<uint32_t>(j) * zstr) * static_cast<uint32_t>(sizeof(float2));
+#pragma unroll
+    for (int n1 = 0; n1 < R1; n1++) v[n1] = ld_uni<WA>(in, static_cast<uint64_t>(n1 * R2) * zstr, lb);
+  }
+  lds_barrier(); // twiddle table visible (the loads above stay in flight across it)
+
+  if (ACTW(R2, j))
+  {
+    step_a<L, kFwd>(v, j, twl);
+#pragma unroll
+    for (int k1 = 0; k1 < R1; k1++) lds[k1 * G::SF + j * G::NL + c] = v[k1];
+  }
+  lds_barrier();
+  float2 X[R2];
+  // the true column: the side array holds bin Ex/2 = a.nxc; pad lanes (never stored) take the last main column
+  const double rho2 = recon_rho2(a.dkx, a.dky, a.dk2, a.ex, a.ny, tc.side ? a.nxc : tc.col, ky);
+  if (ACTW(R1, j))
+  {
+#pragma unroll
+    for (int n2 = 0; n2 < R2; n2++) X[n2] = lds[j * G::SF + n2 * G::NL + c];
+    Dft<R2, kFwd>::run(X);
+#pragma unroll
+    for (int k2 = 0; k2 < R2; k2++)
+    {
+      const uint32_t m  = static_cast<uint32_t>(j + R1 * k2);
+      const uint32_t mp = m <= M ? m : static_cast<uint32_t>(L) - m;
+      lds[j * G::SF + k2 * G::NL + c] = recon_scale(X[k2], recon_w(rho2, mp, a.scale));
+    }
+  }
+  lds_barrier(); // T of the whole line is in the buffer
+  if (ACTW(R1, j))
+  {
+    const bool nearest = a.nearest != 0;
+#pragma unroll
+    for (int k2 = 0; k2 < R2; k2++)
+    {
+      const uint32_t m  = static_cast<uint32_t>(j + R1 * k2);
+      const uint32_t mp = m <= M ? m : static_cast<uint32_t>(L) - m;
+      const double   f  = recon_f(rho2, mp);
+      const bool     in = f <= static_cast<double>(M);
+      // (f > M: the indices are clamped into the line and the value dropped)
+      const uint32_t i0 = in ? static_cast<uint32_t>(f) : M;
+      const uint32_t i1 = i0 + 1u <= M ? i0 + 1u : M;
+      const float    al = static_cast<float>(f - static_cast<double>(i0));
+      const float2   t0 = lds[(i0 % R1) * G::SF + (i0 / R1) * G::NL + c];
+      const float2   t1 = lds[(i1 % R1) * G::SF + (i1 / R1) * G::NL + c];
+      const float2   g  = recon_pick(t0, t1, al, nearest);
+      X[k2] = in ? g : make_float2(0.f, 0.f);
+    }
+  }
+  lds_barrier(); // every gather is done before the inverse overwrites the buffer
+
+  float2 r[R1];
+  inverse_from_regs<L, false, G::NL>(X, r, lds, c, j, twl);
+  if (ACTW(R2, j) && valid)
+  {
+    float2* out = a.s;
+    uint32_t ob = base + static_cast<uint32_t>(j) * zstr;
+    asm volatile("" : "+v"(ob));
+#pragma unroll
+    for (int q2 = 0; q2 < R1; q2++) st_uni<WA>(out, static_cast<uint64_t>(R2 * q2) * zstr, ob * static_cast<uint32_t>(sizeof(float2)), r[q2]);
+  }
+}
+
+struct ReconMix
+{
+  double   dkx, dky, dk2;
+  float    scale;
+  uint32_t ex, ey, lt;
+  uint32_t nearest;
+};
+
+// the rocFFT twin: out[m] = G[m] of the line (ix, iy) of the natural [lt][ey][ex/2 + 1] half-spectrum, out of place
+__global__ __launch_bounds__(256) void k_plane_recon_mix(float2* __restrict__ out, const float2* __restrict__ spec, ReconMix g)
+{
+  const uint32_t nxc = g.ex / 2 + 1;
+  const uint64_t pl  = static_cast<uint64_t>(nxc) * g.ey;
+  const uint64_t n   = pl * g.lt;
+  const uint32_t M   = g.lt / 2;
+  const bool nearest = g.nearest != 0;
+  for (uint64_t e = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; e < n;
+       e += static_cast<uint64_t>(gridDim.x) * blockDim.x)
+  {
+    const uint32_t ix = static_cast<uint32_t>(e % nxc);
+    const uint64_t r  = e / nxc;
+    const uint32_t iy = static_cast<uint32_t>(r % g.ey), m = static_cast<uint32_t>(r / g.ey);
+    const uint64_t col = e - static_cast<uint64_t>(m) * pl;
+    const uint32_t mp  = m <= M ? m : g.lt - m;
+    const double rho2 = recon_rho2(g.dkx, g.dky, g.dk2, g.ex, g.ey, ix, iy);
+    const double f    = recon_f(rho2, mp);
+    float2 res = make_float2(0.f, 0.f);
+    if (f <= static_cast<double>(M))
+    {
+      const uint32_t i0 = static_cast<uint32_t>(f);
+      const uint32_t i1 = i0 + 1u <= M ? i0 + 1u : M;
+      const float    al = static_cast<float>(f - static_cast<double>(i0));
+      const float2   t0 = recon_scale(spec[col + static_cast<uint64_t>(i0) * pl], recon_w(rho2, i0, g.scale));
+      const float2   t1 = recon_scale(spec[col + static_cast<uint64_t>(i1) * pl], recon_w(rho2, i1, g.scale));
+      res = recon_pick(t0, t1, al, nearest);
+    }
+    out[e] = res;
+  }
+}
+
+struct ReconDims { uint32_t ex, ey, lt, nx, ny, nt; };
+
+// vol [lt][ey][ex] <- src [nt][ny][nx] mirrored in time (rows t and lt - t take src[t]), zero elsewhere; V = 4: 16-byte
+// accesses (ex, nx multiples of 4).  lt >= 2 nt - 1: no row is claimed twice.
+template<int V> __global__ __launch_bounds__(256) void k_recon_embed(float* __restrict__ vol, const float* __restrict__ src, ReconDims d)
+{
+  const uint32_t exv = d.ex / V;
+  const uint64_t n   = static_cast<uint64_t>(exv) * d.ey * d.lt;
+  for (uint64_t e = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; e < n;
+       e += static_cast<uint64_t>(gridDim.x) * blockDim.x)
+  {
+    const uint32_t ix = static_cast<uint32_t>(e % exv) * V;
+    const uint64_t r  = e / exv;
+    const uint32_t iy = static_cast<uint32_t>(r % d.ey), t = static_cast<uint32_t>(r / d.ey);
+    const uint32_t ts = t < d.nt ? t : d.lt - t; // the source row: t itself, or its mirror image
+    const bool inside = ix < d.nx && iy < d.ny && ts < d.nt;
+    const uint64_t s  = (static_cast<uint64_t>(ts) * d.ny + iy) * d.nx + ix;
+    if constexpr (V == 4)
+    {
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (inside) v = *reinterpret_cast<const float4*>(src + s);
+      *reinterpret_cast<float4*>(vol + e * 4) = v;
+    }
+    else vol[e] = inside ? src[s] : 0.f;
+  }
+}
+
+__device__ __forceinline__ float recon_clamp(float x, bool positivity) { return (positivity && !(x > 0.f)) ? 0.f : x; }
+
+// out [nt][ny][nx] <- the corner of vol [lt][ey][ex] (nt = the planes), clamped at 0 on request
+template<int V> __global__ __launch_bounds__(256) void k_recon_crop(float* __restrict__ out, const float* __restrict__ vol, ReconDims d,
+                                                                    int positivity)
+{
+  const uint32_t nxv = d.nx / V;
+  const uint64_t n   = static_cast<uint64_t>(nxv) * d.ny * d.nt;
+  const bool     pos = positivity != 0;
+  for (uint64_t e = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; e < n;
+       e += static_cast<uint64_t>(gridDim.x) * blockDim.x)
+  {
+    const uint32_t ix = static_cast<uint32_t>(e % nxv) * V;
+    const uint64_t r  = e / nxv;
+    const uint32_t iy = static_cast<uint32_t>(r % d.ny), t = static_cast<uint32_t>(r / d.ny);
+    const uint64_t s  = (static_cast<uint64_t>(t) * d.ey + iy) * d.ex + ix;
+    if constexpr (V == 4)
+    {
+      float4 q = *reinterpret_cast<const float4*>(vol + s);
+      q.x = recon_clamp(q.x, pos); q.y = recon_clamp(q.y, pos); q.z = recon_clamp(q.z, pos); q.w = recon_clamp(q.w, pos);
+      *reinterpret_cast<float4*>(out + e * 4) = q;
+    }
+    else out[e] = recon_clamp(vol[s], pos);
+  }
+}
+
+bool op_ok(const kw_plane_recon_op* op)
+{
+  return op->dx > 0.0 && op->dy > 0.0 && op->dt > 0.0 && op->c0 > 0.0 && (op->interp == 0 || op->interp == 1);
+}
+
+} // namespace
+
+namespace kwfused {
+
+// the z-pass of kw_fused_plane_recon: the lines of `s` in place
+kw_status zfused_recon(kw_ctx* ctx, float2* s, const kw_plane_recon_op* op)
+{
+  const auto& f = ctx->fused;
+  const kw_constants& c = ctx->c;
+  KW_PROF(ctx, "k_zfused_recon");
+  const double dk = kTwoPi / (static_cast<double>(c.nz) * op->dt * op->c0);
+  ZReconArgs a{};
+  a.s   = s;
+  a.tw  = f.tw[2];
+  a.dkx = kTwoPi / (static_cast<double>(c.nx) * op->dx);
+  a.dky = kTwoPi / (static_cast<double>(c.ny) * op->dy);
+  a.dk2 = dk * dk;
+  a.scale    = static_cast<float>(2.0 / (static_cast<double>(c.nx) * c.ny * c.nz));
+  a.nxc      = f.nxm;
+  a.P        = f.P;
+  a.ex       = c.nx;
+  a.ny       = c.ny;
+  a.nz       = c.nz;
+  a.side_off = f.side_off;
+  a.nearest  = op->interp == 1 ? 1u : 0u;
+  const uint32_t side_tile = (f.side_off != 0) ? 1u : 0u;
+  const dim3 grid(z_tiles(f.P, c.nz) + side_tile, c.ny, 1);
+#define M(LEN) LAUNCH((k_zfused_recon<LEN>), grid, dim3((Geo<LEN, nl_z(LEN)>::THREADS)), a)
+  KW_LEN_SWITCH(c.nz, M)
+#undef M
+  return KW_OK;
+}
+
+} // namespace kwfused
+
+extern "C" {
+
+kw_status kw_plane_recon_mix(kw_ctx* ctx, float* out_spec, const float* spec, const kw_plane_recon_op* op, float scale)
+{
+  KW_CHECK_CTX(ctx);
+  KW_PROF(ctx, "plane_recon_mix");
+  const kw_constants& c = ctx->c; // (a context without constants has no bins)
+  const uint64_t n = ctx->have_consts ? static_cast<uint64_t>(c.nx / 2 + 1) * c.ny * c.nz : 0;
+  if (n == 0) return KW_OK;
+  KW_REQUIRE(out_spec && spec && op && out_spec != spec);
+  KW_REQUIRE(op_ok(op));
+  const double dk = kTwoPi / (static_cast<double>(c.nz) * op->dt * op->c0);
+  ReconMix g{};
+  g.dkx = kTwoPi / (static_cast<double>(c.nx) * op->dx);
+  g.dky = kTwoPi / (static_cast<double>(c.ny) * op->dy);
+  g.dk2 = dk * dk;
+  g.scale = scale;
+  g.ex = c.nx; g.ey = c.ny; g.lt = c.nz;
+  g.nearest = op->interp == 1 ? 1u : 0u;
+  hipLaunchKernelGGL(k_plane_recon_mix, dim3(capped_grid(ctx, n)), dim3(256), 0, ctx->stream,
+                     reinterpret_cast<float2*>(out_spec), reinterpret_cast<const float2*>(spec), g);
+  KW_LAUNCH_CHECK();
+  return KW_OK;
+}
+
+kw_status kw_plane_recon_embed(kw_ctx* ctx, float* vol, const float* src, uint32_t ex, uint32_t ey, uint32_t lt, uint32_t nx,
+                               uint32_t ny, uint32_t nt)
+{
+  KW_CHECK_CTX(ctx);
+  KW_PROF(ctx, "plane_recon_embed");
+  const uint64_t n = static_cast<uint64_t>(ex) * ey * lt;
+  if (n == 0) return KW_OK;
+  KW_REQUIRE(nx <= ex && ny <= ey && (nt == 0 || 2ull * nt - 1ull <= lt));
+  KW_REQUIRE(vol != nullptr);
+  const uint64_t nd = static_cast<uint64_t>(nx) * ny * nt;
+  KW_REQUIRE(nd == 0 || src != nullptr);
+  const ReconDims d{ ex, ey, lt, nx, ny, nd == 0 ? 0u : nt };
+  const bool v4 = ex % 4 == 0 && nx % 4 == 0 && aligned16(vol) && aligned16(src);
+  if (v4) hipLaunchKernelGGL(k_recon_embed<4>, dim3(capped_grid(ctx, n / 4)), dim3(256), 0, ctx->stream, vol, src, d);
+  else hipLaunchKernelGGL(k_recon_embed<1>, dim3(capped_grid(ctx, n)), dim3(256), 0, ctx->stream, vol, src, d);
+  KW_LAUNCH_CHECK();
+  return KW_OK;
+}
+
+kw_status kw_plane_recon_crop(kw_ctx* ctx, float* out, const float* vol, uint32_t ex, uint32_t ey, uint32_t lt, uint32_t nx,
+                              uint32_t ny, uint32_t planes, int32_t positivity)
+{
+  KW_CHECK_CTX(ctx);
+  KW_PROF(ctx, "plane_recon_crop");
+  const uint64_t n = static_cast<uint64_t>(nx) * ny * planes;
+  if (n == 0) return KW_OK;
+  KW_REQUIRE(nx <= ex && ny <= ey && planes <= lt);
+  KW_REQUIRE(out != nullptr && vol != nullptr);
+  const ReconDims d{ ex, ey, lt, nx, ny, planes };
+  const bool v4 = ex % 4 == 0 && nx % 4 == 0 && aligned16(out) && aligned16(vol);
+  if (v4) hipLaunchKernelGGL(k_recon_crop<4>, dim3(capped_grid(ctx, n / 4)), dim3(256), 0, ctx->stream, out, vol, d, positivity);
+  else hipLaunchKernelGGL(k_recon_crop<1>, dim3(capped_grid(ctx, n)), dim3(256), 0, ctx->stream, out, vol, d, positivity);
+  KW_LAUNCH_CHECK();
+  return KW_OK;
+}
+}

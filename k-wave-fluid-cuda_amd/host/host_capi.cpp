@@ -14,6 +14,7 @@
 #include "AngularSpectrum.h"
 #include "AngularSpectrumTime.h"
 #include "CwPropagator.h"
+#include "PlaneRecon.h"
 #include "kwave_host.h"
 
 static thread_local std::string g_err;
@@ -171,6 +172,30 @@ static AngularTimeParameters kwh_angular_time_parameters(const kwh_angular_time_
     throw std::invalid_argument("n_planes: " + std::to_string(c->n_planes) + " is above " + std::to_string(AngularRule::kMaxPlanes));
   if (c->n_planes != 0 && c->z == nullptr) throw std::invalid_argument("z: NULL with n_planes > 0");
   p.z.assign(c->z, c->z + c->n_planes);
+  AngularOptions opt;
+  opt.deviceIdx    = o->device_idx;
+  opt.fusedKernels = o->fused_kernels != 0;
+  p.init(opt);
+  return p;
+}
+
+/// a k-space plane reconstruction with its completed parameters
+struct kwh_plane_recon
+{
+  PlaneReconParameters        params;
+  std::unique_ptr<PlaneRecon> recon;
+};
+
+static PlaneReconParameters kwh_plane_recon_parameters(const kwh_plane_recon_config* c, const kwh_options* o)
+{
+  PlaneReconParameters p;
+  p.nx = c->nx; p.ny = c->ny; p.nt = c->nt;
+  p.dx = c->dx; p.dy = c->dy; p.dt = c->dt;
+  p.c0 = c->c0;
+  p.ex = c->ex; p.ey = c->ey; p.lt = c->lt;
+  p.planes = c->planes;
+  p.interp = c->interp;
+  p.positivity = c->positivity != 0;
   AngularOptions opt;
   opt.deviceIdx    = o->device_idx;
   opt.fusedKernels = o->fused_kernels != 0;
@@ -795,4 +820,70 @@ int kwh_angular_time_get_scalar(kwh_angular_time* s, const char* name, double* o
 }
 
 void* kwh_angular_time_context(kwh_angular_time* s) { return s ? s->projector->context() : nullptr; }
+
+// ---- k-space plane reconstruction ------------------------------------------------------------------------------------
+int kwh_plane_recon_plan(const kwh_plane_recon_config* config, const kwh_options* o, uint64_t out_expanded[3], int32_t* out_fast_path)
+{
+  KWH_TRY
+  if (!config || !o) throw std::invalid_argument("kwh_plane_recon_plan: NULL argument");
+  const PlaneReconParameters p = kwh_plane_recon_parameters(config, o);
+  if (out_expanded) { out_expanded[0] = p.ex; out_expanded[1] = p.ey; out_expanded[2] = p.lt; }
+  if (out_fast_path) *out_fast_path = p.fastPath ? 1 : 0;
+  KWH_CATCH
+}
+
+int kwh_plane_recon_create(const kwh_plane_recon_config* config, const kwh_options* o, kwh_plane_recon** out)
+{
+  KWH_TRY
+  if (!config || !o || !out) throw std::invalid_argument("kwh_plane_recon_create: NULL argument");
+  *out = nullptr;
+  std::unique_ptr<kwh_plane_recon> s(new kwh_plane_recon());
+  s->params = kwh_plane_recon_parameters(config, o);
+  try { s->recon.reset(new PlaneRecon(s->params)); }
+  catch (const CwDeviceError& e) { g_err = e.what(); return static_cast<int>(e.status); } // KW_ERR_NO_DEVICE among them
+  *out = s.release();
+  KWH_CATCH
+}
+
+int kwh_plane_recon_destroy(kwh_plane_recon* s)
+{
+  KWH_TRY
+  delete s;
+  KWH_CATCH
+}
+
+int kwh_plane_recon_run(kwh_plane_recon* s, const float* p)
+{
+  KWH_TRY
+  if (!s || !p) throw std::invalid_argument("kwh_plane_recon_run: NULL argument");
+  s->recon->run(p);
+  KWH_CATCH
+}
+
+int kwh_plane_recon_get(kwh_plane_recon* s, const char* name, float* dst, uint64_t n)
+{
+  KWH_TRY
+  if (!s || !name || !dst) throw std::invalid_argument("kwh_plane_recon_get: NULL argument");
+  s->recon->get(name, dst, n);
+  KWH_CATCH
+}
+
+int kwh_plane_recon_get_scalar(kwh_plane_recon* s, const char* name, double* out)
+{
+  KWH_TRY
+  if (!s || !name || !out) throw std::invalid_argument("kwh_plane_recon_get_scalar: NULL argument");
+  const std::string n(name);
+  const PlaneReconParameters& p = s->recon->parameters();
+  if (n == "fused_pipeline") *out = s->recon->usesFusedPipeline() ? 1.0 : 0.0;
+  else if (n == "Ex") *out = static_cast<double>(p.ex);
+  else if (n == "Ey") *out = static_cast<double>(p.ey);
+  else if (n == "Lt") *out = static_cast<double>(p.lt);
+  else if (n == "planes") *out = static_cast<double>(p.planes);
+  else if (n == "dz") *out = p.dz();
+  else if (n == "runs") *out = static_cast<double>(s->recon->runs());
+  else throw std::invalid_argument(std::string("unknown scalar ") + name);
+  KWH_CATCH
+}
+
+void* kwh_plane_recon_context(kwh_plane_recon* s) { return s ? s->recon->context() : nullptr; }
 }
