@@ -19,23 +19,10 @@
 // The field is complex but the pipeline is R2C / C2R, and H depends on kx^2 + ky^2 only: the 2x2 mix of kw_cw.hip
 //   Pr^ = Hr Sr^ - Hi Si^        Pi^ = Hi Sr^ + Hr Si^
 // gives Hermitian half-spectra again.
+#include "kw_elementwise.h"
 #include "kw_fused.hip"
 
 namespace {
-
-constexpr int kBlocksPerCu = 8;
-
-inline unsigned capped_grid(const kw_ctx* ctx, uint64_t work)
-{
-  uint64_t       g   = (work + 255) / 256;
-  const uint64_t cap = static_cast<uint64_t>(ctx->cu_count) * kBlocksPerCu;
-  if (g > cap) g = cap;
-  if (g == 0) g = 1;
-  return static_cast<unsigned>(g);
-}
-
-constexpr double kTwoPi = 6.283185307179586476925286766559;
-constexpr double kLog2e = 1.4426950408889634073599246810019;
 
 struct AngOpArgs
 {
@@ -43,14 +30,6 @@ struct AngOpArgs
   uint32_t  nxc, ex, ey, nz, restrict_on;
   double    dkx, dky, k, alpha, z0, dz, half_d2; // half_d2 = D^2 / 2
 };
-
-// fixed-point turns of q * z: round(frac(q z / 2 pi) 2^32) as a wrapping 32-bit word
-__device__ __forceinline__ uint32_t phase_word(double q, double z)
-{
-  const double t = q * z / kTwoPi;
-  const double w = rint((t - floor(t)) * 4294967296.0);
-  return static_cast<uint32_t>(static_cast<uint64_t>(w) & 0xFFFFFFFFull);
-}
 
 __global__ __launch_bounds__(256) void k_angular_operator(AngOpArgs g)
 {
@@ -60,8 +39,8 @@ __global__ __launch_bounds__(256) void k_angular_operator(AngOpArgs g)
   {
 #pragma clang fp contract(off)
     const uint32_t ix = static_cast<uint32_t>(e % g.nxc), iy = static_cast<uint32_t>(e / g.nxc);
-    const double kx  = g.dkx * static_cast<double>(ix <= g.ex / 2 ? ix : g.ex - ix);
-    const double ky  = g.dky * static_cast<double>(iy <= g.ey / 2 ? iy : g.ey - iy);
+    const double kx  = g.dkx * static_cast<double>(kw_folded(ix, g.ex));
+    const double ky  = g.dky * static_cast<double>(kw_folded(iy, g.ey));
     const double kr2 = (kx * kx) + (ky * ky);
     const double k2  = g.k * g.k;
     const double q   = sqrt(fabs(k2 - kr2));
@@ -69,8 +48,8 @@ __global__ __launch_bounds__(256) void k_angular_operator(AngOpArgs g)
     double   b0 = 0.0, b1 = 0.0;
     if (kr2 < k2)
     {
-      a0 = phase_word(q, g.z0);
-      a1 = phase_word(q, g.dz);
+      a0 = kw_phase_word(q * g.z0 / kTwoPi); // the turns of q z
+      a1 = kw_phase_word(q * g.dz / kTwoPi);
       b0 = (g.alpha * g.z0 * g.k / q) * kLog2e;
       b1 = (g.alpha * g.dz * g.k / q) * kLog2e;
     }

@@ -13,25 +13,10 @@
 //   kw_angular_time_embed / _reduce   the record into the corner of the zero-filled volume; max_t, min_t and the series
 //                        of the domain crop
 // One real array is enough: H(-w) = conj H(w) and H depends on kx^2 + ky^2 only, so the half-spectrum stays Hermitian.
+#include "kw_elementwise.h"
 #include "kw_fused.hip"
 
 namespace {
-
-constexpr int kBlocksPerCu = 8;
-
-inline unsigned capped_grid(const kw_ctx* ctx, uint64_t work)
-{
-  uint64_t       g   = (work + 255) / 256;
-  const uint64_t cap = static_cast<uint64_t>(ctx->cu_count) * kBlocksPerCu;
-  if (g > cap) g = cap;
-  if (g == 0) g = 1;
-  return static_cast<unsigned>(g);
-}
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-constexpr double kTwoPi = 6.283185307179586476925286766559;
-constexpr double kLog2e = 1.4426950408889634073599246810019;
 
 // what H needs besides the bin: a plain-data copy of the plane's constants (ZTimeArgs carries the same)
 struct TimeH
@@ -43,19 +28,12 @@ struct TimeH
   uint32_t      restriction, retarded;
 };
 
-// fixed-point turns: round(frac(t) 2^32) as a wrapping 32-bit word (negative t is covered by floor)
-__device__ __forceinline__ uint32_t phase_word(double t)
-{
-  const double w = rint((t - floor(t)) * 4294967296.0);
-  return static_cast<uint32_t>(static_cast<uint64_t>(w) & 0xFFFFFFFFull);
-}
-
 // kx^2 + ky^2 of column ix (0 ... Ex/2) and row iy, float64
 __device__ __forceinline__ double time_kr2(double dkx, double dky, uint32_t ex, uint32_t ey, uint32_t ix, uint32_t iy)
 {
 #pragma clang fp contract(off)
-  const double kx = dkx * static_cast<double>(ix <= ex / 2 ? ix : ex - ix);
-  const double ky = dky * static_cast<double>(iy <= ey / 2 ? iy : ey - iy);
+  const double kx = dkx * static_cast<double>(kw_folded(ix, ex));
+  const double ky = dky * static_cast<double>(kw_folded(iy, ey));
   return (kx * kx) + (ky * ky);
 }
 
@@ -79,7 +57,7 @@ __device__ __attribute__((noinline)) float2 time_h(TimeHLds g, double kr2, uint3
   const bool     prop = kr2 < k2, evan = kr2 > k2;
   const double   qp   = evan ? 0.0 : q;
   const double   t    = (qp - (g->retarded ? k : 0.0)) * z / kTwoPi;
-  const uint32_t word = phase_word(t);
+  const uint32_t word = kw_phase_word(t);
   const float    ang  = static_cast<float>(static_cast<int32_t>(word)) * 1.4629180792671596e-9f;
   float sn, cs;
   sincosf(ang, &sn, &cs);
@@ -211,38 +189,13 @@ __global__ __launch_bounds__(256) void k_angular_time_mix(float2* __restrict__ o
   }
 }
 
-struct TimeDims { uint32_t ex, ey, lt, nx, ny, nt; };
-
-// vol [lt][ey][ex] <- src [nt][ny][nx] in the corner, zero elsewhere; V = 4: 16-byte accesses (ex, nx multiples of 4)
-template<int V> __global__ __launch_bounds__(256) void k_time_embed(float* __restrict__ vol, const float* __restrict__ src, TimeDims d)
-{
-  const uint32_t exv = d.ex / V;
-  const uint64_t n   = static_cast<uint64_t>(exv) * d.ey * d.lt;
-  for (uint64_t e = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; e < n;
-       e += static_cast<uint64_t>(gridDim.x) * blockDim.x)
-  {
-    const uint32_t ix = static_cast<uint32_t>(e % exv) * V;
-    const uint64_t r  = e / exv;
-    const uint32_t iy = static_cast<uint32_t>(r % d.ey), t = static_cast<uint32_t>(r / d.ey);
-    const bool inside = ix < d.nx && iy < d.ny && t < d.nt;
-    const uint64_t s  = (static_cast<uint64_t>(t) * d.ny + iy) * d.nx + ix;
-    if constexpr (V == 4)
-    {
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (inside) v = *reinterpret_cast<const float4*>(src + s);
-      *reinterpret_cast<float4*>(vol + e * 4) = v;
-    }
-    else vol[e] = inside ? src[s] : 0.f;
-  }
-}
-
 // max_t / min_t and the series of the domain crop.  A block takes a tile of TP * V consecutive points (y, x) of the
 // domain and splits the record along t over its 256 / TP thread rows: a small plane with a long record still fills the
 // machine.  The rows' partial extrema meet in LDS; max and min are exact and order-free, so the result is deterministic
 // without atomics.  Tiles are walked grid-stride.
 template<int V, int TP> __global__ __launch_bounds__(256) void k_time_reduce(const float* __restrict__ vol, float* __restrict__ p_max,
                                                                              float* __restrict__ p_min,
-                                                                             float* __restrict__ series, TimeDims d)
+                                                                             float* __restrict__ series, kw_record_dims d)
 {
   constexpr int TS = 256 / TP;
   __shared__ float smax[TS][TP * V];
@@ -380,10 +333,10 @@ kw_status kw_angular_time_embed(kw_ctx* ctx, float* vol, const float* src, uint3
   KW_REQUIRE(vol != nullptr);
   const uint64_t nd = static_cast<uint64_t>(nx) * ny * nt;
   KW_REQUIRE(nd == 0 || src != nullptr);
-  const TimeDims d{ ex, ey, lt, nx, ny, nd == 0 ? 0u : nt };
+  const kw_record_dims d{ ex, ey, lt, nx, ny, nd == 0 ? 0u : nt };
   const bool v4 = ex % 4 == 0 && nx % 4 == 0 && aligned16(vol) && aligned16(src);
-  if (v4) hipLaunchKernelGGL(k_time_embed<4>, dim3(capped_grid(ctx, n / 4)), dim3(256), 0, ctx->stream, vol, src, d);
-  else hipLaunchKernelGGL(k_time_embed<1>, dim3(capped_grid(ctx, n)), dim3(256), 0, ctx->stream, vol, src, d);
+  if (v4) hipLaunchKernelGGL((k_record_embed<4, false>), dim3(capped_grid(ctx, n / 4)), dim3(256), 0, ctx->stream, vol, src, d);
+  else hipLaunchKernelGGL((k_record_embed<1, false>), dim3(capped_grid(ctx, n)), dim3(256), 0, ctx->stream, vol, src, d);
   KW_LAUNCH_CHECK();
   return KW_OK;
 }
@@ -398,7 +351,7 @@ kw_status kw_angular_time_reduce(kw_ctx* ctx, const float* vol, uint32_t ex, uin
   if (p_max == nullptr && p_min == nullptr && series == nullptr) return KW_OK;
   KW_REQUIRE(nx <= ex && ny <= ey && nt <= lt);
   KW_REQUIRE(vol != nullptr);
-  const TimeDims d{ ex, ey, lt, nx, ny, nt };
+  const kw_record_dims d{ ex, ey, lt, nx, ny, nt };
   const bool v4 = ex % 4 == 0 && nx % 4 == 0 && aligned16(vol) && aligned16(p_max) && aligned16(p_min) && aligned16(series);
   if (v4)
   {

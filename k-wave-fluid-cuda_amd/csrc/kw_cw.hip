@@ -13,6 +13,7 @@
 // F{Sr} and F{Si} are mixed bin by bin)
 //   Pr^ = Gr Sr^ - Gi Si^        Pi^ = Gi Sr^ + Gr Si^
 // are Hermitian half-spectra again, and two C2R transforms give Re P and Im P.
+#include "kw_elementwise.h"
 #include "kw_fused.hip"
 
 namespace {
@@ -244,22 +245,8 @@ template<int L> __global__ __launch_bounds__(Geo<L / 2>::THREADS) void k_zfused_
 }
 
 // =====================================================================================================================
-// element-wise kernels: 256 threads, at most CU count x 8 blocks striding over the work (house style of kw_thermal.hip)
+// element-wise kernels: 256 threads, at most CU count x 8 blocks striding over the work (kw_elementwise.h)
 // =====================================================================================================================
-constexpr int kBlocksPerCu = 8;
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
-
-inline unsigned capped_grid(const kw_ctx* ctx, uint64_t work)
-{
-  uint64_t       g   = (work + 255) / 256;
-  const uint64_t cap = static_cast<uint64_t>(ctx->cu_count) * kBlocksPerCu;
-  if (g > cap) g = cap;
-  if (g == 0) g = 1;
-  return static_cast<unsigned>(g);
-}
-
 // G(a) exp(-i w T) * divider for a = c0 |k| in the regular form (kwave_hip.h), all in float64:
 //   G = i [ sin(a T)/a - T exp(i (a + w) T/2) sinc((a - w) T/2) ] / (a + w)
 // sinc(0) = 1 and sin(a T)/a -> T at a = 0 are the functions' own values there, not treated bins: the form is regular at
@@ -278,8 +265,8 @@ __global__ __launch_bounds__(256) void k_cw_operator(float* __restrict__ g_re, f
     const uint64_t r  = e / nxc;
     const uint32_t iy = static_cast<uint32_t>(r % ny), iz = static_cast<uint32_t>(r / ny);
     const double kx = dkx * static_cast<double>(ix);
-    const double ky = dky * static_cast<double>(iy <= ny / 2 ? iy : ny - iy); // |k| only: the sign of a bin does not matter
-    const double kz = dkz * static_cast<double>(iz <= nz / 2 ? iz : nz - iz);
+    const double ky = dky * static_cast<double>(kw_folded(iy, ny)); // |k| only: the sign of a bin does not matter
+    const double kz = dkz * static_cast<double>(kw_folded(iz, nz));
     const double a  = c0 * sqrt(kx * kx + ky * ky + kz * kz);
     const double s1 = (a == 0.0) ? T : sin(a * T) / a;
     const double x  = 0.5 * (a - w) * T;

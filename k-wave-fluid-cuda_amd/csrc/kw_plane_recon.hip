@@ -10,31 +10,17 @@
 //                        operator array and no index table in memory
 //   kw_plane_recon_mix   the same on the natural [Lt][Ey][Ex/2 + 1] spectrum of kw_fft_r2c_3d (rocFFT path, and the twin)
 //   kw_plane_recon_embed / _crop   the mirrored embedding of the record; the first planes of the domain crop, clamped on request
+#include "kw_elementwise.h"
 #include "kw_fused.hip"
 
 namespace {
-
-constexpr int kBlocksPerCu = 8;
-
-inline unsigned capped_grid(const kw_ctx* ctx, uint64_t work)
-{
-  uint64_t       g   = (work + 255) / 256;
-  const uint64_t cap = static_cast<uint64_t>(ctx->cu_count) * kBlocksPerCu;
-  if (g > cap) g = cap;
-  if (g == 0) g = 1;
-  return static_cast<unsigned>(g);
-}
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-constexpr double kTwoPi = 6.283185307179586476925286766559;
 
 // (kx^2 + ky^2) / dk^2 of column ix (0 ... Ex/2) and row iy, float64
 __device__ __forceinline__ double recon_rho2(double dkx, double dky, double dk2, uint32_t ex, uint32_t ey, uint32_t ix, uint32_t iy)
 {
 #pragma clang fp contract(off)
-  const double kx = dkx * static_cast<double>(ix <= ex / 2 ? ix : ex - ix);
-  const double ky = dky * static_cast<double>(iy <= ey / 2 ? iy : ey - iy);
+  const double kx = dkx * static_cast<double>(kw_folded(ix, ex));
+  const double ky = dky * static_cast<double>(kw_folded(iy, ey));
   return ((kx * kx) + (ky * ky)) / dk2;
 }
 
@@ -212,37 +198,10 @@ __global__ __launch_bounds__(256) void k_plane_recon_mix(float2* __restrict__ ou
   }
 }
 
-struct ReconDims { uint32_t ex, ey, lt, nx, ny, nt; };
-
-// vol [lt][ey][ex] <- src [nt][ny][nx] mirrored in time (rows t and lt - t take src[t]), zero elsewhere; V = 4: 16-byte
-// accesses (ex, nx multiples of 4).  lt >= 2 nt - 1: no row is claimed twice.
-template<int V> __global__ __launch_bounds__(256) void k_recon_embed(float* __restrict__ vol, const float* __restrict__ src, ReconDims d)
-{
-  const uint32_t exv = d.ex / V;
-  const uint64_t n   = static_cast<uint64_t>(exv) * d.ey * d.lt;
-  for (uint64_t e = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; e < n;
-       e += static_cast<uint64_t>(gridDim.x) * blockDim.x)
-  {
-    const uint32_t ix = static_cast<uint32_t>(e % exv) * V;
-    const uint64_t r  = e / exv;
-    const uint32_t iy = static_cast<uint32_t>(r % d.ey), t = static_cast<uint32_t>(r / d.ey);
-    const uint32_t ts = t < d.nt ? t : d.lt - t; // the source row: t itself, or its mirror image
-    const bool inside = ix < d.nx && iy < d.ny && ts < d.nt;
-    const uint64_t s  = (static_cast<uint64_t>(ts) * d.ny + iy) * d.nx + ix;
-    if constexpr (V == 4)
-    {
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (inside) v = *reinterpret_cast<const float4*>(src + s);
-      *reinterpret_cast<float4*>(vol + e * 4) = v;
-    }
-    else vol[e] = inside ? src[s] : 0.f;
-  }
-}
-
 __device__ __forceinline__ float recon_clamp(float x, bool positivity) { return (positivity && !(x > 0.f)) ? 0.f : x; }
 
 // out [nt][ny][nx] <- the corner of vol [lt][ey][ex] (nt = the planes), clamped at 0 on request
-template<int V> __global__ __launch_bounds__(256) void k_recon_crop(float* __restrict__ out, const float* __restrict__ vol, ReconDims d,
+template<int V> __global__ __launch_bounds__(256) void k_recon_crop(float* __restrict__ out, const float* __restrict__ vol, kw_record_dims d,
                                                                     int positivity)
 {
   const uint32_t nxv = d.nx / V;
@@ -341,10 +300,10 @@ kw_status kw_plane_recon_embed(kw_ctx* ctx, float* vol, const float* src, uint32
   KW_REQUIRE(vol != nullptr);
   const uint64_t nd = static_cast<uint64_t>(nx) * ny * nt;
   KW_REQUIRE(nd == 0 || src != nullptr);
-  const ReconDims d{ ex, ey, lt, nx, ny, nd == 0 ? 0u : nt };
+  const kw_record_dims d{ ex, ey, lt, nx, ny, nd == 0 ? 0u : nt };
   const bool v4 = ex % 4 == 0 && nx % 4 == 0 && aligned16(vol) && aligned16(src);
-  if (v4) hipLaunchKernelGGL(k_recon_embed<4>, dim3(capped_grid(ctx, n / 4)), dim3(256), 0, ctx->stream, vol, src, d);
-  else hipLaunchKernelGGL(k_recon_embed<1>, dim3(capped_grid(ctx, n)), dim3(256), 0, ctx->stream, vol, src, d);
+  if (v4) hipLaunchKernelGGL((k_record_embed<4, true>), dim3(capped_grid(ctx, n / 4)), dim3(256), 0, ctx->stream, vol, src, d);
+  else hipLaunchKernelGGL((k_record_embed<1, true>), dim3(capped_grid(ctx, n)), dim3(256), 0, ctx->stream, vol, src, d);
   KW_LAUNCH_CHECK();
   return KW_OK;
 }
@@ -358,7 +317,7 @@ kw_status kw_plane_recon_crop(kw_ctx* ctx, float* out, const float* vol, uint32_
   if (n == 0) return KW_OK;
   KW_REQUIRE(nx <= ex && ny <= ey && planes <= lt);
   KW_REQUIRE(out != nullptr && vol != nullptr);
-  const ReconDims d{ ex, ey, lt, nx, ny, planes };
+  const kw_record_dims d{ ex, ey, lt, nx, ny, planes };
   const bool v4 = ex % 4 == 0 && nx % 4 == 0 && aligned16(out) && aligned16(vol);
   if (v4) hipLaunchKernelGGL(k_recon_crop<4>, dim3(capped_grid(ctx, n / 4)), dim3(256), 0, ctx->stream, out, vol, d, positivity);
   else hipLaunchKernelGGL(k_recon_crop<1>, dim3(capped_grid(ctx, n)), dim3(256), 0, ctx->stream, out, vol, d, positivity);

@@ -10,7 +10,7 @@
 //   * Device constants travel as a by-value kernel argument (SGPRs) instead of a __constant__ symbol.
 //   * Arithmetic association order follows the cited reference lines exactly.
 // All kernels are bandwidth-bound (0.1-0.3 flop/B): no LDS tiling, no MFMA.
-#include "kw_internal.h"
+#include "kw_elementwise.h"
 
 namespace {
 
@@ -31,8 +31,6 @@ inline RowGeom row_geom(const kw_constants& c, int vec)
   g.grid  = dim3((rows + kRowsPerBlock - 1) / kRowsPerBlock, (c.nx + kWave * vec - 1) / (kWave * vec), 1);
   return g;
 }
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 template<typename... P> inline bool all_aligned16(P... ptrs)
 {

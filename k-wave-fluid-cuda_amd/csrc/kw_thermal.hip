@@ -14,11 +14,9 @@
 // Both kernels are bandwidth-bound (up to 13 array passes of 4 B per point against ~15 flops): R^(43 - T) is one exp2f.
 #include <utility>
 
-#include "kw_internal.h"
+#include "kw_elementwise.h"
 
 namespace {
-
-constexpr int kBlocksPerCu = 8; // grid cap: CU count x 8 blocks of 256 threads (the samplers' cap)
 
 enum : int
 {
@@ -160,18 +158,6 @@ template<int V, int... M> UpdateKernel update_kernel(int mask, std::integer_sequ
 {
   static const UpdateKernel table[] = { k_thermal_update<V, M>... };
   return table[mask];
-}
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-// CU count x 8 blocks at the most, shrunk to the work: `work` = threads wanted
-inline unsigned capped_grid(const kw_ctx* ctx, uint64_t work)
-{
-  uint64_t       g   = (work + 255) / 256;
-  const uint64_t cap = static_cast<uint64_t>(ctx->cu_count) * kBlocksPerCu;
-  if (g > cap) g = cap;
-  if (g == 0) g = 1;
-  return static_cast<unsigned>(g);
 }
 
 } // namespace

@@ -4,26 +4,7 @@
 #include <cmath>
 #include <stdexcept>
 
-#include "CwParameters.h"
-
-namespace
-{
-[[noreturn]] void refuse(const std::string& parameter, const std::string& what)
-{
-  throw std::invalid_argument(parameter + ": " + what);
-}
-
-void checkSize(size_t n, const char* name)
-{
-  if (n == 0) refuse(name, "0 is not a grid size");
-  if (n >= (1ull << 31)) refuse(name, std::to_string(n) + " is not a grid size");
-}
-
-void checkPositive(double v, const char* name, const char* unit)
-{
-  if (!(v > 0.0) || !std::isfinite(v)) refuse(name, std::to_string(v) + " is not a positive " + unit);
-}
-} // namespace
+using namespace GridRule;
 
 namespace AngularRule
 {
@@ -35,7 +16,7 @@ size_t chunkPlanes(size_t ex, size_t ey, size_t planes)
 }
 } // namespace AngularRule
 
-void AngularParameters::init(const AngularOptions& opt)
+void AngularParameters::init(const DeviceOptions& opt)
 {
   options = opt;
   checkSize(nx, "Nx");
@@ -53,36 +34,16 @@ void AngularParameters::init(const AngularOptions& opt)
                          " (the phase accumulator is specified up to plane index 4095)");
   if (!(alphaNp >= 0.0) || !std::isfinite(alphaNp)) refuse("alpha_np", std::to_string(alphaNp) + " is not an absorption >= 0 in Np/m");
 
-  const size_t n[2]     = { nx, ny };
-  size_t*      e[2]     = { &ex, &ey };
-  const char*  names[2] = { "Ex", "Ey" };
-  if (ex != 0 || ey != 0)
-  {
-    for (int a = 0; a < 2; a++)
-    {
-      if (*e[a] == 0) refuse(names[a], "missing while the other side of the expanded grid is given");
-      if (*e[a] % 2 != 0) refuse(names[a], std::to_string(*e[a]) + " is odd (the real transforms need even sides)");
-      if (*e[a] < n[a]) refuse(names[a], std::to_string(*e[a]) + " is below N = " + std::to_string(n[a]));
-      if (*e[a] >= (1ull << 31)) refuse(names[a], std::to_string(*e[a]) + " is not a grid size");
-    }
-  }
-  else
-  {
-    bool fast = options.fusedKernels;
-    for (int a = 0; a < 2 && fast; a++) fast = CwRule::nextFastLength(2 * n[a]) != 0;
-    for (int a = 0; a < 2; a++) *e[a] = fast ? CwRule::nextFastLength(2 * n[a]) : 2 * n[a];
-  }
-  const bool fastSides = options.fusedKernels && CwRule::isFastLength(ex) && CwRule::isFastLength(ey);
+  if (ex != 0 || ey != 0) checkGivenSides(nx, ny, ex, ey, true);
+  else defaultDoubledSides(nx, ny, ex, ey, options.fusedKernels);
+  const bool fastSides = options.fusedKernels && isFastLength(ex) && isFastLength(ey);
   if (chunkPlanes == 0) chunkPlanes = AngularRule::chunkPlanes(ex, ey, planes);
   else
   {
     if (chunkPlanes > AngularRule::kMaxPlanes) refuse("chunk_planes", std::to_string(chunkPlanes) + " is above 4096");
-    if (fastSides && !CwRule::isFastLength(chunkPlanes))
+    if (fastSides && !isFastLength(chunkPlanes))
       refuse("chunk_planes", std::to_string(chunkPlanes) + " is no fast-path length (16, 32, 48, 64 ...) on a fast-path grid");
   }
-  // 32-bit element indices in the pipeline and in the FFT wrapper
-  const long double total = static_cast<long double>(ex) * static_cast<long double>(ey) * static_cast<long double>(chunkPlanes);
-  if (total >= 4294967296.0L)
-    refuse("E", std::to_string(ex) + " x " + std::to_string(ey) + " x " + std::to_string(chunkPlanes) + " points per chunk is not below 2^32");
-  fastPath = fastSides && CwRule::isFastLength(chunkPlanes);
+  checkTotal(ex, ey, chunkPlanes, "points per chunk");
+  fastPath = fastSides && isFastLength(chunkPlanes);
 }

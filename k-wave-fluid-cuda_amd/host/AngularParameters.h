@@ -16,11 +16,7 @@
 #include <cstdint>
 #include <string>
 
-struct AngularOptions
-{
-  int  deviceIdx    = -1;
-  bool fusedKernels = true;
-};
+#include "GridRules.h"
 
 namespace AngularRule
 {
@@ -34,9 +30,9 @@ class AngularParameters
 {
  public:
   /// checks every parameter and fills in ex / ey and chunkPlanes where they are 0; throws std::invalid_argument naming the parameter
-  void init(const AngularOptions& options);
+  void init(const DeviceOptions& options);
 
-  AngularOptions options;
+  DeviceOptions options;
   size_t nx = 0, ny = 0;          ///< the plane
   double dx = 0, dy = 0;          ///< [m]
   double c0 = 0, f0 = 0;          ///< [m/s], [Hz]

@@ -1,6 +1,6 @@
 // AngularSpectrum.h — angular-spectrum CW projector: a complex pressure plane carried to the planes z_j = z0 + j dz of a
 // homogeneous, possibly absorbing medium (DESIGN.md "Angular-spectrum projector"; what k-Wave's angularSpectrumCW
-// computes).  Owns its own kw_ctx, like CwPropagator, and builds the operator tables once; every run reuses them.
+// computes).  Owns its context through a DeviceGrid and builds the operator tables once; every run reuses them.
 //
 //   run:  embed the plane into the zero-filled expanded pair (kw_cw_embed, one plane), transform it once
 //         (kw_fused_angular_forward, or kw_fft_r2c_3d on the 2-D plans), then project()
@@ -13,19 +13,15 @@
 // spectra 16 R; and the result, 8 bytes per domain point, plus one staging array of that size.
 #ifndef KW_HOST_ANGULAR_SPECTRUM_H
 #define KW_HOST_ANGULAR_SPECTRUM_H
-#include <stdexcept>
 #include <string>
-#include <vector>
 
 #include "AngularParameters.h"
-#include "CwPropagator.h"
-#include "kwave_hip.h"
+#include "DeviceGrid.h"
 
 class AngularSpectrum
 {
  public:
   explicit AngularSpectrum(const AngularParameters& parameters);
-  ~AngularSpectrum();
   AngularSpectrum(const AngularSpectrum&) = delete;
   AngularSpectrum& operator=(const AngularSpectrum&) = delete;
 
@@ -37,21 +33,15 @@ class AngularSpectrum
   void heat(const float* q, float qScalar, float* dst, size_t n);
   /// the chunks alone, from the source spectra as they stand (tools/bench_angular.py)
   void project();
-  bool    usesFusedPipeline() const { return mFused; }
+  bool    usesFusedPipeline() const { return mGrid.fused(); }
   size_t  runs() const { return mRuns; }
-  kw_ctx* context() const { return mCtx; }
+  kw_ctx* context() const { return mGrid.ctx(); }
   const AngularParameters& parameters() const { return mPar; }
 
  private:
-  void   check(kw_status s) const;
-  void*  deviceBytes(size_t bytes);
-  float* deviceArray(size_t nFloats) { return static_cast<float*>(deviceBytes(nFloats * sizeof(float))); }
-
   AngularParameters mPar;
-  kw_ctx*      mCtx = nullptr;
-  bool         mFused = false;
+  DeviceGrid   mGrid; // the context, the pipeline and every device array below
   size_t       mRuns = 0;
-  std::vector<void*> mOwned;
   float *mRe = nullptr, *mIm = nullptr;         // the chunk: Ex Ey Zc each
   uint32_t *mTab = nullptr, *mTabImported = nullptr;
   float *mSrcRe = nullptr, *mSrcIm = nullptr;   // the source's 2-D spectra (pipeline layout, or [Ey][Ex/2 + 1])

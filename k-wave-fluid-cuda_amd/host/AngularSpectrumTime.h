@@ -1,6 +1,6 @@
 // AngularSpectrumTime.h — time-domain angular-spectrum projector: a pressure record p0[t][y][x] on a plane carried to
 // parallel planes at the distances z_j of a homogeneous, possibly absorbing medium (DESIGN.md "Time-domain
-// angular-spectrum projector"; what k-Wave's angularSpectrum computes).  Owns its own kw_ctx, like AngularSpectrum.
+// angular-spectrum projector"; what k-Wave's angularSpectrum computes).  Owns its context through a DeviceGrid.
 //
 //   setInput: embed the record into the zero-filled volume Lt x Ey x Ex (kw_angular_time_embed), transform it once and keep
 //         the result — fast path: kw_fused_angular_time_forward (the (kx, ky, t) half-spectrum); others: kw_fft_r2c_3d
@@ -13,19 +13,15 @@
 // one series 4 Nx Ny Nt each; p_max and p_min 4 Nx Ny per plane each.
 #ifndef KW_HOST_ANGULAR_SPECTRUM_TIME_H
 #define KW_HOST_ANGULAR_SPECTRUM_TIME_H
-#include <stdexcept>
 #include <string>
-#include <vector>
 
 #include "AngularTimeParameters.h"
-#include "CwPropagator.h"
-#include "kwave_hip.h"
+#include "DeviceGrid.h"
 
 class AngularSpectrumTime
 {
  public:
   explicit AngularSpectrumTime(const AngularTimeParameters& parameters);
-  ~AngularSpectrumTime();
   AngularSpectrumTime(const AngularSpectrumTime&) = delete;
   AngularSpectrumTime& operator=(const AngularSpectrumTime&) = delete;
 
@@ -39,23 +35,18 @@ class AngularSpectrumTime
   void get(const std::string& name, float* dst, size_t n);
   /// plane j recomputed: dst [Nt][Ny][Nx], n = Nx Ny Nt
   void series(size_t j, float* dst, size_t n);
-  bool    usesFusedPipeline() const { return mFused; }
+  bool    usesFusedPipeline() const { return mGrid.fused(); }
   size_t  runs() const { return mRuns; }
-  kw_ctx* context() const { return mCtx; }
+  kw_ctx* context() const { return mGrid.ctx(); }
   const AngularTimeParameters& parameters() const { return mPar; }
 
  private:
-  void   check(kw_status s) const;
-  void*  deviceBytes(size_t bytes);
-  float* deviceArray(size_t nFloats) { return static_cast<float*>(deviceBytes(nFloats * sizeof(float))); }
-  void   plane(size_t j, float* pMax, float* pMin, float* series);
+  void plane(size_t j, float* pMax, float* pMin, float* series);
 
   AngularTimeParameters mPar;
-  kw_ctx*      mCtx = nullptr;
-  bool         mFused = false;
+  DeviceGrid   mGrid; // the context, the pipeline and every device array below
   bool         mHaveInput = false;
   size_t       mRuns = 0;
-  std::vector<void*> mOwned;
   float*  mVol = nullptr;     // Lt Ey Ex: the embedded record, then each plane's record
   float*  mKept = nullptr;    // the kept spectrum
   float*  mSpec = nullptr;    // rocFFT path: the plane's spectrum

@@ -4,28 +4,9 @@
 #include <cmath>
 #include <stdexcept>
 
-#include "CwParameters.h"
+using namespace GridRule;
 
-namespace
-{
-[[noreturn]] void refuse(const std::string& parameter, const std::string& what)
-{
-  throw std::invalid_argument(parameter + ": " + what);
-}
-
-void checkSize(size_t n, const char* name)
-{
-  if (n == 0) refuse(name, "0 is not a grid size");
-  if (n >= (1ull << 31)) refuse(name, std::to_string(n) + " is not a grid size");
-}
-
-void checkPositive(double v, const char* name, const char* unit)
-{
-  if (!(v > 0.0) || !std::isfinite(v)) refuse(name, std::to_string(v) + " is not a positive " + unit);
-}
-} // namespace
-
-void AngularTimeParameters::init(const AngularOptions& opt)
+void AngularTimeParameters::init(const DeviceOptions& opt)
 {
   options = opt;
   checkSize(nx, "Nx");
@@ -45,25 +26,8 @@ void AngularTimeParameters::init(const AngularOptions& opt)
     if (!(z[j] >= 0.0) || !std::isfinite(z[j]))
       refuse("z", "z[" + std::to_string(j) + "] = " + std::to_string(z[j]) + " is not a distance >= 0 (reverse projection is not built)");
 
-  const size_t n[2]     = { nx, ny };
-  size_t*      e[2]     = { &ex, &ey };
-  const char*  names[2] = { "Ex", "Ey" };
-  if (ex != 0 || ey != 0)
-  {
-    for (int a = 0; a < 2; a++)
-    {
-      if (*e[a] == 0) refuse(names[a], "missing while the other side of the expanded grid is given");
-      if (*e[a] % 2 != 0) refuse(names[a], std::to_string(*e[a]) + " is odd (the real transforms need even sides)");
-      if (*e[a] < n[a]) refuse(names[a], std::to_string(*e[a]) + " is below N = " + std::to_string(n[a]));
-      if (*e[a] >= (1ull << 31)) refuse(names[a], std::to_string(*e[a]) + " is not a grid size");
-    }
-  }
-  else
-  {
-    bool fast = options.fusedKernels;
-    for (int a = 0; a < 2 && fast; a++) fast = CwRule::nextFastLength(2 * n[a]) != 0;
-    for (int a = 0; a < 2; a++) *e[a] = fast ? CwRule::nextFastLength(2 * n[a]) : 2 * n[a];
-  }
+  if (ex != 0 || ey != 0) checkGivenSides(nx, ny, ex, ey, true);
+  else defaultDoubledSides(nx, ny, ex, ey, options.fusedKernels);
   if (lt != 0)
   {
     if (lt % 2 != 0) refuse("Lt", std::to_string(lt) + " is odd (the Nyquist bin of the record is dropped: Lt is even)");
@@ -72,14 +36,11 @@ void AngularTimeParameters::init(const AngularOptions& opt)
   }
   else
   {
-    const size_t fast = options.fusedKernels ? CwRule::nextFastLength(nt) : 0;
+    const size_t fast = options.fusedKernels ? nextFastLength(nt) : 0;
     lt = fast != 0 ? fast : nt + nt % 2;
   }
-  // 32-bit element indices in the pipeline and in the FFT wrapper
-  const long double total = static_cast<long double>(ex) * static_cast<long double>(ey) * static_cast<long double>(lt);
-  if (total >= 4294967296.0L)
-    refuse("E", std::to_string(ex) + " x " + std::to_string(ey) + " x " + std::to_string(lt) + " points is not below 2^32");
-  fastPath = options.fusedKernels && CwRule::isFastLength(ex) && CwRule::isFastLength(ey) && CwRule::isFastLength(lt);
+  checkTotal(ex, ey, lt);
+  fastPath = options.fusedKernels && isFastLength(ex) && isFastLength(ey) && isFastLength(lt);
 }
 
 std::vector<double> AngularTimeParameters::akTable() const

@@ -22,9 +22,9 @@ class AngularTimeParameters
 {
  public:
   /// checks every parameter and fills in ex / ey / lt where they are 0; throws std::invalid_argument naming the parameter
-  void init(const AngularOptions& options);
+  void init(const DeviceOptions& options);
 
-  AngularOptions options;
+  DeviceOptions options;
   size_t nx = 0, ny = 0, nt = 0;  ///< the record
   double dx = 0, dy = 0, dt = 0;  ///< [m], [m], [s]
   double c0 = 0;                  ///< [m/s]

@@ -5,45 +5,14 @@
 #include <cmath>
 #include <stdexcept>
 
-namespace
-{
-[[noreturn]] void refuse(const std::string& parameter, const std::string& what)
-{
-  throw std::invalid_argument(parameter + ": " + what);
-}
-
-// KW_FUSED_LENGTHS of csrc/kw_fused.hip, ascending
-const size_t kFastLengths[] = { 16,  32,  48,  64,  72,  80,  96,  100, 108, 112, 120, 128, 140, 144, 160, 168,
-                                180, 192, 196, 200, 216, 224, 240, 252, 256, 280, 288, 300, 320, 324, 336, 360,
-                                384, 392, 400, 420, 432, 448, 480, 500, 504, 512, 540, 560, 576, 600, 640, 648,
-                                672, 700, 720, 756, 768, 784, 800, 840, 864, 896, 900, 960, 1024 };
-
-void checkSize(size_t n, const char* name)
-{
-  if (n == 0) refuse(name, "0 is not a grid size");
-  if (n >= (1ull << 31)) refuse(name, std::to_string(n) + " is not a grid size");
-}
-
-void checkPositive(double v, const char* name, const char* unit)
-{
-  if (!(v > 0.0) || !std::isfinite(v)) refuse(name, std::to_string(v) + " is not a positive " + unit);
-}
-} // namespace
+using namespace GridRule;
 
 namespace CwRule
 {
-bool isFastLength(size_t n) { return std::binary_search(std::begin(kFastLengths), std::end(kFastLengths), n); }
-
-size_t nextFastLength(size_t n)
-{
-  const size_t* p = std::lower_bound(std::begin(kFastLengths), std::end(kFastLengths), n);
-  return p == std::end(kFastLengths) ? 0 : *p;
-}
-
 size_t leastSide(size_t n, double d, double c0, double t) { return n + static_cast<size_t>(std::ceil(c0 * t / d)); }
 } // namespace CwRule
 
-void CwParameters::init(const CwOptions& opt)
+void CwParameters::init(const DeviceOptions& opt)
 {
   options = opt;
   checkSize(nx, "Nx");
@@ -93,12 +62,9 @@ void CwParameters::init(const CwOptions& opt)
   else
   {
     bool fast = options.fusedKernels;
-    for (int a = 0; a < 3 && fast; a++) fast = CwRule::nextFastLength(least[a]) != 0;
-    for (int a = 0; a < 3; a++) *e[a] = fast ? CwRule::nextFastLength(least[a]) : least[a] + least[a] % 2;
+    for (int a = 0; a < 3 && fast; a++) fast = nextFastLength(least[a]) != 0;
+    for (int a = 0; a < 3; a++) *e[a] = fast ? nextFastLength(least[a]) : least[a] + least[a] % 2;
   }
-  // 32-bit element indices in the pipeline and in the FFT wrapper
-  const long double total = static_cast<long double>(ex) * static_cast<long double>(ey) * static_cast<long double>(ez);
-  if (total >= 4294967296.0L)
-    refuse("E", std::to_string(ex) + " x " + std::to_string(ey) + " x " + std::to_string(ez) + " points is not below 2^32");
-  fastPath = options.fusedKernels && CwRule::isFastLength(ex) && CwRule::isFastLength(ey) && CwRule::isFastLength(ez);
+  checkTotal(ex, ey, ez);
+  fastPath = options.fusedKernels && isFastLength(ex) && isFastLength(ey) && isFastLength(ez);
 }

@@ -14,18 +14,10 @@
 #include <cstdint>
 #include <string>
 
-struct CwOptions
-{
-  int  deviceIdx    = -1;
-  bool fusedKernels = true;
-};
+#include "GridRules.h"
 
 namespace CwRule
 {
-/// the fused pipeline's line lengths (csrc/kw_fused.hip KW_FUSED_LENGTHS; tests/test_cw_host.py compares the two lists)
-bool   isFastLength(size_t n);
-/// smallest fast-path length >= n, 0 when there is none
-size_t nextFastLength(size_t n);
 /// N + ceil(c0 T / d): the least side that keeps the periodic images out of the domain until T
 size_t leastSide(size_t n, double d, double c0, double t);
 } // namespace CwRule
@@ -34,9 +26,9 @@ class CwParameters
 {
  public:
   /// checks every parameter and fills in t and ex / ey / ez where they are 0; throws std::invalid_argument naming the parameter
-  void init(const CwOptions& options);
+  void init(const DeviceOptions& options);
 
-  CwOptions options;
+  DeviceOptions options;
   size_t nx = 0, ny = 0, nz = 0;   ///< domain
   double dx = 0, dy = 0, dz = 0;   ///< [m]
   double c0 = 0, f0 = 0;           ///< [m/s], [Hz]

@@ -1,6 +1,6 @@
 // CwPropagator.h — steady-state pressure of a continuous-wave source in a homogeneous lossless medium in one FFT round
-// trip (DESIGN.md "CW field propagator"; what k-Wave's acousticFieldPropagator computes).  Owns its own kw_ctx, like
-// ThermalSolver, and builds the operator G exp(-i w T) / N once; every run reuses it.
+// trip (DESIGN.md "CW field propagator"; what k-Wave's acousticFieldPropagator computes).  Owns its context through
+// a DeviceGrid and builds the operator G exp(-i w T) / N once; every run reuses it.
 //
 //   run:  embed the source into the zero-filled expanded pair (kw_cw_embed)
 //         fast-path grids: kw_fused_cw_pair;   others: kw_fft_r2c_3d x 2, kw_cw_mix, kw_fft_c2r_3d x 2
@@ -13,25 +13,15 @@
 // plus four arrays of the DOMAIN's size (two inputs, two staging outputs).
 #ifndef KW_HOST_CW_PROPAGATOR_H
 #define KW_HOST_CW_PROPAGATOR_H
-#include <stdexcept>
 #include <string>
-#include <vector>
 
 #include "CwParameters.h"
-#include "kwave_hip.h"
-
-/// a failing device call with its kw_status (kwh_cw_create hands KW_ERR_NO_DEVICE through)
-struct CwDeviceError : std::runtime_error
-{
-  kw_status status;
-  CwDeviceError(kw_status s, const std::string& what) : std::runtime_error(what), status(s) {}
-};
+#include "DeviceGrid.h"
 
 class CwPropagator
 {
  public:
   explicit CwPropagator(const CwParameters& parameters);
-  ~CwPropagator();
   CwPropagator(const CwPropagator&) = delete;
   CwPropagator& operator=(const CwPropagator&) = delete;
 
@@ -41,22 +31,17 @@ class CwPropagator
   void get(const std::string& name, float* dst, size_t n);
   /// Q = q |P|^2: q per point (n floats on the host), or NULL and qScalar
   void heat(const float* q, float qScalar, float* dst, size_t n);
-  bool    usesFusedPipeline() const { return mFused; }
+  bool    usesFusedPipeline() const { return mGrid.fused(); }
   size_t  runs() const { return mRuns; }
-  kw_ctx* context() const { return mCtx; }
+  kw_ctx* context() const { return mGrid.ctx(); }
   const CwParameters& parameters() const { return mPar; }
   /// the pair stage alone on the expanded pair as it stands (tools/bench_cw.py)
   void propagate();
 
  private:
-  void   check(kw_status s) const;
-  float* deviceArray(size_t nFloats);
-
   CwParameters mPar;
-  kw_ctx*      mCtx = nullptr;
-  bool         mFused = false;
+  DeviceGrid   mGrid; // the context, the pipeline and every device array below
   size_t       mRuns = 0;
-  std::vector<void*> mOwned;
   float *mRe = nullptr, *mIm = nullptr;     // the expanded pair
   float *mGRe = nullptr, *mGIm = nullptr;   // operators: imported (fast path) or reduced (rocFFT path)
   float *mSpecRe = nullptr, *mSpecIm = nullptr; // rocFFT path: half spectra

@@ -1,0 +1,67 @@
+// GridRules.cpp — see GridRules.h.
+#include "GridRules.h"
+
+#include <algorithm>
+#include <cmath>
+#include <iterator>
+#include <stdexcept>
+
+namespace
+{
+// KW_FUSED_LENGTHS of csrc/kw_fused.hip, ascending
+const size_t kFastLengths[] = { 16,  32,  48,  64,  72,  80,  96,  100, 108, 112, 120, 128, 140, 144, 160, 168,
+                                180, 192, 196, 200, 216, 224, 240, 252, 256, 280, 288, 300, 320, 324, 336, 360,
+                                384, 392, 400, 420, 432, 448, 480, 500, 504, 512, 540, 560, 576, 600, 640, 648,
+                                672, 700, 720, 756, 768, 784, 800, 840, 864, 896, 900, 960, 1024 };
+} // namespace
+
+namespace GridRule
+{
+void refuse(const std::string& parameter, const std::string& what) { throw std::invalid_argument(parameter + ": " + what); }
+
+void checkSize(size_t n, const char* name, size_t limit)
+{
+  if (n == 0) refuse(name, "0 is not a grid size");
+  if (n >= limit) refuse(name, std::to_string(n) + " is not a grid size");
+}
+
+void checkPositive(double v, const char* name, const char* unit)
+{
+  if (!(v > 0.0) || !std::isfinite(v)) refuse(name, std::to_string(v) + " is not a positive " + unit);
+}
+
+bool isFastLength(size_t n) { return std::binary_search(std::begin(kFastLengths), std::end(kFastLengths), n); }
+
+size_t nextFastLength(size_t n)
+{
+  const size_t* p = std::lower_bound(std::begin(kFastLengths), std::end(kFastLengths), n);
+  return p == std::end(kFastLengths) ? 0 : *p;
+}
+
+void checkTotal(size_t ex, size_t ey, size_t ez, const char* points)
+{
+  const long double total = static_cast<long double>(ex) * static_cast<long double>(ey) * static_cast<long double>(ez);
+  if (total >= 4294967296.0L)
+    refuse("E", std::to_string(ex) + " x " + std::to_string(ey) + " x " + std::to_string(ez) + " " + points + " is not below 2^32");
+}
+
+void checkGivenSides(size_t nx, size_t ny, size_t ex, size_t ey, bool requireEven)
+{
+  const size_t n[2] = { nx, ny }, e[2] = { ex, ey };
+  const char*  names[2] = { "Ex", "Ey" };
+  for (int a = 0; a < 2; a++)
+  {
+    if (e[a] == 0) refuse(names[a], "missing while the other side of the expanded grid is given");
+    if (requireEven && e[a] % 2 != 0) refuse(names[a], std::to_string(e[a]) + " is odd (the real transforms need even sides)");
+    if (e[a] < n[a]) refuse(names[a], std::to_string(e[a]) + " is below N = " + std::to_string(n[a]));
+    if (e[a] >= (1ull << 31)) refuse(names[a], std::to_string(e[a]) + " is not a grid size");
+  }
+}
+
+void defaultDoubledSides(size_t nx, size_t ny, size_t& ex, size_t& ey, bool fusedKernels)
+{
+  const bool fast = fusedKernels && nextFastLength(2 * nx) != 0 && nextFastLength(2 * ny) != 0;
+  ex = fast ? nextFastLength(2 * nx) : 2 * nx;
+  ey = fast ? nextFastLength(2 * ny) : 2 * ny;
+}
+} // namespace GridRule

@@ -2,75 +2,21 @@
 // kw_fused_plane_recon entry points.
 #include "PlaneRecon.h"
 
-#include <new>
-
-void PlaneRecon::check(kw_status s) const
+PlaneRecon::PlaneRecon(const PlaneReconParameters& parameters) : mPar(parameters), mGrid(mPar.options.deviceIdx)
 {
-  if (s == KW_OK) return;
-  if (s == KW_ERR_ALLOC) throw std::bad_alloc();
-  throw CwDeviceError(s, kw_last_error());
-}
+  const size_t ne = mPar.nExpanded(), nr = mPar.nReduced();
+  mGrid.setConstants(gridConstants(mPar.ex, mPar.ey, mPar.lt));
+  const bool fused = mGrid.choosePipeline(mPar.fastPath);
 
-PlaneRecon::PlaneRecon(const PlaneReconParameters& parameters) : mPar(parameters)
-{
-  check(kw_init(mPar.options.deviceIdx, &mCtx));
-  try
+  mVol = mGrid.array(ne);
+  if (!fused)
   {
-    const size_t ne = mPar.nExpanded(), nr = mPar.nReduced();
-    kw_constants k{};
-    k.nx = static_cast<uint32_t>(mPar.ex);
-    k.ny = static_cast<uint32_t>(mPar.ey);
-    k.nz = static_cast<uint32_t>(mPar.lt);
-    k.n_elements = static_cast<uint32_t>(ne);
-    k.nx_complex = static_cast<uint32_t>(mPar.ex / 2 + 1);
-    k.ny_complex = k.ny;
-    k.nz_complex = k.nz;
-    k.n_elements_complex = static_cast<uint32_t>(nr);
-    k.fft_divider   = 1.0f / static_cast<float>(ne);
-    k.fft_divider_x = 1.0f / static_cast<float>(mPar.ex);
-    k.fft_divider_y = 1.0f / static_cast<float>(mPar.ey);
-    k.fft_divider_z = 1.0f / static_cast<float>(mPar.lt);
-    check(kw_set_constants(mCtx, &k));
-    int fusedOk = 0;
-    if (mPar.fastPath) check(kw_fused_supported(mCtx, &fusedOk));
-    mFused = fusedOk != 0;
-    if (mFused) check(kw_fused_create(mCtx));
-    else check(kw_fft_create_plans_3d(mCtx));
-
-    mVol = deviceArray(ne);
-    if (!mFused)
-    {
-      mSpecA = deviceArray(2 * nr);
-      mSpecB = deviceArray(2 * nr);
-    }
-    mRecord = deviceArray(mPar.nRecord());
-    mResult = deviceArray(mPar.nResult());
-    check(kw_sync(mCtx));
+    mSpecA = mGrid.array(2 * nr);
+    mSpecB = mGrid.array(2 * nr);
   }
-  catch (...)
-  {
-    for (void* p : mOwned) kw_free(mCtx, p);
-    if (mFused) kw_fused_destroy(mCtx);
-    kw_destroy(mCtx);
-    throw;
-  }
-}
-
-PlaneRecon::~PlaneRecon()
-{
-  if (mCtx == nullptr) return;
-  kw_sync(mCtx);
-  for (void* p : mOwned) kw_free(mCtx, p);
-  if (mFused) kw_fused_destroy(mCtx);
-  kw_destroy(mCtx);
-}
-
-void* PlaneRecon::deviceBytes(size_t bytes)
-{
-  void* d = nullptr;
-  check(kw_malloc(mCtx, bytes, &d));
-  mOwned.push_back(d);
-  return d;
+  mRecord = mGrid.array(mPar.nRecord());
+  mResult = mGrid.array(mPar.nResult());
+  mGrid.check(kw_sync(context()));
 }
 
 void PlaneRecon::reconstruct()
@@ -78,12 +24,12 @@ void PlaneRecon::reconstruct()
   kw_plane_recon_op op{};
   op.dx = mPar.dx; op.dy = mPar.dy; op.dt = mPar.dt; op.c0 = mPar.c0;
   op.interp = mPar.interp;
-  if (mFused) check(kw_fused_plane_recon(mCtx, mVol, &op, mVol));
+  if (mGrid.fused()) mGrid.check(kw_fused_plane_recon(context(), mVol, &op, mVol));
   else
   {
-    check(kw_fft_r2c_3d(mCtx, mVol, mSpecA));
-    check(kw_plane_recon_mix(mCtx, mSpecB, mSpecA, &op, static_cast<float>(2.0 / static_cast<double>(mPar.nExpanded()))));
-    check(kw_fft_c2r_3d(mCtx, mSpecB, mVol));
+    mGrid.check(kw_fft_r2c_3d(context(), mVol, mSpecA));
+    mGrid.check(kw_plane_recon_mix(context(), mSpecB, mSpecA, &op, static_cast<float>(2.0 / static_cast<double>(mPar.nExpanded()))));
+    mGrid.check(kw_fft_c2r_3d(context(), mSpecB, mVol));
   }
 }
 
@@ -91,10 +37,10 @@ void PlaneRecon::run(const float* p)
 {
   const uint32_t ex = static_cast<uint32_t>(mPar.ex), ey = static_cast<uint32_t>(mPar.ey), lt = static_cast<uint32_t>(mPar.lt);
   const uint32_t nx = static_cast<uint32_t>(mPar.nx), ny = static_cast<uint32_t>(mPar.ny);
-  check(kw_memcpy_h2d(mCtx, mRecord, p, mPar.nRecord() * sizeof(float)));
-  check(kw_plane_recon_embed(mCtx, mVol, mRecord, ex, ey, lt, nx, ny, static_cast<uint32_t>(mPar.nt)));
+  mGrid.check(kw_memcpy_h2d(context(), mRecord, p, mPar.nRecord() * sizeof(float)));
+  mGrid.check(kw_plane_recon_embed(context(), mVol, mRecord, ex, ey, lt, nx, ny, static_cast<uint32_t>(mPar.nt)));
   reconstruct();
-  check(kw_plane_recon_crop(mCtx, mResult, mVol, ex, ey, lt, nx, ny, static_cast<uint32_t>(mPar.planes), mPar.positivity ? 1 : 0));
+  mGrid.check(kw_plane_recon_crop(context(), mResult, mVol, ex, ey, lt, nx, ny, static_cast<uint32_t>(mPar.planes), mPar.positivity ? 1 : 0));
   mRuns++;
 }
 
@@ -103,5 +49,5 @@ void PlaneRecon::get(const std::string& name, float* dst, size_t n)
   if (name != "p0") throw std::invalid_argument("no reconstruction output named " + name + " (p0)");
   if (n != mPar.nResult()) throw std::invalid_argument("size mismatch for " + name);
   if (mRuns == 0) throw std::invalid_argument(name + ": no run yet");
-  check(kw_memcpy_d2h(mCtx, dst, mResult, n * sizeof(float)));
+  mGrid.check(kw_memcpy_d2h(context(), dst, mResult, n * sizeof(float)));
 }

@@ -1,6 +1,6 @@
 // PlaneRecon.h — k-space plane reconstruction: the record p[t][y][x] of a planar sensor to the initial pressure
 // p0[z][y][x] that produced it, homogeneous medium (DESIGN.md "k-space plane reconstruction"; what k-Wave's
-// kspacePlaneRecon computes).  Owns its own kw_ctx, like AngularSpectrumTime.
+// kspacePlaneRecon computes).  Owns its context through a DeviceGrid.
 //
 //   run:  the record to the device, kw_plane_recon_embed (mirrored in time into the zero volume Lt x Ey x Ex), then
 //         fast path: kw_fused_plane_recon, in place — others: kw_fft_r2c_3d, kw_plane_recon_mix, kw_fft_c2r_3d —
@@ -10,19 +10,15 @@
 // (fast path) or two spectra 8 R each (rocFFT); the record 4 Nx Ny Nt; the result 4 Nx Ny planes.
 #ifndef KW_HOST_PLANE_RECON_H
 #define KW_HOST_PLANE_RECON_H
-#include <stdexcept>
 #include <string>
-#include <vector>
 
-#include "CwPropagator.h"
+#include "DeviceGrid.h"
 #include "PlaneReconParameters.h"
-#include "kwave_hip.h"
 
 class PlaneRecon
 {
  public:
   explicit PlaneRecon(const PlaneReconParameters& parameters);
-  ~PlaneRecon();
   PlaneRecon(const PlaneRecon&) = delete;
   PlaneRecon& operator=(const PlaneRecon&) = delete;
 
@@ -30,22 +26,17 @@ class PlaneRecon
   void run(const float* p);
   /// "p0" of the last run: n = Nx Ny planes
   void get(const std::string& name, float* dst, size_t n);
-  bool    usesFusedPipeline() const { return mFused; }
+  bool    usesFusedPipeline() const { return mGrid.fused(); }
   size_t  runs() const { return mRuns; }
-  kw_ctx* context() const { return mCtx; }
+  kw_ctx* context() const { return mGrid.ctx(); }
   const PlaneReconParameters& parameters() const { return mPar; }
 
  private:
-  void   check(kw_status s) const;
-  void*  deviceBytes(size_t bytes);
-  float* deviceArray(size_t nFloats) { return static_cast<float*>(deviceBytes(nFloats * sizeof(float))); }
-  void   reconstruct(); // the transform stage, in place on the volume
+  void reconstruct(); // the transform stage, in place on the volume
 
   PlaneReconParameters mPar;
-  kw_ctx*      mCtx = nullptr;
-  bool         mFused = false;
+  DeviceGrid   mGrid; // the context, the pipeline and every device array below
   size_t       mRuns = 0;
-  std::vector<void*> mOwned;
   float* mVol = nullptr;     // Lt Ey Ex: the embedded record, then the reconstruction
   float* mSpecA = nullptr;   // rocFFT path: the spectrum of the volume
   float* mSpecB = nullptr;   // rocFFT path: the re-gridded spectrum

@@ -7,6 +7,7 @@
 
 namespace
 {
+// (its own, not GridRule::refuse: this file is built alone by tests/test_thermal_host.py)
 [[noreturn]] void refuse(const std::string& dataset, const std::string& what)
 {
   throw std::invalid_argument(dataset + ": " + what);

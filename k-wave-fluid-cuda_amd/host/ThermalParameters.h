@@ -12,14 +12,13 @@
 #include <string>
 #include <vector>
 
+#include "GridRules.h"
 #include "InputProvider.h"
 
 /// what the thermal solver takes from kwh_options
-struct ThermalOptions
+struct ThermalOptions : DeviceOptions
 {
-  int    deviceIdx    = -1;
-  bool   fusedKernels = true;
-  size_t slabRanks    = 1;
+  size_t slabRanks = 1;
 };
 
 /// a per-point coefficient: an array of the grid's size, or one value

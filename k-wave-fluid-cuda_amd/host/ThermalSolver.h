@@ -1,6 +1,6 @@
 // ThermalSolver.h — explicit k-space time stepping of the Pennes bioheat equation on a periodic grid, with the CEM43
 // thermal dose accumulated on the GPU (DESIGN.md "Bioheat"; what k-Wave's kWaveDiffusion computes).  A second solver
-// beside KSpaceFirstOrderSolver: it owns its own kw_ctx, so acoustic and thermal solvers can share a process.
+// beside KSpaceFirstOrderSolver: it owns its own kw_ctx (a DeviceGrid), so acoustic and thermal solvers can share a process.
 //
 // One step = the diffusion term by FFT stages of the device library, then kw_thermal_update:
 //   Laplacian form (scalar K):  L = F^-1{ -|k|^2 kappa_d F{T} }                   kw_fused_scale_source | rocFFT twins
@@ -11,22 +11,21 @@
 #include <string>
 #include <vector>
 
+#include "DeviceGrid.h"
 #include "ThermalParameters.h"
-#include "kwave_hip.h"
 
 class ThermalSolver
 {
  public:
   explicit ThermalSolver(const ThermalParameters& parameters);
-  ~ThermalSolver();
   ThermalSolver(const ThermalSolver&) = delete;
   ThermalSolver& operator=(const ThermalSolver&) = delete;
 
   /// n steps; heatOn = false leaves Q out (cooling)
   void   run(size_t nSteps, bool heatOn);
   size_t timeIndex() const { return mTimeIndex; }
-  bool   usesFusedPipeline() const { return mFused; }
-  kw_ctx* context() const { return mCtx; }
+  bool   usesFusedPipeline() const { return mGrid.fused(); }
+  kw_ctx* context() const { return mGrid.ctx(); }
   /// "T", "cem43", "T_max", "Q": n floats of the grid
   void   getMatrix(const std::string& name, float* dst, size_t n);
   void   setMatrix(const std::string& name, const float* src, size_t n);
@@ -37,17 +36,12 @@ class ThermalSolver
   size_t sensorSize() const { return mPar.sensorIndex.size(); }
 
  private:
-  float* deviceArray(size_t nFloats);
-  float* upload(const std::vector<float>& host);
-  float* importPadded(const float* reducedDevice);
   float* matrix(const std::string& name, bool forWriting);
   void   diffusionTerm();
 
   ThermalParameters mPar;
-  kw_ctx*           mCtx = nullptr;
-  bool              mFused = false;
+  DeviceGrid        mGrid; // the context, the pipeline and every device array below
   size_t            mTimeIndex = 0;
-  std::vector<void*> mOwned; // every device allocation, freed by the destructor
   float *mT = nullptr, *mCem43 = nullptr, *mTMax = nullptr, *mQ = nullptr;
   float *mA = nullptr, *mP = nullptr, *mTa = nullptr;
   float* mD[3] = { nullptr, nullptr, nullptr };      // Laplacian (mD[0]) or the three terms of the divergence

@@ -91,6 +91,29 @@ void kwh_build_solver(kwh_solver& s, const InputProvider& fileInput, const Param
   catch (...) { g_err = "unknown exception"; return 1; }                                                               \
   return 0;
 
+static DeviceOptions kwh_device_options(const kwh_options* o)
+{
+  DeviceOptions opt;
+  opt.deviceIdx    = o->device_idx;
+  opt.fusedKernels = o->fused_kernels != 0;
+  return opt;
+}
+
+/// the body of kwh_cw_create and its kin: a handle, `build` (the parameters, then the operator) on it, and a failing
+/// device call handed through as its kw_status (KW_ERR_NO_DEVICE among them)
+template <class Handle, class Build>
+static int kwh_create_handle(const char* who, const void* config, const kwh_options* o, Handle** out, Build build)
+{
+  KWH_TRY
+  if (!config || !o || !out) throw std::invalid_argument(std::string(who) + ": NULL argument");
+  *out = nullptr;
+  std::unique_ptr<Handle> s(new Handle());
+  try { build(*s); }
+  catch (const DeviceError& e) { g_err = e.what(); return static_cast<int>(e.status); }
+  *out = s.release();
+  KWH_CATCH
+}
+
 /// a thermal solver with the input it was created from
 struct kwh_thermal
 {
@@ -117,10 +140,7 @@ static CwParameters kwh_cw_parameters(const kwh_cw_config* c, const kwh_options*
   p.ex = c->ex; p.ey = c->ey; p.ez = c->ez;
   if (c->source_scale_kwave != 0) p.kwaveScale();
   else if (c->source_scale_re != 0.0 || c->source_scale_im != 0.0) { p.scaleRe = c->source_scale_re; p.scaleIm = c->source_scale_im; }
-  CwOptions opt;
-  opt.deviceIdx    = o->device_idx;
-  opt.fusedKernels = o->fused_kernels != 0;
-  p.init(opt);
+  p.init(kwh_device_options(o));
   return p;
 }
 
@@ -143,10 +163,7 @@ static AngularParameters kwh_angular_parameters(const kwh_angular_config* c, con
   p.restriction = c->angular_restriction != 0;
   p.ex = c->ex; p.ey = c->ey;
   p.chunkPlanes = c->chunk_planes;
-  AngularOptions opt;
-  opt.deviceIdx    = o->device_idx;
-  opt.fusedKernels = o->fused_kernels != 0;
-  p.init(opt);
+  p.init(kwh_device_options(o));
   return p;
 }
 
@@ -172,10 +189,7 @@ static AngularTimeParameters kwh_angular_time_parameters(const kwh_angular_time_
     throw std::invalid_argument("n_planes: " + std::to_string(c->n_planes) + " is above " + std::to_string(AngularRule::kMaxPlanes));
   if (c->n_planes != 0 && c->z == nullptr) throw std::invalid_argument("z: NULL with n_planes > 0");
   p.z.assign(c->z, c->z + c->n_planes);
-  AngularOptions opt;
-  opt.deviceIdx    = o->device_idx;
-  opt.fusedKernels = o->fused_kernels != 0;
-  p.init(opt);
+  p.init(kwh_device_options(o));
   return p;
 }
 
@@ -196,10 +210,7 @@ static PlaneReconParameters kwh_plane_recon_parameters(const kwh_plane_recon_con
   p.planes = c->planes;
   p.interp = c->interp;
   p.positivity = c->positivity != 0;
-  AngularOptions opt;
-  opt.deviceIdx    = o->device_idx;
-  opt.fusedKernels = o->fused_kernels != 0;
-  p.init(opt);
+  p.init(kwh_device_options(o));
   return p;
 }
 
@@ -489,9 +500,8 @@ int kwh_thermal_create(const kwh_dataset* datasets, size_t n, const kwh_options*
                  DimensionSizes(d.nx, d.ny, d.nz));
   }
   ThermalOptions opt;
-  opt.deviceIdx    = o->device_idx;
-  opt.fusedKernels = o->fused_kernels != 0;
-  opt.slabRanks    = o->slab_ranks ? o->slab_ranks : 1;
+  static_cast<DeviceOptions&>(opt) = kwh_device_options(o);
+  opt.slabRanks = o->slab_ranks ? o->slab_ranks : 1;
   s->params.init(s->input, opt);
   s->solver.reset(new ThermalSolver(s->params));
   *out = s.release();
@@ -579,15 +589,10 @@ int kwh_cw_plan(const kwh_cw_config* config, const kwh_options* o, double* out_t
 
 int kwh_cw_create(const kwh_cw_config* config, const kwh_options* o, kwh_cw** out)
 {
-  KWH_TRY
-  if (!config || !o || !out) throw std::invalid_argument("kwh_cw_create: NULL argument");
-  *out = nullptr;
-  std::unique_ptr<kwh_cw> s(new kwh_cw());
-  s->params = kwh_cw_parameters(config, o);
-  try { s->propagator.reset(new CwPropagator(s->params)); }
-  catch (const CwDeviceError& e) { g_err = e.what(); return static_cast<int>(e.status); } // KW_ERR_NO_DEVICE among them
-  *out = s.release();
-  KWH_CATCH
+  return kwh_create_handle("kwh_cw_create", config, o, out, [&](kwh_cw& s) {
+    s.params = kwh_cw_parameters(config, o);
+    s.propagator.reset(new CwPropagator(s.params));
+  });
 }
 
 int kwh_cw_destroy(kwh_cw* s)
@@ -664,15 +669,10 @@ int kwh_angular_plan(const kwh_angular_config* config, const kwh_options* o, uin
 
 int kwh_angular_create(const kwh_angular_config* config, const kwh_options* o, kwh_angular** out)
 {
-  KWH_TRY
-  if (!config || !o || !out) throw std::invalid_argument("kwh_angular_create: NULL argument");
-  *out = nullptr;
-  std::unique_ptr<kwh_angular> s(new kwh_angular());
-  s->params = kwh_angular_parameters(config, o);
-  try { s->projector.reset(new AngularSpectrum(s->params)); }
-  catch (const CwDeviceError& e) { g_err = e.what(); return static_cast<int>(e.status); } // KW_ERR_NO_DEVICE among them
-  *out = s.release();
-  KWH_CATCH
+  return kwh_create_handle("kwh_angular_create", config, o, out, [&](kwh_angular& s) {
+    s.params = kwh_angular_parameters(config, o);
+    s.projector.reset(new AngularSpectrum(s.params));
+  });
 }
 
 int kwh_angular_destroy(kwh_angular* s)
@@ -745,15 +745,10 @@ int kwh_angular_time_plan(const kwh_angular_time_config* config, const kwh_optio
 
 int kwh_angular_time_create(const kwh_angular_time_config* config, const kwh_options* o, kwh_angular_time** out)
 {
-  KWH_TRY
-  if (!config || !o || !out) throw std::invalid_argument("kwh_angular_time_create: NULL argument");
-  *out = nullptr;
-  std::unique_ptr<kwh_angular_time> s(new kwh_angular_time());
-  s->params = kwh_angular_time_parameters(config, o);
-  try { s->projector.reset(new AngularSpectrumTime(s->params)); }
-  catch (const CwDeviceError& e) { g_err = e.what(); return static_cast<int>(e.status); } // KW_ERR_NO_DEVICE among them
-  *out = s.release();
-  KWH_CATCH
+  return kwh_create_handle("kwh_angular_time_create", config, o, out, [&](kwh_angular_time& s) {
+    s.params = kwh_angular_time_parameters(config, o);
+    s.projector.reset(new AngularSpectrumTime(s.params));
+  });
 }
 
 int kwh_angular_time_destroy(kwh_angular_time* s)
@@ -834,15 +829,10 @@ int kwh_plane_recon_plan(const kwh_plane_recon_config* config, const kwh_options
 
 int kwh_plane_recon_create(const kwh_plane_recon_config* config, const kwh_options* o, kwh_plane_recon** out)
 {
-  KWH_TRY
-  if (!config || !o || !out) throw std::invalid_argument("kwh_plane_recon_create: NULL argument");
-  *out = nullptr;
-  std::unique_ptr<kwh_plane_recon> s(new kwh_plane_recon());
-  s->params = kwh_plane_recon_parameters(config, o);
-  try { s->recon.reset(new PlaneRecon(s->params)); }
-  catch (const CwDeviceError& e) { g_err = e.what(); return static_cast<int>(e.status); } // KW_ERR_NO_DEVICE among them
-  *out = s.release();
-  KWH_CATCH
+  return kwh_create_handle("kwh_plane_recon_create", config, o, out, [&](kwh_plane_recon& s) {
+    s.params = kwh_plane_recon_parameters(config, o);
+    s.recon.reset(new PlaneRecon(s.params));
+  });
 }
 
 int kwh_plane_recon_destroy(kwh_plane_recon* s)

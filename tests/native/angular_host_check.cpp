@@ -1,7 +1,7 @@
 // angular_host_check.cpp — the host side of the angular-spectrum projector as a stand-alone CPU program:
 // AngularParameters::init through valid inputs (the expanded sides and the plane-chunk size by their rules) and refusals.
 // Built with -fsanitize=address,undefined by tests/test_angular_host.py together with host/AngularParameters.cpp and
-// host/CwParameters.cpp (the fast-path length table).  Host code only.
+// host/GridRules.cpp (the shared rules and the fast-path length table).  Host code only.
 // Every case prints "<name>: ok ..." or "<name>: <message>".
 #include <cstdio>
 #include <functional>
@@ -29,7 +29,7 @@ void run(const char* name, const std::function<void(AngularParameters&)>& change
 {
   AngularParameters p = base();
   change(p);
-  AngularOptions o;
+  DeviceOptions o;
   o.fusedKernels = fused;
   try
   {

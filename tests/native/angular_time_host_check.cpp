@@ -1,7 +1,7 @@
 // angular_time_host_check.cpp — the host side of the time-domain angular-spectrum projector as a stand-alone CPU program:
 // AngularTimeParameters::init through valid inputs (the expanded sides and the record length by their rules) and refusals,
 // and the absorption table.  Built with -fsanitize=address,undefined by tests/test_angular_time_host.py together with
-// host/AngularTimeParameters.cpp and host/CwParameters.cpp (the fast-path length table).  Host code only.
+// host/AngularTimeParameters.cpp and host/GridRules.cpp (the shared rules and the fast-path length table).  Host code only.
 // Every case prints "<name>: ok ..." or "<name>: <message>".
 #include <cstdio>
 #include <functional>
@@ -27,7 +27,7 @@ void run(const char* name, const std::function<void(AngularTimeParameters&)>& ch
 {
   AngularTimeParameters p = base();
   change(p);
-  AngularOptions o;
+  DeviceOptions o;
   o.fusedKernels = fused;
   try
   {

@@ -1,6 +1,6 @@
 // cw_host_check.cpp — the host side of the CW field propagator as a stand-alone CPU program: CwParameters::init through
 // its valid inputs (T and the expanded grid by the no-wrap-around rule) and every refusal.  Built with
-// -fsanitize=address,undefined by tests/test_cw_host.py together with host/CwParameters.cpp.
+// -fsanitize=address,undefined by tests/test_cw_host.py together with host/CwParameters.cpp and host/GridRules.cpp.
 // Every case prints "<name>: ok ..." or "<name>: <message>".
 #include <cstdio>
 #include <functional>
@@ -25,7 +25,7 @@ void run(const char* name, const std::function<void(CwParameters&)>& change, boo
 {
   CwParameters p = base();
   change(p);
-  CwOptions o;
+  DeviceOptions o;
   o.fusedKernels = fused;
   try
   {
@@ -52,8 +52,8 @@ int main()
   run("beyond_1024", [](CwParameters& p) { p.nx = 600; p.ny = 16; p.nz = 16; });
   run("kwave_scale", [](CwParameters& p) { p.kwaveScale(); });
   run("lengths", [](CwParameters&) {
-    if (!CwRule::isFastLength(16) || !CwRule::isFastLength(1024) || CwRule::isFastLength(22) || CwRule::nextFastLength(17) != 32 ||
-        CwRule::nextFastLength(1025) != 0 || CwRule::nextFastLength(0) != 16 || CwRule::leastSide(32, 1e-3, 1500.0, 3.7e-5) != 88)
+    if (!GridRule::isFastLength(16) || !GridRule::isFastLength(1024) || GridRule::isFastLength(22) || GridRule::nextFastLength(17) != 32 ||
+        GridRule::nextFastLength(1025) != 0 || GridRule::nextFastLength(0) != 16 || CwRule::leastSide(32, 1e-3, 1500.0, 3.7e-5) != 88)
       throw std::invalid_argument("length table is wrong");
   });
   // ---- refused --------------------------------------------------------------------------------------------------------

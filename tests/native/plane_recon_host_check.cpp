@@ -1,7 +1,7 @@
 // plane_recon_host_check.cpp — the host side of the k-space plane reconstruction as a stand-alone CPU program:
 // PlaneReconParameters::init through valid inputs (the expanded sides and the length of the mirrored record by their rules)
 // and refusals.  Built with -fsanitize=address,undefined by tests/test_plane_recon_host.py together with
-// host/PlaneReconParameters.cpp and host/CwParameters.cpp (the fast-path length table).  Host code only.
+// host/PlaneReconParameters.cpp and host/GridRules.cpp (the shared rules and the fast-path length table).  Host code only.
 // Every case prints "<name>: ok ..." or "<name>: <message>".
 #include <cstdio>
 #include <functional>
@@ -26,7 +26,7 @@ void run(const char* name, const std::function<void(PlaneReconParameters&)>& cha
 {
   PlaneReconParameters p = base();
   change(p);
-  AngularOptions o;
+  DeviceOptions o;
   o.fusedKernels = fused;
   try
   {

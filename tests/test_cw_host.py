@@ -137,7 +137,7 @@ def test_given_time_and_sides_are_kept(cw):
 
 
 def test_host_length_table_is_the_pipelines(cw):
-    """CwParameters.cpp carries its own copy of KW_FUSED_LENGTHS: every length and its neighbours, through the rule"""
+    """GridRules.cpp carries the host's copy of KW_FUSED_LENGTHS: every length and its neighbours, through the rule"""
     lengths = cr.fast_lengths()
     for length in lengths:
         for want in (length, length - 2):
@@ -241,7 +241,8 @@ def test_host_parameters_under_address_and_ub_sanitizers(tmp_path):
     exe = str(tmp_path / "cw_host_check")
     cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
            "-fno-omit-frame-pointer", "-I" + os.path.join(ROOT, "include"), "-I" + host,
-           os.path.join(ROOT, "tests", "native", "cw_host_check.cpp"), os.path.join(host, "CwParameters.cpp"), "-o", exe]
+           os.path.join(ROOT, "tests", "native", "cw_host_check.cpp"), os.path.join(host, "CwParameters.cpp"),
+           os.path.join(host, "GridRules.cpp"), "-o", exe]
     b = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
     assert b.returncode == 0, b.stdout[-4000:]
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120,

@@ -239,7 +239,7 @@ def test_host_parameters_under_address_and_ub_sanitizers(tmp_path):
     cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
            "-fno-omit-frame-pointer", "-I" + os.path.join(ROOT, "include"), "-I" + host,
            os.path.join(ROOT, "tests", "native", "plane_recon_host_check.cpp"),
-           os.path.join(host, "PlaneReconParameters.cpp"), os.path.join(host, "CwParameters.cpp"), "-o", exe]
+           os.path.join(host, "PlaneReconParameters.cpp"), os.path.join(host, "GridRules.cpp"), "-o", exe]
     b = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
     assert b.returncode == 0, b.stdout[-4000:]
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120,
