@@ -157,6 +157,17 @@ def test_pair_stage_at_every_line_length(dev, L):
     assert max(errs) < PARITY
 
 
+@pytest.mark.parametrize("L", LENGTHS)
+def test_pair_stage_at_every_line_length_with_side_array(dev, L):
+    """96 x 16 x L: k_zfused_pair<L> (k_zfused_pair_split for the 2 x 256 form of 512) on three main column tiles (two
+    32-column ones, the second half valid, at 240 and 400) and on the side block of the x-Nyquist column, which reads both
+    operator parts from the per-length side rows that kw_fused_import_reduced wrote.  White-noise sources: that column
+    carries 1 / 96 of the energy.  Measured 2.0e-7 to 2.7e-7 (worst at 864)."""
+    errs = pair_case(dev, 96, 16, L, twin=False)
+    print(f"fused pair 96x16x{L}: rel L2 re {errs[0]:.3e} im {errs[1]:.3e}")
+    assert max(errs) < PARITY
+
+
 @pytest.mark.parametrize("dims", MIXED, ids=["x".join(map(str, d)) for d in MIXED])
 def test_pair_stage_on_mixed_grids_and_its_rocfft_twin(dev, dims):
     errs = pair_case(dev, *dims, twin=True)

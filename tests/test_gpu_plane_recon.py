@@ -133,8 +133,10 @@ def twin_stage(vol, spacing, dt, interps):
 @pytest.mark.parametrize("L", LENGTHS)
 def test_stage_at_every_line_length(dev, L):
     """t-even random volumes.  (16, 16, L): k_zfused_recon<L>, the gather along a line of every length, both interpolants;
-    (L, 16, 16): the side array from L = 32 on, the column addressing and the x-inverse at every length, linear.  The whole
-    expanded output is compared.  Measured 1.7e-7 to 2.5e-7 (worst at 756): white noise needed no smoother input."""
+    (L, 16, 16): the column addressing and the x-passes at every length, linear (where L is a multiple of 32 they write and
+    read the side array, whose y- and z-passes ran at length 16 only).  The whole expanded output is compared.  Measured
+    1.7e-7 to 2.5e-7 (worst at 756): white noise needed no smoother input.  The side array here covers the x-pass side
+    only: k_zfused_recon<L> with a side block is in test_stage_at_every_line_length_with_side_array."""
     for (ex, ey, lt), interps in (((16, 16, L), pr.INTERPS), ((L, 16, 16), ("linear",))):
         assert_margins(ex, ey, lt)
         vol = pr.even_volume((lt, ey, ex), ex * 1009 + ey * 31 + lt)
@@ -143,6 +145,21 @@ def test_stage_at_every_line_length(dev, L):
             err = pr.rel_l2(g, pr.stage(vol, SPACING, DT, C0, interp))
             print(f"plane-recon stage {ex}x{ey}x{lt} {interp}: rel L2 {err:.3e}")
             assert err < PARITY, (ex, ey, lt, interp)
+
+
+@pytest.mark.parametrize("L", LENGTHS)
+def test_stage_at_every_line_length_with_side_array(dev, L):
+    """t-even random volumes of (96, 16, L): k_zfused_recon<L> on three main column tiles (two 32-column ones, the second
+    half valid, at 240 and 400) and on the side block of the x-Nyquist column, which forms the re-gridding weight at
+    kx = Nx/2 for 16 rows ky; both interpolants, the whole expanded output.  Measured 1.9e-7 to 2.8e-7 (worst at 648)."""
+    ex, ey, lt = 96, 16, L
+    assert_margins(ex, ey, lt)
+    vol = pr.even_volume((lt, ey, ex), ex * 1009 + ey * 31 + lt)
+    got = fused_stage(dev, vol, SPACING, DT, pr.INTERPS)
+    for interp, g in zip(pr.INTERPS, got):
+        err = pr.rel_l2(g, pr.stage(vol, SPACING, DT, C0, interp))
+        print(f"plane-recon stage {ex}x{ey}x{lt} {interp}: rel L2 {err:.3e}")
+        assert err < PARITY, (ex, ey, lt, interp)
 
 
 # ---- 2. fused against twin ------------------------------------------------------------------------------------------------

@@ -20,6 +20,16 @@ worst (every stage, variant and chained sequence; the largest in the linear chai
 Per stage the worst line is 1.0e-6 (velocity), 9.9e-7 (initial velocity), 8.9e-7 (velocity gradient), 1.9e-6 (density),
 7.7e-7 (absorption pressure), 8.2e-7 (scale source).  A chained call (KW_FUSED_CHAIN_U / U_IN_SCRATCH / CHAIN_TERMS /
 TERMS_IN_SCRATCH / CHAIN_P / P_IN_SCRATCH) gave the unchained call's result bit for bit everywhere: that is asserted.
+
+Grids with the x-Nyquist column kept apart (the side array: every Nx that is a multiple of 32, asserted at set-up from
+kw_fused_angular_elems): (96, L, 16) and (96, 16, L) at every length, (32, 72, L) and (32, L, 72) at nine lengths whose 72
+line positions end in a partial side block.  There a fourth number is checked per output, the rel-L2 over (z, y) of the
+x-Nyquist component sum_x (-1)^x o[z, y, x]: with white-noise inputs it carries 1 / Nx of the energy, so a fault in a few
+bins of the side array is diluted about tenfold in the whole-array figure and not at all in this one.  Measured worst on
+these grids, under the same rule: whole array 5.6e-7 and upper half 5.5e-7 (96 x 16 x 504), worst line 1.8e-6
+(32 x 72 x 240): the three bounds above stay as they are.  x-Nyquist component 4.9e-7 (96 x 504 x 16) -> 1.9e-6.  (With
+a linear chain, which the two ragged grids of 1024 no longer run to stay within the time of the mixed grids,
+32 x 1024 x 72 gave 5.8e-7, 5.8e-7 and 5.0e-7.)
 """
 import ctypes as C
 import os
@@ -39,6 +49,7 @@ pytestmark = pytest.mark.gpu
 TOL_WHOLE = 2.2e-6
 TOL_LINE = 5e-6
 TOL_UPPER = 2.1e-6
+TOL_NYQUIST = 1.9e-6
 
 CHAIN_U, P_IN_SCRATCH = 1, 2           # kw_fused_velocity flags
 U_IN_SCRATCH, CHAIN_TERMS = 1, 2       # kw_fused_density / kw_fused_velocity_gradient flags
@@ -62,6 +73,16 @@ AXIS_GRIDS = list(dict.fromkeys([(n, 16, 16) for n in LENGTHS] + [(16, n, 16) fo
 TWO_D_NY = 108  # no multiple of 16, 20, 24 or 32: every x tile size ends in a masked tile
 TWO_D_GRIDS = [(n, TWO_D_NY, 1) for n in LENGTHS if n not in NO_TAIL]
 MIXED_GRIDS = [(140, 252, 48), (864, 16, 48), (100, 196, 72)]
+# Nx = 96: 48 main bins (three 16-column tiles; two 32-column tiles, the second half valid, at 240 and 400) and the
+# x-Nyquist column apart as the side array, handled by one more tile index
+SIDE_NX = 96
+SIDE_GRIDS = list(dict.fromkeys([(SIDE_NX, n, 16) for n in LENGTHS] + [(SIDE_NX, 16, n) for n in LENGTHS]))
+# 72 line positions: four and a half 16-position side blocks, two and a quarter 32-position ones.  The lengths: both with
+# 32-column z tiles (240, 400), the shortest, both ends of the 512 split (512, 540), factors 3, 5 and 7, the longest
+RAGGED_NX, RAGGED_POSITIONS = 32, 72
+RAGGED_LENGTHS = (16, 72, 100, 240, 256, 400, 512, 540, 1024)
+RAGGED_SIDE_GRIDS = list(dict.fromkeys([(RAGGED_NX, RAGGED_POSITIONS, n) for n in RAGGED_LENGTHS] +
+                                       [(RAGGED_NX, n, RAGGED_POSITIONS) for n in RAGGED_LENGTHS]))
 
 
 def _g(x):
@@ -125,12 +146,30 @@ def metrics(got, ref, axes):
     return whole, line, upper
 
 
+def nyquist_error(got, ref):
+    """rel-L2 over (z, y) of the x-Nyquist component sum_x (-1)^x o[z, y, x]: what the side array alone carries"""
+    sign = 1.0 - 2.0 * (np.arange(ref.shape[2]) % 2)
+    g, r = got.astype(np.float64) @ sign, ref @ sign
+    nref = np.linalg.norm(r)
+    if nref == 0.0:
+        assert np.max(np.abs(g)) == 0.0
+        return 0.0
+    return float(np.linalg.norm(g - r) / nref)
+
+
 class Checker:
-    def __init__(self, axes):
-        self.axes, self.rows = axes, []
+    def __init__(self, axes, nyquist=False):
+        self.axes, self.rows, self.nyquist = axes, [], ([] if nyquist else None)
 
     def __call__(self, label, got, ref):
         self.rows.append((label,) + metrics(got, ref, self.axes))
+        if self.nyquist is not None:
+            self.nyquist.append((label + " x-Nyquist", nyquist_error(got, ref)))
+
+    def worst(self):
+        """(whole, line, upper, x-Nyquist) maxima over the rows compared with fp64"""
+        rows = [r[1:] for r in self.rows if not r[0].endswith("vs unchained")]
+        return tuple(max(r[i] for r in rows) for i in range(3)) + (max((v for _, v in self.nyquist or []), default=0.0),)
 
     def chain(self, label, chained, unchained):
         """chained and unchained calls run the same arithmetic: the number of elements that differ in any bit"""
@@ -145,6 +184,7 @@ class Checker:
                     bad.append((label, w))
             elif not (w <= TOL_WHOLE and ln <= TOL_LINE and up <= TOL_UPPER):
                 bad.append((label, w, ln, up))
+        bad += [(label, v) for label, v in self.nyquist or [] if not v <= TOL_NYQUIST]
         return bad
 
 
@@ -167,6 +207,11 @@ class Grid:
         assert ok.value == 1, dims
         d.call("fused_create")
         n = C.c_size_t()
+        # a plane of the pipeline's layout: rows of Nx/2 bins and the x-Nyquist column behind them (the side array), or
+        # rows of Nx/2 + 1 bins padded to whole 16-column tiles
+        d.call("fused_angular_elems", C.byref(n))
+        assert n.value in ((nx // 2 + 1) * ny, (nx // 2 + 1 + 15) // 16 * 16 * ny), (dims, n.value)
+        self.side = n.value == (nx // 2 + 1) * ny and (nx // 2 + 1) % 16 != 0
         d.call("fused_reduced_elems", C.byref(n))
         self.ops = make_operators(syn, self.rng, nx, ny, nz)
         self.padded = {}
@@ -386,10 +431,12 @@ def run_chain(g, chk, kind):
         chk.chain(f"chain {kind} {k}", v, plain[k][0])
 
 
-def check_grid(syn, dims, axes, chains, plane_kernels=1):
+def check_grid(syn, dims, axes, chains, plane_kernels=1, side=False):
+    """side: the grid must keep its x-Nyquist column as the side array, and that component is checked on its own"""
     g = Grid(syn, dims, plane_kernels)
     try:
-        chk = Checker(axes)
+        assert g.side or not side, dims
+        chk = Checker(axes, nyquist=side)
         run_stages(g, chk)
         for kind in chains:
             run_chain(g, chk, kind)
@@ -400,6 +447,7 @@ def check_grid(syn, dims, axes, chains, plane_kernels=1):
 
 
 def _assert_ok(chk, dims):
+    print("%s: worst whole %.3e line %.3e upper %.3e x-Nyquist %.3e" % ((dims,) + chk.worst()))
     bad = chk.failures()
     assert not bad, (dims, bad[:8])
 
@@ -421,6 +469,24 @@ def test_stages_every_length(syn, dims):
 def test_stages_masked_x_tiles_2d(syn, dims):
     """2-D grids whose Ny rows end in a partial x tile (TAIL kernels)"""
     _assert_ok(check_grid(syn, dims, (1, 2), (CHAIN_KINDS[TWO_D_GRIDS.index(dims) % 3],)), dims)
+
+
+@pytest.mark.parametrize("dims", SIDE_GRIDS, ids=lambda d: "x".join(map(str, d)))
+def test_stages_every_length_with_side_array(syn, dims):
+    """(96, L, 16) and (96, 16, L): every y- and z-pass kernel at every length with three (at 240 and 400 along z: one
+    and a half) main column tiles and the side block of the x-Nyquist column, whose lanes are line positions and whose
+    operators k_import_reduced_side laid out per length; one chained sequence per grid, in turn"""
+    axes = tuple(2 - a for a in (1, 2) if dims[a] != 16) or (0, 1)  # array axes are (z, y, x)
+    _assert_ok(check_grid(syn, dims, axes, (CHAIN_KINDS[SIDE_GRIDS.index(dims) % 3],), side=True), dims)
+
+
+@pytest.mark.parametrize("dims", RAGGED_SIDE_GRIDS, ids=lambda d: "x".join(map(str, d)))
+def test_stages_ragged_side_blocks(syn, dims):
+    """(32, 72, L) and (32, L, 72): 72 line positions end in a partial side block, in the z-pass (positions are ky) and in
+    the y-pass (positions are z): the dead, masked and clamped lanes of tile_coord; one chained sequence per grid, in
+    turn, but for the two grids of 1024"""
+    chains = () if max(dims) == 1024 else (CHAIN_KINDS[RAGGED_SIDE_GRIDS.index(dims) % 3],)  # 2.4 M points: stages only
+    _assert_ok(check_grid(syn, dims, (0, 1, 2), chains, side=True), dims)
 
 
 def test_lengths_without_tails_refused_in_2d():
