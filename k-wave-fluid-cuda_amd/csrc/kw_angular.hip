@@ -131,8 +131,8 @@ __device__ __forceinline__ void mix_bin(const float2& x, const float2& y, float 
 }
 
 // =====================================================================================================================
-// y-inverse of the projector: tile (kx tile = blockIdx.x, plane = blockIdx.y of the chunk).  k_ypass<L, kInv>'s geometry,
-// addressing and exchange, with three differences:
+// y-inverse of the projector: tile (kx tile = blockIdx.x, plane = blockIdx.y of the chunk).  A y-pass whose body spells
+// the line-tile steps of kw_fused.hip out (see "line-tile steps" there for why); its own:
 //   - the input lines are the SOURCE's 2-D spectra a.in[0] (Sr^) and a.in[1] (Si^): the same lines for every plane, no z
 //     in the address (side blocks: every lane reads the one side column, whatever its plane)
 //   - before the transform each bin is multiplied: the five table lines are read at the very addresses of the spectrum

@@ -84,32 +84,26 @@ __device__ __forceinline__ float2 time_mul(const float2& x, float hr, float hi)
 
 // =====================================================================================================================
 // z-pass of the projector: tile (ky = blockIdx.y, kx tile = blockIdx.x; the side array's blocks as in tile_coord) of the
-// kept spectrum.  k_zfused<L, Z_SOURCE>'s geometry, addressing and exchange, with two differences:
+// kept spectrum, on the line-tile steps (kw_fused.hip).  Its own:
 //   - the lines are read from a.in (the kept spectrum) and written to a.out (scratch array 0): a.in survives for the next
 //     plane
-//   - after the forward transform thread (c, j) holds the bins m = j + R1 k2; it forms H(kx of its column, ky, m) there
-//     and multiplies.  Nothing but the Lt/2 + 1 values of a.ak is read for it.  time_h is called, not inlined (see
+//   - after the forward transform row thread (c, j) holds the bins m = j + R1 k2; it forms H(kx of its column, ky, m)
+//     there and multiplies.  Nothing but the Lt/2 + 1 values of a.ak is read for it.  time_h is called, not inlined (see
 //     there); its constants and a.ak are staged in LDS once per block.
+//   load | barrier (twiddles, aks, gsh) | fwd_cols | barrier | fwd_rows -> H | inverse_from_regs -> store
 // =====================================================================================================================
 template<int L> __global__ __launch_bounds__((Geo<L, nl_z(L)>::THREADS)) void k_zfused_time(ZTimeArgs a)
 {
   using G = Geo<L, nl_z(L)>;
   constexpr int R1 = G::R1, R2 = G::R2;
-  constexpr bool WA = (R2 == G::TPL) || ((G::NL * R2) % 64 == 0 && 64 % G::NL == 0); // step-A participants: whole waves
   __shared__ float2 lds[G::LDSB];
   __shared__ float2 twl[G::TWN];
   __shared__ double aks[L / 2 + 1]; // a.ak, read once per block instead of once per bin
   __shared__ TimeH  gsh;
   load_twiddles<L>(twl, a.tw);
-  const int       c     = threadIdx.x % G::NL;
-  const int       j     = threadIdx.x / G::NL;
-  const TileCoord tc    = tile_coord<G::NL>(a.nxc, a.P, a.side_off, gridDim.y, c);
-  if (tc.dead) return;
-  const uint32_t ky     = tc.pos;
-  const bool     valid  = tc.valid;
-  const uint32_t zstr   = a.ny * tc.pitch;
-  const uint32_t base   = ky * tc.pitch + (tc.side ? 0u : tc.kx) + tc.off;
-  const uint32_t basel  = ky * tc.pitch + tc.col + tc.off;
+  const LineTile t      = line_tile<G>(a.nxc, a.P, a.side_off, a.ny, 1u);
+  if (t.tc.dead) return;
+  const int      c      = t.c, j = t.j;
   if (a.ak != nullptr)
     for (int e = threadIdx.x; e < L / 2 + 1; e += blockDim.x) aks[e] = a.ak[e];
   if (threadIdx.x == 0)
@@ -124,31 +118,18 @@ template<int L> __global__ __launch_bounds__((Geo<L, nl_z(L)>::THREADS)) void k_
   } // (both published by the barrier that publishes the twiddle table)
 
   float2 v[R1];
-  if (ACTW(R2, j))
-  {
-    const float2* __restrict__ in = a.in;
-    const uint32_t lb = (basel + static_cast<uint32_t>(j) * zstr) * static_cast<uint32_t>(sizeof(float2));
-#pragma unroll
-    for (int n1 = 0; n1 < R1; n1++) v[n1] = ld_uni<WA>(in, static_cast<uint64_t>(n1 * R2) * zstr, lb);
-  }
+  if (ACTW(R2, j)) load_lines<G>(v, a.in, t);
   lds_barrier(); // twiddle table visible (the loads above stay in flight across it)
 
-  if (ACTW(R2, j))
-  {
-    step_a<L, kFwd>(v, j, twl);
-#pragma unroll
-    for (int k1 = 0; k1 < R1; k1++) lds[k1 * G::SF + j * G::NL + c] = v[k1];
-  }
+  if (ACTW(R2, j)) fwd_cols<L, kFwd, G::NL>(v, lds, c, j, twl);
   lds_barrier();
   float2 X[R2];
   if (ACTW(R1, j))
   {
-#pragma unroll
-    for (int n2 = 0; n2 < R2; n2++) X[n2] = lds[j * G::SF + n2 * G::NL + c];
-    Dft<R2, kFwd>::run(X);
+    fwd_rows<L, kFwd, G::NL>(X, lds, c, j);
     const TimeHLds gl = (TimeHLds)&gsh;
     // the true column: the side array holds bin Ex/2 = a.nxc; pad lanes (never stored) take the last main column
-    const double kr2 = time_kr2(a.dkx, a.dky, a.ex, a.ny, tc.side ? a.nxc : tc.col, ky);
+    const double kr2 = time_kr2(a.dkx, a.dky, a.ex, a.ny, t.tc.side ? a.nxc : t.tc.col, t.pos);
 #pragma unroll
     for (int k2 = 0; k2 < R2; k2++)
     {
@@ -159,14 +140,7 @@ template<int L> __global__ __launch_bounds__((Geo<L, nl_z(L)>::THREADS)) void k_
 
   float2 r[R1];
   inverse_from_regs<L, false, G::NL>(X, r, lds, c, j, twl);
-  if (ACTW(R2, j) && valid)
-  {
-    float2* __restrict__ out = a.out;
-    uint32_t ob = base + static_cast<uint32_t>(j) * zstr;
-    asm volatile("" : "+v"(ob));
-#pragma unroll
-    for (int q2 = 0; q2 < R1; q2++) st_uni<WA>(out, static_cast<uint64_t>(R2 * q2) * zstr, ob * static_cast<uint32_t>(sizeof(float2)), r[q2]);
-  }
+  store_lines<G>(a.out, t, r);
 }
 
 // the rocFFT twin: out[e] = spec[e] H on the natural [lt][ey][ex/2 + 1] half-spectrum, out of place
@@ -293,12 +267,7 @@ kw_status zfused_time(kw_ctx* ctx, const float2* in, float2* out, const kw_angul
   a.ny       = c.ny;
   a.nz       = c.nz;
   a.side_off = f.side_off;
-  const uint32_t side_tile = (f.side_off != 0) ? 1u : 0u;
-  const dim3 grid(z_tiles(f.P, c.nz) + side_tile, c.ny, 1);
-#define M(LEN) LAUNCH((k_zfused_time<LEN>), grid, dim3((Geo<LEN, nl_z(LEN)>::THREADS)), a)
-  KW_LEN_SWITCH(c.nz, M)
-#undef M
-  return KW_OK;
+  return KW_LAUNCH_ZPASS((k_zfused_time<LEN>), c.nz, z_pass_grid(ctx, nl_z(c.nz)), a);
 }
 
 } // namespace kwfused

@@ -20,8 +20,9 @@ namespace {
 
 // =====================================================================================================================
 // z-fused pair: tile (ky = blockIdx.y, kx tile = blockIdx.x) of the two spectra a.in[0] (Sr^) and a.in[1] (Si^), the
-// operators a.op[0] = Gr and a.op[1] = Gi in the imported run layout (load_op_run).  The geometry, addressing and the
-// exchange-buffer discipline are k_zfused's:
+// operators a.op[0] = Gr and a.op[1] = Gi in the imported run layout (load_op_run).  The body spells the line-tile steps
+// of kw_fused.hip out, as k_zfused does (see "line-tile steps" there for why and for the exchange-buffer discipline);
+// its own are the second array and the 2x2 mix:
 //   forward 0   write columns | barrier | read rows            (array 1's lines requested before the barrier: in flight
 //   barrier                                                      during array 0's transform, as in Z_ABSORB)
 //   forward 1   write columns | barrier | read rows   -> mix in registers
@@ -35,7 +36,7 @@ template<int L> __global__ __launch_bounds__((Geo<L, nl_z(L)>::THREADS)) void k_
 {
   using G = Geo<L, nl_z(L)>;
   constexpr int R1 = G::R1, R2 = G::R2;
-  constexpr bool WA = (R2 == G::TPL) || ((G::NL * R2) % 64 == 0 && 64 % G::NL == 0); // step-A participants: whole waves
+  constexpr bool WA = G::WA;
   __shared__ float2 lds[G::LDSB];
   __shared__ float2 twl[G::TWN];
   load_twiddles<L>(twl, a.tw);
@@ -135,7 +136,7 @@ template<int L> __global__ __launch_bounds__((Geo<L, nl_z(L)>::THREADS)) void k_
   }
 }
 
-// The same on lines of 512 = 2 x 256 (k_zfused_split's scheme; the operators are imported in ITS run layout whenever
+// The same on lines of 512 = 2 x 256 (k_zfused_split's steps; the operators are imported in ITS run layout whenever
 // kw_tuning::split512 is on, so this is the form that goes with them).  Eight 256-point exchanges per tile — two forward
 // halves per array, two inverse halves per output — each writing exactly the cells its thread read in the one before
 // (column / row / column / row ...): the only barriers are the ones inside them.
@@ -149,54 +150,21 @@ template<int L> __global__ __launch_bounds__(Geo<L / 2>::THREADS) void k_zfused_
   __shared__ float2 twl[G::TWN];
   __shared__ float2 tw2[H];
   load_twiddles_split<L>(twl, tw2, a.tw);
-  const int       c     = threadIdx.x % G::NL;
-  const int       j     = threadIdx.x / G::NL;
-  const TileCoord tc    = tile_coord<G::NL>(a.nxc, a.P, a.side_off, gridDim.y, c);
-  if (tc.dead) return;
-  const uint32_t ky     = tc.pos;
-  const bool     valid  = tc.valid;
-  const uint32_t zstr   = a.ny * tc.pitch;
-  const uint32_t base   = ky * tc.pitch + (tc.side ? 0u : tc.kx) + tc.off;
-  const uint32_t basel  = ky * tc.pitch + tc.col + tc.off;
-  constexpr int  OPV    = op_vec(2 * R2); // run of this thread: bins 2*(j + R1*k2) + h at run index 2*k2 + h
-  const uint32_t opbase = tc.side ? a.op_side_off + (((ky / NLMAX) * (2 * R2 / OPV) * R1 + j) * NLMAX + ky % NLMAX) * OPV
-                                  : (((ky * (a.Pop / NLMAX) + tc.col / NLMAX) * (2 * R2 / OPV) * R1 + j) * NLMAX + tc.col % NLMAX) * OPV;
+  const LineTile t      = line_tile<G>(a.nxc, a.P, a.side_off, a.ny, 1u);
+  if (t.tc.dead) return;
+  const int      c      = t.c, j = t.j;
+  const uint32_t opbase = op_run_base<2 * R2, R1>(t, a.Pop, a.op_side_off); // run: bins 2*(j + R1*k2) + h at run index 2*k2 + h
 
   float2 Xa[R2], Xb[R2], Ya[R2], Yb[R2]; // after the forward transforms: bins 2*(j + R1*k2) and 2*(j + R1*k2) + 1
   {
     float2 va[R1], vb[R1], ua[R1], ub[R1];
-    const float2* __restrict__ in0 = a.in[0];
-    const float2* __restrict__ in1 = a.in[1];
-    const uint32_t lb = (basel + static_cast<uint32_t>(j) * zstr) * static_cast<uint32_t>(sizeof(float2));
-#pragma unroll
-    for (int n1 = 0; n1 < R1; n1++)
-    {
-      va[n1] = ld_uni(in0, static_cast<uint64_t>(n1 * R2) * zstr, lb);
-      vb[n1] = ld_uni(in0, static_cast<uint64_t>(H + n1 * R2) * zstr, lb);
-    }
-#pragma unroll
-    for (int n1 = 0; n1 < R1; n1++)
-    { // the second array's lines: in flight during the first array's transforms
-      ua[n1] = ld_uni(in1, static_cast<uint64_t>(n1 * R2) * zstr, lb);
-      ub[n1] = ld_uni(in1, static_cast<uint64_t>(H + n1 * R2) * zstr, lb);
-    }
+    load_split_halves<L>(va, vb, a.in[0], t);
+    load_split_halves<L>(ua, ub, a.in[1], t); // the second array's lines: in flight during the first array's transforms
     lds_barrier(); // twiddle tables visible
-#pragma unroll
-    for (int n1 = 0; n1 < R1; n1++)
-    {
-      const float2 lo = va[n1], hi = vb[n1];
-      va[n1] = cadd(lo, hi);
-      vb[n1] = apply_tw<kFwd>(csub(lo, hi), tw2[n1 * R2 + j]);
-    }
+    split_butterfly<L>(va, vb, j, tw2);
     line_fft<H, kFwd>(va, Xa, lds, c, j, twl);
     line_fft<H, kFwd, true>(vb, Xb, lds, c, j, twl);
-#pragma unroll
-    for (int n1 = 0; n1 < R1; n1++)
-    {
-      const float2 lo = ua[n1], hi = ub[n1];
-      ua[n1] = cadd(lo, hi);
-      ub[n1] = apply_tw<kFwd>(csub(lo, hi), tw2[n1 * R2 + j]);
-    }
+    split_butterfly<L>(ua, ub, j, tw2);
     line_fft<H, kFwd>(ua, Ya, lds, c, j, twl);       // after a read by columns: writes columns
     line_fft<H, kFwd, true>(ub, Yb, lds, c, j, twl); // after a read by rows: writes rows
   }
@@ -228,19 +196,7 @@ template<int L> __global__ __launch_bounds__(Geo<L / 2>::THREADS) void k_zfused_
       for (int k2 = 0; k2 < R2; k2++) w[k2] = o ? Yb[k2] : Xb[k2];
       inverse_from_regs<H>(w, rb, lds, c, j, twl);       // after a read by rows: write rows
     }
-    if (valid)
-    {
-      float2* __restrict__ out = a.out[o];
-      uint32_t ob = base + static_cast<uint32_t>(j) * zstr;
-      asm volatile("" : "+v"(ob));
-#pragma unroll
-      for (int q2 = 0; q2 < R1; q2++)
-      { // n = j + R2*q2
-        const float2 t = apply_tw<kInv>(rb[q2], tw2[j + R2 * q2]);
-        st_uni(out, static_cast<uint64_t>(R2 * q2) * zstr, ob * static_cast<uint32_t>(sizeof(float2)), cadd(ra[q2], t));
-        st_uni(out, static_cast<uint64_t>(H + R2 * q2) * zstr, ob * static_cast<uint32_t>(sizeof(float2)), csub(ra[q2], t));
-      }
-    }
+    store_split_halves<L>(a.out[o], t, ra, rb, tw2);
   }
 }
 
@@ -488,17 +444,12 @@ kw_status zfused_pair(kw_ctx* ctx, ZArgs a)
   a.ny          = f.nyl;
   a.nz          = f.nz_global;
   a.narr        = 2;
-  const uint32_t side_tile = (f.side_off != 0) ? 1u : 0u;
   if (f.nz_global == 512 && f.split512)
   {
-    LAUNCH((k_zfused_pair_split<512>), dim3(f.P / NLMAX + side_tile, f.nyl, 1), dim3(Geo<256>::THREADS), a);
+    LAUNCH((k_zfused_pair_split<512>), z_pass_grid(ctx, NLMAX), dim3(Geo<256>::THREADS), a);
     return KW_OK;
   }
-  const dim3 grid(z_tiles(f.P, f.nz_global) + side_tile, f.nyl, 1);
-#define M(LEN) LAUNCH((k_zfused_pair<LEN>), grid, dim3((Geo<LEN, nl_z(LEN)>::THREADS)), a)
-  KW_LEN_SWITCH(f.nz_global, M)
-#undef M
-  return KW_OK;
+  return KW_LAUNCH_ZPASS((k_zfused_pair<LEN>), f.nz_global, z_pass_grid(ctx, nl_z(f.nz_global)), a);
 }
 
 } // namespace kwfused

@@ -34,6 +34,7 @@
 #include "kw_internal.h"
 
 #include <cmath>
+#include <type_traits>
 
 using namespace kwfft;
 
@@ -290,6 +291,8 @@ template<int L, int NLV = nl_yz(L)> struct Geo
   static constexpr int NL      = NLV;
   static constexpr int TPL     = cmax(R1, R2);
   static constexpr int THREADS = NL * TPL;
+  // y/z passes: the R2 threads per line of a step-A region (line loads and stores) are whole waves — see ACTW, ld_uni<PIN>
+  static constexpr bool WA     = (R2 == TPL) || ((NL * R2) % 64 == 0 && 64 % NL == 0);
   // y/z passes: LDS[k1][n2][c]; +16 complex per k1 block keeps the step-B reads conflict-free
   static constexpr int PADB    = NL;
   static constexpr int SF      = R2 * NL + PADB; // stride per k1 (forward and inverse use the same cells, see inverse_from_regs)
@@ -490,113 +493,135 @@ template<int L, int DIR> __device__ __forceinline__ void step_a(float2 (&v)[Fac<
   for (int k1 = 1; k1 < Fac<L>::R1; k1++) v[k1] = apply_tw<DIR>(v[k1], twl[k1 * Geo<L>::TP + n2]);
 }
 
-// =====================================================================================================================
-// y-pass: in-place complex FFT along y (stride P) for tile (z = blockIdx.y, kx tile = blockIdx.x), array blockIdx.z
-// =====================================================================================================================
+// ---- line-tile steps ------------------------------------------------------------------------------------------------
+// What a y- or z-pass kernel is assembled from: the block's tile, the line loads and stores, and the two exchanges of a
+// four-step transform through the block's buffer lds[G::LDSB].  A kernel's body keeps what is its own — which arrays,
+// what happens to a bin between the transforms — and the order of loads, barriers and stores.
+// On the steps: k_zfused_split, k_zfused_pair_split (kw_cw.hip), k_zfused_time (kw_angular_time.hip), k_zfused_recon
+// (kw_plane_recon.hip); k_ypass and k_ypass_split take the tile and keep their RowAddr loads and stores.  k_zfused,
+// k_zfused_pair (kw_cw.hip) and k_yinv_angular (kw_angular.hip) spell the same steps out in their bodies: assembled from
+// the functions below the compiler allocates their guarded (non-whole-wave) and spilling instantiations differently — an
+// occupancy step lost at some lengths, scratch bytes gained at others — so they stay as they were written.  A change to
+// a step below is a change to those three bodies as well.
+//
+// Who calls a step.  Threads are laid out t = j * NL + c.  A thread with ACTW(R2, j) is "column thread" n2 = j of its
+// line (c): it holds the R1 elements x[n1 * R2 + j] before a forward transform and after an inverse.  A thread with
+// ACTW(R1, j) is "row thread" k1 = j: it holds the R2 bins X[j + R1 * k2] between them.  load_lines and
+// fwd_cols are for column threads, fwd_rows is for row threads, and the kernel calls them under that guard (it usually
+// has more to do under the same one); store_lines and inverse_from_regs make the test themselves and are called by
+// every thread.
+//
+// Exchange-buffer discipline.  Cell (k1, n2) of column c is lds[k1 * SF + n2 * NL + c].  In a forward exchange column
+// thread n2 writes the cells (k1, n2) for all k1 ("its column") and, after a barrier, row thread k1 reads (k1, n2) for
+// all n2 ("its row").  inverse_from_regs runs that backwards over the same cells: row thread k1 writes its row — cells
+// nobody else has read — and, after a barrier, column thread q1 reads its column.  A thread therefore only ever
+// overwrites what it read last itself: no barrier is needed between a forward read and the inverse's write, nor between
+// the inverse's read and the next forward write.  Two exchanges of the same direction in a row do need one (the second
+// one's writers overwrite cells other threads may still be reading), unless the second runs transposed (ROWWRITE /
+// COLWRITE, square factorisations), which restores "writes what it has just read".
 
-// PIN / POUT: packed (per-peer chunk) addressing on the input / output side; the natural layout is the cheap
-// compile-time-strided case  element(k) = base + k * P.
-template<int L, int DIR, bool PIN, bool POUT>
-__global__ __launch_bounds__(Geo<L>::THREADS) void k_ypass(PassArgs a)
+// The block's tile and this thread's place in it.  Element n of the thread's line (position pos, column c of the tile)
+// is element base + n * lstride of a scratch array; loads use basel instead, whose pad lanes re-read the last column.
+struct LineTile
 {
-  using G = Geo<L>;
-  constexpr int R1 = G::R1, R2 = G::R2;
-  __shared__ float2 lds[G::LDSB];
-  __shared__ float2 twl[G::TWN];
-  load_twiddles<L>(twl, a.tw);
-  const int      c     = threadIdx.x % G::NL;
-  const int      j     = threadIdx.x / G::NL;
-  const TileCoord tc   = tile_coord<G::NL>(a.nxc, a.P, a.side_off, gridDim.y, c);
-  if (tc.dead) return;
-  const uint32_t kx    = tc.side ? 0u : tc.kx; // addressing column (side blocks: the one column of the side array)
-  const bool     valid = tc.valid;
-  const uint32_t kxl   = tc.col;
-  const uint32_t z     = tc.pos + a.z0;
-  const uint32_t Pe    = tc.pitch, soff = tc.off; // row pitch / offset of the region (main rows, or the side array)
-  const uint32_t PXe   = tc.side ? 1u : a.PX;     // the same on the packed (exchange) side: per-peer chunks of the side array
-  const uint32_t arr0  = blockIdx.z * a.narr; // each block takes a.narr arrays back to back (next one's lines prefetched)
+  int       c, j;    // column of the tile; thread row (n2 = j as a column thread, k1 = j as a row thread)
+  TileCoord tc;
+  uint32_t  pos;     // line position: ky (z-pass) / z (y-pass), the launch's first position included
+  bool      valid;   // the column exists (or, in a side block, the position): its results are stored
+  uint32_t  lstride; // element stride along the line
+  uint32_t  base, basel;
+};
+// lmul / bmul: strides along the line and from one line position to the next, in rows of the block's region (its pitch:
+// P, or 1 in the side array).  z-pass: (ny, 1); y-pass: (1, ny); lines with free strides and no side array (Z_SHIFT):
+// P = 1 and the strides in elements.  The caller returns at once when tc.dead (a side block past the last position).
+template<class G>
+__device__ __forceinline__ LineTile line_tile(uint32_t nxc, uint32_t P, uint32_t side_off, uint32_t lmul, uint32_t bmul,
+                                              uint32_t pos0 = 0)
+{
+  LineTile t;
+  t.c       = threadIdx.x % G::NL;
+  t.j       = threadIdx.x / G::NL;
+  t.tc      = tile_coord<G::NL>(nxc, P, side_off, gridDim.y, t.c);
+  t.pos     = t.tc.pos + pos0;
+  t.valid   = t.tc.valid;
+  t.lstride = lmul * t.tc.pitch;
+  const uint32_t bstride = bmul * t.tc.pitch;
+  t.base    = t.pos * bstride + (t.tc.side ? 0u : t.tc.kx) + t.tc.off;
+  t.basel   = t.pos * bstride + t.tc.col + t.tc.off;
+  return t;
+}
 
-  auto load_lines = [&](float2 (&v)[R1], const float2* __restrict__ Sin) {
-    if (PIN)
-    {
-#pragma unroll
-      for (int n1 = 0; n1 < R1; n1++) v[n1] = Sin[a.ain.row(z, n1 * R2 + j) * PXe + kxl + soff];
-    }
-    else
-    {
-      uint32_t b = (z * a.ain.zmul + j * a.ain.estride) * Pe + kxl + soff; // estride = 1 (y lines) or ny (z probe)
-      asm volatile("" : "+v"(b));
-      const uint32_t step = R2 * a.ain.estride * Pe;
-#pragma unroll
-      for (int n1 = 0; n1 < R1; n1++)
-        v[n1] = ld_uni(Sin, static_cast<uint64_t>(n1) * step, b * static_cast<uint32_t>(sizeof(float2)));
-    }
-  };
+// Operators live in a tile-blocked layout [ky][kx tile][kz][16]: the 16 x nz values of a z-pass block's tile are one
+// contiguous run (k_import_reduced), instead of 64-B pieces a whole plane apart.  Index of vector q = 0 of row thread
+// t.j's run of RUN values (load_op_run); side blocks: the side column's values are stored like one more row of tiles
+// whose columns are the ky, op_side_off floats into the array.
+template<int RUN, int R1>
+__device__ __forceinline__ uint32_t op_run_base(const LineTile& t, uint32_t Pop, uint32_t op_side_off)
+{
+  constexpr int  OPV = op_vec(RUN);
+  const uint32_t ky  = t.pos;
+  return t.tc.side ? op_side_off + (((ky / NLMAX) * (RUN / OPV) * R1 + t.j) * NLMAX + ky % NLMAX) * OPV
+                   : (((ky * (Pop / NLMAX) + t.tc.col / NLMAX) * (RUN / OPV) * R1 + t.j) * NLMAX + t.tc.col % NLMAX) * OPV;
+}
 
-  float2 v[R1];
-  if (ACTW(R2, j)) load_lines(v, a.in[arr0]);
-  lds_barrier(); // twiddle table visible (the line loads stay in flight across it)
-#pragma unroll 1
-  for (uint32_t ia = 0; ia < a.narr; ia++)
+// Column thread: its R1 line elements x[n1 * R2 + j].  PIN as in ld_uni: G::WA wherever the guard can split a wave.
+template<class G, bool PIN = G::WA>
+__device__ __forceinline__ void load_lines(float2 (&v)[G::R1], const float2* __restrict__ in, const LineTile& t)
+{
+  const uint32_t lb = (t.basel + static_cast<uint32_t>(t.j) * t.lstride) * static_cast<uint32_t>(sizeof(float2));
+#pragma unroll
+  for (int n1 = 0; n1 < G::R1; n1++) v[n1] = ld_uni<PIN>(in, static_cast<uint64_t>(n1 * G::R2) * t.lstride, lb);
+}
+// Every thread: a column thread's x[j + R2 * q2] after an inverse, where the column is valid.  The element index is
+// laundered through an empty asm, which makes the address arithmetic per store (and, in the kernels that request the
+// next array's lines inside their loop, per load): left alone the compiler hoists it, and 16 hoisted 64-bit addresses
+// cost an occupancy step.
+template<class G, bool PIN = G::WA>
+__device__ __forceinline__ void store_lines(float2* __restrict__ out, const LineTile& t, const float2 (&r)[G::R1])
+{
+  if (ACTW(G::R2, t.j) && t.valid)
   {
-    if (ACTW(R2, j))
-    {
-      const float2* __restrict__ m = a.mul[arr0 + ia];
-      if (m != nullptr)
-      {
+    uint32_t ob = t.base + static_cast<uint32_t>(t.j) * t.lstride;
+    asm volatile("" : "+v"(ob));
 #pragma unroll
-        for (int n1 = 0; n1 < R1; n1++) v[n1] = cmulf(v[n1], m[n1 * R2 + j]);
-      }
-      step_a<L, DIR>(v, j, twl);
-#pragma unroll
-      for (int k1 = 0; k1 < R1; k1++) lds[k1 * G::SF + j * G::NL + c] = v[k1];
-      if (ia + 1 < a.narr) load_lines(v, a.in[arr0 + ia + 1]);
-    }
-    lds_barrier();
-    if (ACTW(R1, j))
-    {
-      float2 w[R2];
-#pragma unroll
-      for (int n2 = 0; n2 < R2; n2++) w[n2] = lds[j * G::SF + n2 * G::NL + c];
-      Dft<R2, DIR>::run(w);
-      if (valid)
-      {
-        float2* __restrict__ Sout = a.out[arr0 + ia];
-        if (POUT)
-        {
-#pragma unroll
-          for (int k2 = 0; k2 < R2; k2++) Sout[a.aout.row(z, j + R1 * k2) * PXe + kx + soff] = w[k2];
-        }
-        else
-        {
-          uint32_t b = (z * a.aout.zmul + j * a.aout.estride) * Pe + kx + soff;
-          asm volatile("" : "+v"(b));
-          const uint32_t step = R1 * a.aout.estride * Pe;
-#pragma unroll
-          for (int k2 = 0; k2 < R2; k2++) st_uni(Sout, static_cast<uint64_t>(k2) * step, b * static_cast<uint32_t>(sizeof(float2)), w[k2]);
-        }
-      }
-    }
-    if (ia + 1 < a.narr) lds_barrier(); // exchange buffer reused by the next array
+    for (int q2 = 0; q2 < G::R1; q2++) st_uni<PIN>(out, static_cast<uint64_t>(G::R2 * q2) * t.lstride, ob * static_cast<uint32_t>(sizeof(float2)), r[q2]);
   }
 }
 
-// =====================================================================================================================
-// z-fused: forward along z, spectral multiply, inverse along z.  Tile (y = blockIdx.y, kx tile = blockIdx.x).
-// =====================================================================================================================
-// Z_SHIFT: plain "transform along a line, multiply bin k by a complex H[k], transform back" on lines with arbitrary
-// strides — the half-cell shift of a staggered velocity (computeVelocityShiftInY / InZ) done on pairs of real
-// x-neighbours packed as one complex value
-enum ZMode { Z_PGRAD = 0, Z_VGRAD = 1, Z_ABSORB = 2, Z_SOURCE = 3, Z_SHIFT = 4 };
+// The forward exchange of an L-point transform of sign DIR, in two halves around the kernel's lds_barrier().
+// Column thread: step A on its registers, then its column of the buffer.  ROWWRITE: the transposed cell assignment.
+template<int L, int DIR, int NLV = nl_yz(L), bool ROWWRITE = false>
+__device__ __forceinline__ void fwd_cols(float2 (&v)[Fac<L>::R1], float2* lds, int c, int j, const float2* twl)
+{
+  using G = Geo<L, NLV>;
+  static_assert(!ROWWRITE || G::R1 == G::R2, "transposed exchange needs a square factorisation");
+  step_a<L, DIR>(v, j, twl);
+#pragma unroll
+  for (int k1 = 0; k1 < G::R1; k1++) lds[ROWWRITE ? j * G::SF + k1 * G::NL + c : k1 * G::SF + j * G::NL + c] = v[k1];
+}
+// Row thread: its row of the buffer, then step B; ends with X[j + R1 * k2].
+template<int L, int DIR, int NLV = nl_yz(L), bool ROWWRITE = false>
+__device__ __forceinline__ void fwd_rows(float2 (&X)[Fac<L>::R2], const float2* lds, int c, int j)
+{
+  using G = Geo<L, NLV>;
+#pragma unroll
+  for (int n2 = 0; n2 < G::R2; n2++) X[n2] = lds[ROWWRITE ? n2 * G::SF + j * G::NL + c : j * G::SF + n2 * G::NL + c];
+  Dft<G::R2, DIR>::run(X);
+}
+// Both halves for a block all of whose threads are column and row threads (R1 == R2 == TPL): the transform of the step-A
+// registers v, X[j + R1 * k2] in w.  ROWWRITE: for a transform that follows an exchange whose read was by rows, so that
+// no barrier is needed in between.  Otherwise the buffer must be free on entry.
+template<int H, int DIR, bool ROWWRITE = false, int NLV = nl_yz(H)>
+__device__ __forceinline__ void line_fft(float2 (&v)[Fac<H>::R1], float2 (&w)[Fac<H>::R2], float2* lds, int c, int j,
+                                         const float2* twl)
+{
+  fwd_cols<H, DIR, NLV, ROWWRITE>(v, lds, c, j, twl);
+  lds_barrier();
+  fwd_rows<H, DIR, NLV, ROWWRITE>(w, lds, c, j);
+}
 
-
-// inverse along the line, started from the step-B register layout (thread (c,k1) holds X[k1 + R1*k2]); result:
-// thread (c,q1) holds x[q1 + R2*q2], q2 < R1 — returned in v.
-// The exchange runs the forward one backwards over the same cells: in the forward transform thread n2 writes the cells
-// (k1, n2) for all k1 ("its column") and thread k1 reads (k1, n2) for all n2 ("its row"); here thread k1 writes its row
-// — cells nobody else has read — and thread q1 reads its column.  A thread therefore only ever overwrites what it read
-// last itself: no barrier is needed between the forward read and this write, nor between this read and the next
-// forward write.
+// Every thread: inverse along the line, started from the row threads' registers (X[j + R1 * k2] in w); the column
+// threads end with x[j + R2 * q2], q2 < R1, in v.  The exchange is the forward one run backwards (see above).
 // COLWRITE (square factorisations only, used by the 2 x 256 split kernels): the transposed cell assignment — thread k1
 // writes its column and thread q1 reads its row — for an exchange that follows one whose read was by columns.
 template<int L, bool COLWRITE = false, int NLV = nl_yz(L)>
@@ -627,14 +652,123 @@ __device__ __forceinline__ void inverse_from_regs(float2 (&w)[Fac<L>::R2], float
   }
 }
 
+// =====================================================================================================================
+// y-pass: in-place complex FFT along y (stride P) for tile (z = blockIdx.y, kx tile = blockIdx.x), array blockIdx.z
+// =====================================================================================================================
+
+// PIN / POUT: packed (per-peer chunk) addressing on the input / output side; the natural layout is the cheap
+// compile-time-strided case  element(k) = base + k * P.  Both go through the launch's RowAddr (ain / aout), so the line
+// loads and stores are this kernel's own; the tile is line_tile's.  The exchange is fwd_cols / fwd_rows spelt out (written
+// with the two steps the compiler allocates a register more or less at most lengths, and an occupancy step with it at
+// some).
+//   per array:  [mul] write columns | next array's lines requested | barrier | read rows -> store | barrier (buffer reused)
+template<int L, int DIR, bool PIN, bool POUT>
+__global__ __launch_bounds__(Geo<L>::THREADS) void k_ypass(PassArgs a)
+{
+  using G = Geo<L>;
+  constexpr int R1 = G::R1, R2 = G::R2;
+  __shared__ float2 lds[G::LDSB];
+  __shared__ float2 twl[G::TWN];
+  load_twiddles<L>(twl, a.tw);
+  // RowAddr addressing (natural or packed) is this kernel's own: zero strides leave t.lstride / t.base / t.basel inert;
+  // only c, j, tc, pos and valid are used
+  const LineTile t     = line_tile<G>(a.nxc, a.P, a.side_off, 0u, 0u, a.z0);
+  if (t.tc.dead) return;
+  const int      c     = t.c, j = t.j;
+  const uint32_t kx    = t.tc.side ? 0u : t.tc.kx; // addressing column (side blocks: the one column of the side array)
+  const uint32_t kxl   = t.tc.col;
+  const uint32_t z     = t.pos;
+  const uint32_t Pe    = t.tc.pitch, soff = t.tc.off; // row pitch / offset of the region (main rows, or the side array)
+  const uint32_t PXe   = t.tc.side ? 1u : a.PX;       // the same on the packed (exchange) side: per-peer chunks of the side array
+  const uint32_t arr0  = blockIdx.z * a.narr; // each block takes a.narr arrays back to back (next one's lines prefetched)
+
+  auto ld = [&](float2 (&v)[R1], const float2* __restrict__ Sin) {
+    if (PIN)
+    {
+#pragma unroll
+      for (int n1 = 0; n1 < R1; n1++) v[n1] = Sin[a.ain.row(z, n1 * R2 + j) * PXe + kxl + soff];
+    }
+    else
+    {
+      uint32_t b = (z * a.ain.zmul + j * a.ain.estride) * Pe + kxl + soff; // estride = 1 (y lines) or ny (z probe)
+      asm volatile("" : "+v"(b));
+      const uint32_t step = R2 * a.ain.estride * Pe;
+#pragma unroll
+      for (int n1 = 0; n1 < R1; n1++)
+        v[n1] = ld_uni(Sin, static_cast<uint64_t>(n1) * step, b * static_cast<uint32_t>(sizeof(float2)));
+    }
+  };
+
+  float2 v[R1];
+  if (ACTW(R2, j)) ld(v, a.in[arr0]);
+  lds_barrier(); // twiddle table visible (the line loads stay in flight across it)
+#pragma unroll 1
+  for (uint32_t ia = 0; ia < a.narr; ia++)
+  {
+    if (ACTW(R2, j))
+    {
+      const float2* __restrict__ m = a.mul[arr0 + ia];
+      if (m != nullptr)
+      {
+#pragma unroll
+        for (int n1 = 0; n1 < R1; n1++) v[n1] = cmulf(v[n1], m[n1 * R2 + j]);
+      }
+      step_a<L, DIR>(v, j, twl);
+#pragma unroll
+      for (int k1 = 0; k1 < R1; k1++) lds[k1 * G::SF + j * G::NL + c] = v[k1];
+      if (ia + 1 < a.narr) ld(v, a.in[arr0 + ia + 1]);
+    }
+    lds_barrier();
+    if (ACTW(R1, j))
+    {
+      float2 w[R2];
+#pragma unroll
+      for (int n2 = 0; n2 < R2; n2++) w[n2] = lds[j * G::SF + n2 * G::NL + c];
+      Dft<R2, DIR>::run(w);
+      if (t.valid)
+      {
+        float2* __restrict__ Sout = a.out[arr0 + ia];
+        if (POUT)
+        {
+#pragma unroll
+          for (int k2 = 0; k2 < R2; k2++) Sout[a.aout.row(z, j + R1 * k2) * PXe + kx + soff] = w[k2];
+        }
+        else
+        {
+          uint32_t b = (z * a.aout.zmul + j * a.aout.estride) * Pe + kx + soff;
+          asm volatile("" : "+v"(b));
+          const uint32_t step = R1 * a.aout.estride * Pe;
+#pragma unroll
+          for (int k2 = 0; k2 < R2; k2++) st_uni(Sout, static_cast<uint64_t>(k2) * step, b * static_cast<uint32_t>(sizeof(float2)), w[k2]);
+        }
+      }
+    }
+    if (ia + 1 < a.narr) lds_barrier(); // exchange buffer reused by the next array
+  }
+}
+
+// =====================================================================================================================
+// z-fused: forward along z, spectral multiply, inverse along z.  Tile (y = blockIdx.y, kx tile = blockIdx.x).
+// =====================================================================================================================
+// Z_SHIFT: plain "transform along a line, multiply bin k by a complex H[k], transform back" on lines with arbitrary
+// strides — the half-cell shift of a staggered velocity (computeVelocityShiftInY / InZ) done on pairs of real
+// x-neighbours packed as one complex value
+enum ZMode { Z_PGRAD = 0, Z_VGRAD = 1, Z_ABSORB = 2, Z_SOURCE = 3, Z_SHIFT = 4 };
+
+
 // One block owns the z-lines of tile (ky = blockIdx.y, kx tile = blockIdx.x) of `narr` arrays (VGRAD: the three velocity
 // spectra, ABSORB: the two pressure terms), processed back to back: the lines of array i+1 are in flight while array i
 // is transformed, and kappa is fetched once for all three velocity components.  PGRAD has one input and three outputs.
+// The body spells the line-tile steps out (see there for why): tile set-up = line_tile, opbase = op_run_base, the first
+// load = load_lines, the exchange = fwd_cols / fwd_rows, the store = store_lines; its own are the operator multiply, the
+// axis handling and the prefetch of the next array.
+//   per array:  write columns | next array's lines requested | barrier | read rows -> multiply |
+//               per output: inverse_from_regs -> store | barrier before the next output's inverse
 template<int L, int MODE> __global__ __launch_bounds__((Geo<L, nl_z(L)>::THREADS), big_line_waves(L)) void k_zfused(ZArgs a)
 {
   using G = Geo<L, nl_z(L)>;
   constexpr int R1 = G::R1, R2 = G::R2;
-  constexpr bool WA = (R2 == G::TPL) || ((G::NL * R2) % 64 == 0 && 64 % G::NL == 0); // step-A participants: whole waves
+  constexpr bool WA = G::WA;
   __shared__ float2 lds[G::LDSB];
   __shared__ float2 twl[G::TWN];
   load_twiddles<L>(twl, a.tw);
@@ -807,26 +941,58 @@ template<int L> __device__ __forceinline__ void load_twiddles_split(float2* twl,
   for (int e = threadIdx.x; e < L / 2; e += G::THREADS) tw2[e] = tw[e];
 }
 
-// H-point transform of the step-A registers v (thread (c, n2 = j) holds x[n1*R2 + j]); thread (c, k1 = j) ends with
-// X[j + R1*k2] in w.  Default cell assignment: the thread writes its column of the exchange buffer and reads its row;
-// ROWWRITE: the transposed one (writes its row, reads its column) — for a transform that follows an exchange whose
-// read was by rows, so that every thread overwrites only what it read itself and no barrier is needed in between
-// (see inverse_from_regs).  Otherwise the buffer must be free on entry.
-template<int H, int DIR, bool ROWWRITE = false>
-__device__ __forceinline__ void line_fft(float2 (&v)[Fac<H>::R1], float2 (&w)[Fac<H>::R2], float2* lds, int c, int j,
-                                         const float2* twl)
+// The steps of the split lines' z-passes (every thread of the block is a column and a row thread of the H-point
+// transforms).  The lower and the upper half of the thread's line: x[n1 * R2 + j] in va, x[H + n1 * R2 + j] in vb ...
+template<int L>
+__device__ __forceinline__ void load_split_halves(float2 (&va)[Fac<L / 2>::R1], float2 (&vb)[Fac<L / 2>::R1],
+                                                  const float2* __restrict__ in, const LineTile& t)
 {
+  constexpr int H = L / 2;
   using G = Geo<H>;
-  static_assert(!ROWWRITE || G::R1 == G::R2, "transposed exchange needs a square factorisation");
-  step_a<H, DIR>(v, j, twl);
+  const uint32_t lb = (t.basel + static_cast<uint32_t>(t.j) * t.lstride) * static_cast<uint32_t>(sizeof(float2));
 #pragma unroll
-  for (int k1 = 0; k1 < G::R1; k1++) lds[ROWWRITE ? j * G::SF + k1 * G::NL + c : k1 * G::SF + j * G::NL + c] = v[k1];
-  lds_barrier();
+  for (int n1 = 0; n1 < G::R1; n1++)
+  {
+    va[n1] = ld_uni(in, static_cast<uint64_t>(n1 * G::R2) * t.lstride, lb);
+    vb[n1] = ld_uni(in, static_cast<uint64_t>(H + n1 * G::R2) * t.lstride, lb);
+  }
+}
+// ... their radix-2 stage on the way in, once tw2 is visible: va <- a, vb <- b, the step-A registers of the two halves
+template<int L>
+__device__ __forceinline__ void split_butterfly(float2 (&va)[Fac<L / 2>::R1], float2 (&vb)[Fac<L / 2>::R1], int j, const float2* tw2)
+{
+  using G = Geo<L / 2>;
 #pragma unroll
-  for (int n2 = 0; n2 < G::R2; n2++) w[n2] = lds[ROWWRITE ? n2 * G::SF + j * G::NL + c : j * G::SF + n2 * G::NL + c];
-  Dft<G::R2, DIR>::run(w);
+  for (int n1 = 0; n1 < G::R1; n1++)
+  {
+    const float2 lo = va[n1], hi = vb[n1];
+    va[n1] = cadd(lo, hi);
+    vb[n1] = apply_tw<kFwd>(csub(lo, hi), tw2[n1 * G::R2 + j]);
+  }
+}
+// ... and the recombination of the two inverse halves ra = a[j + R2 * q2], rb = b[j + R2 * q2] on the way out
+template<int L>
+__device__ __forceinline__ void store_split_halves(float2* __restrict__ out, const LineTile& t, const float2 (&ra)[Fac<L / 2>::R1],
+                                                   const float2 (&rb)[Fac<L / 2>::R1], const float2* tw2)
+{
+  constexpr int H = L / 2;
+  using G = Geo<H>;
+  if (t.valid)
+  {
+    uint32_t ob = t.base + static_cast<uint32_t>(t.j) * t.lstride;
+    asm volatile("" : "+v"(ob)); // (see store_lines)
+#pragma unroll
+    for (int q2 = 0; q2 < G::R1; q2++)
+    { // n = j + R2*q2
+      const float2 w = apply_tw<kInv>(rb[q2], tw2[t.j + G::R2 * q2]);
+      st_uni(out, static_cast<uint64_t>(G::R2 * q2) * t.lstride, ob * static_cast<uint32_t>(sizeof(float2)), cadd(ra[q2], w));
+      st_uni(out, static_cast<uint64_t>(H + G::R2 * q2) * t.lstride, ob * static_cast<uint32_t>(sizeof(float2)), csub(ra[q2], w));
+    }
+  }
 }
 
+// The y-pass of the split lines: forward-only (no recombination), with the optional factor folded into its radix-2
+// stage, and RowAddr addressing on both sides as in k_ypass — so the halves' loads and stores are its own.
 template<int L, int DIR, bool PIN, bool POUT>
 __global__ __launch_bounds__(Geo<L / 2>::THREADS) void k_ypass_split(PassArgs a)
 {
@@ -838,16 +1004,17 @@ __global__ __launch_bounds__(Geo<L / 2>::THREADS) void k_ypass_split(PassArgs a)
   __shared__ float2 twl[G::TWN];
   __shared__ float2 tw2[H];
   load_twiddles_split<L>(twl, tw2, a.tw);
-  const int      c     = threadIdx.x % G::NL;
-  const int      j     = threadIdx.x / G::NL;
-  const TileCoord tc   = tile_coord<G::NL>(a.nxc, a.P, a.side_off, gridDim.y, c);
-  if (tc.dead) return;
-  const uint32_t kx    = tc.side ? 0u : tc.kx;
-  const bool     valid = tc.valid;
-  const uint32_t kxl   = tc.col;
-  const uint32_t z     = tc.pos + a.z0;
-  const uint32_t Pe    = tc.pitch, soff = tc.off;
-  const uint32_t PXe   = tc.side ? 1u : a.PX;
+  // RowAddr addressing (natural or packed) is this kernel's own: zero strides leave t.lstride / t.base / t.basel inert;
+  // only c, j, tc, pos and valid are used
+  const LineTile t     = line_tile<G>(a.nxc, a.P, a.side_off, 0u, 0u, a.z0);
+  if (t.tc.dead) return;
+  const int      c     = t.c, j = t.j;
+  const uint32_t kx    = t.tc.side ? 0u : t.tc.kx;
+  const bool     valid = t.valid;
+  const uint32_t kxl   = t.tc.col;
+  const uint32_t z     = t.pos;
+  const uint32_t Pe    = t.tc.pitch, soff = t.tc.off;
+  const uint32_t PXe   = t.tc.side ? 1u : a.PX;
   const float2* __restrict__ Sin = a.in[blockIdx.z];
   float2* __restrict__ Sout      = a.out[blockIdx.z];
 
@@ -921,21 +1088,12 @@ template<int L, int MODE> __global__ __launch_bounds__(Geo<L / 2>::THREADS) void
   __shared__ float2 twl[G::TWN];
   __shared__ float2 tw2[H];
   load_twiddles_split<L>(twl, tw2, a.tw);
-  const int      c      = threadIdx.x % G::NL;
-  const int      j      = threadIdx.x / G::NL;
-  const TileCoord tc    = tile_coord<G::NL>(a.nxc, a.P, a.side_off, gridDim.y, c);
-  if (tc.dead) return;
-  const uint32_t ky     = tc.pos;
-  const bool     valid  = tc.valid;
-  const uint32_t zstr   = a.ny * tc.pitch;
-  const uint32_t kxl    = tc.kx < a.nxc ? tc.kx : (tc.side ? a.nxc : a.nxc - 1u); // true column (ddx lookups)
-  const uint32_t base   = ky * tc.pitch + (tc.side ? 0u : tc.kx) + tc.off;
-  const uint32_t basel  = ky * tc.pitch + tc.col + tc.off;
-  // operators live in a tile-blocked layout [ky][kx tile][kz][16]: the 16 x nz values of this block's tile are one
-  // contiguous run (k_import_reduced), instead of 64-B pieces a whole plane apart
-  constexpr int  OPV    = op_vec(2 * R2); // run of this thread: bins 2*(j + R1*k2) + h at run index 2*k2 + h
-  const uint32_t opbase = tc.side ? a.op_side_off + (((ky / NLMAX) * (2 * R2 / OPV) * R1 + j) * NLMAX + ky % NLMAX) * OPV
-                                  : (((ky * (a.Pop / NLMAX) + tc.col / NLMAX) * (2 * R2 / OPV) * R1 + j) * NLMAX + tc.col % NLMAX) * OPV;
+  const LineTile t      = line_tile<G>(a.nxc, a.P, a.side_off, a.ny, 1u);
+  if (t.tc.dead) return;
+  const int      c      = t.c, j = t.j;
+  const uint32_t ky     = t.pos;
+  const uint32_t kxl    = t.tc.kx < a.nxc ? t.tc.kx : (t.tc.side ? a.nxc : a.nxc - 1u); // true column (ddx lookups)
+  const uint32_t opbase = op_run_base<2 * R2, R1>(t, a.Pop, a.op_side_off); // run: bins 2*(j + R1*k2) + h at run index 2*k2 + h
   constexpr bool MULTI  = (MODE == Z_VGRAD || MODE == Z_ABSORB);
   const uint32_t arr    = MULTI ? a.arr0 + blockIdx.z : 0;
   // PGRAD: the x- and y-gradients share one z-inverse — ddx(kx), ddy(ky) do not depend on kz, so they are applied after
@@ -945,22 +1103,9 @@ template<int L, int MODE> __global__ __launch_bounds__(Geo<L / 2>::THREADS) void
   float2 Xa[R2], Xb[R2]; // after the forward transform: X[2*(j + R1*k2)], X[2*(j + R1*k2) + 1]
   {
     float2 va[R1], vb[R1];
-    const float2* __restrict__ in = a.in[arr];
-    const uint32_t lb = basel + static_cast<uint32_t>(j) * zstr;
-#pragma unroll
-    for (int n1 = 0; n1 < R1; n1++)
-    {
-      va[n1] = ld_uni(in, static_cast<uint64_t>(n1 * R2) * zstr, lb * static_cast<uint32_t>(sizeof(float2)));
-      vb[n1] = ld_uni(in, static_cast<uint64_t>(H + n1 * R2) * zstr, lb * static_cast<uint32_t>(sizeof(float2)));
-    }
+    load_split_halves<L>(va, vb, a.in[arr], t);
     lds_barrier(); // twiddle tables visible
-#pragma unroll
-    for (int n1 = 0; n1 < R1; n1++)
-    {
-      const float2 lo = va[n1], hi = vb[n1];
-      va[n1] = cadd(lo, hi);
-      vb[n1] = apply_tw<kFwd>(csub(lo, hi), tw2[n1 * R2 + j]);
-    }
+    split_butterfly<L>(va, vb, j, tw2);
     // four exchanges per line and output (two forward, two inverse halves), each writing exactly the cells its thread
     // read in the one before (column / row / column / row ...): the only barriers left are the ones inside them
     line_fft<H, kFwd>(va, Xa, lds, c, j, twl);
@@ -1017,19 +1162,7 @@ template<int L, int MODE> __global__ __launch_bounds__(Geo<L / 2>::THREADS) void
       if (half == 0) inverse_from_regs<H, true>(w, ra, lds, c, j, twl); // after a read by columns: write columns
       else inverse_from_regs<H>(w, rb, lds, c, j, twl);                  // after a read by rows: write rows
     }
-    if (valid)
-    {
-      float2* __restrict__ out = a.out[(MODE == Z_PGRAD) ? 2 * o : arr];
-      uint32_t ob = base + static_cast<uint32_t>(j) * zstr;
-      asm volatile("" : "+v"(ob));
-#pragma unroll
-      for (int q2 = 0; q2 < R1; q2++)
-      { // n = j + R2*q2
-        const float2 t = apply_tw<kInv>(rb[q2], tw2[j + R2 * q2]);
-        st_uni(out, static_cast<uint64_t>(R2 * q2) * zstr, ob * static_cast<uint32_t>(sizeof(float2)), cadd(ra[q2], t));
-        st_uni(out, static_cast<uint64_t>(H + R2 * q2) * zstr, ob * static_cast<uint32_t>(sizeof(float2)), csub(ra[q2], t));
-      }
-    }
+    store_split_halves<L>(a.out[(MODE == Z_PGRAD) ? 2 * o : arr], t, ra, rb, tw2);
   }
 }
 
@@ -1863,6 +1996,30 @@ template<int L, bool TAIL = false> __global__ __launch_bounds__(GeoX<L>::THREADS
     hipLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, __VA_ARGS__);                                              \
     KW_LAUNCH_CHECK();                                                                                                 \
   } while (0)
+
+// f(std::integral_constant<int, LEN>) for the runtime line length len
+template<class F> kw_status with_length(uint32_t len, F&& f)
+{
+#define M(LEN) return f(std::integral_constant<int, LEN>())
+  KW_LEN_SWITCH(len, M)
+#undef M
+}
+// Grid of a z-pass over the pipeline's scratch layout: the tiles of a row plus one tile index for the blocks of the
+// x-Nyquist side array (tile_coord), by the local rows, by `nz` (arrays, where each block takes one).  `nl`: columns per
+// tile of the kernel launched — nl_z(length) for the kernels on Geo<L, nl_z(L)>, NLMAX for the 2 x 256 split kernels.
+inline dim3 z_pass_grid(const kw_ctx* ctx, uint32_t nl, uint32_t nz = 1)
+{
+  const auto& f = ctx->fused;
+  return dim3((f.P + nl - 1u) / nl + (f.side_off != 0 ? 1u : 0u), f.nyl, nz);
+}
+// Launch of z-pass kernel K at the runtime line length len (a kw_status): K names the kernel with LEN for its length,
+// as in  return KW_LAUNCH_ZPASS((k_zfused_pair<LEN>), f.nz_global, z_pass_grid(ctx, nl_z(f.nz_global)), a);
+#define KW_LAUNCH_ZPASS(K, len, grid, ...)                                                                             \
+  with_length(len, [&](auto kw_len) -> kw_status {                                                                     \
+    constexpr int LEN = decltype(kw_len)::value;                                                                       \
+    LAUNCH(K, grid, dim3((Geo<LEN, nl_z(LEN)>::THREADS)), __VA_ARGS__);                                                \
+    return KW_OK;                                                                                                      \
+  })
 
 // the x lines whose x-inverse kernels a code object holds: every length, those below KW_LONG_LINES, those from it on
 enum XLines { X_ALL, X_SHORT, X_LONG };

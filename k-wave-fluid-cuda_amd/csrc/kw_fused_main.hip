@@ -199,7 +199,6 @@ template<int MODE> kw_status launch_zfused(kw_ctx* ctx, int narr, ZArgs a)
   if (f.two_d) a.dd[2] = a.dd[1]; // ... whose derivative vector is ddy
   a.side_off    = f.side_off;
   a.op_side_off = f.side_off; // the imported operators hold the side column's values behind the P * ny * nz of the row tiles
-  const uint32_t side_tile = (f.side_off != 0) ? 1u : 0u;
   a.P       = f.slab ? f.PX : f.P; // slab mode: the z-pass works on the exchanged rows in place
   a.Pop     = f.P;
   a.ny      = f.nyl;
@@ -207,24 +206,19 @@ template<int MODE> kw_status launch_zfused(kw_ctx* ctx, int narr, ZArgs a)
   a.ky0     = f.rank * f.nyl;
   a.narr    = narr;
   if (f.nz_global == 512 && f.split512)
-  {
-    LAUNCH((k_zfused_split<512, MODE>), dim3(f.P / NLMAX + side_tile, f.nyl, narr), dim3(Geo<256>::THREADS), a);
+  { // 2 x 256 lines: one array per block
+    LAUNCH((k_zfused_split<512, MODE>), z_pass_grid(ctx, NLMAX, narr), dim3(Geo<256>::THREADS), a);
     return KW_OK;
   }
   // smallest grids (fewer blocks than two per CU): one array per block instead of the arrays back to back (64^3: z-fused
   // kernels 10.6 -> 8.8 us, step +4 %; at 128^3, 640 blocks, the in-block walk with its prefetch is still the faster form)
-  uint32_t split = 1;
-  if ((MODE == Z_VGRAD || MODE == Z_ABSORB) && narr > 1 &&
-      (z_tiles(f.P, f.nz_global) + side_tile) * f.nyl < 2u * static_cast<uint32_t>(ctx->cu_count))
+  dim3 grid = z_pass_grid(ctx, nl_z(f.nz_global));
+  if ((MODE == Z_VGRAD || MODE == Z_ABSORB) && narr > 1 && grid.x * grid.y < 2u * static_cast<uint32_t>(ctx->cu_count))
   {
-    split  = static_cast<uint32_t>(narr);
+    grid.z = static_cast<uint32_t>(narr);
     a.narr = 1;
   }
-  const dim3 grid(z_tiles(f.P, f.nz_global) + side_tile, f.nyl, split);
-#define M(LEN) LAUNCH((k_zfused<LEN, MODE>), grid, dim3((Geo<LEN, nl_z(LEN)>::THREADS)), a)
-  KW_LEN_SWITCH(f.nz_global, M)
-#undef M
-  return KW_OK;
+  return KW_LAUNCH_ZPASS((k_zfused<LEN, MODE>), f.nz_global, grid, a);
 }
 
 // the full tiles go to the code object that holds this epilogue's kernels for rows of this length, the partial last tile
@@ -1240,6 +1234,25 @@ kw_status kw_fused_absorption_pressure_one(kw_ctx* ctx, float* p, const float* t
   return KW_OK;
 }
 
+// The Z_SHIFT pass of kw_fused_shift_velocity: the real array is read as nx/2 complex columns (no side array); `lines`
+// lines of `len` elements along `axis`, whose elements are lrows rows of nx/2 apart and whose neighbours brows rows.
+// (Z_SHIFT reads neither ZArgs::ny nor ::nz.)
+static kw_status launch_zshift(kw_ctx* ctx, const float* in, float* out, const float* filter, int axis, uint32_t len, uint32_t lines,
+                        uint32_t lrows, uint32_t brows)
+{
+  ZArgs z{};
+  z.in[0]   = reinterpret_cast<const float2*>(in);
+  z.out[0]  = reinterpret_cast<float2*>(out);
+  z.dd[2]   = reinterpret_cast<const float2*>(filter);
+  z.tw      = ctx->fused.tw[axis];
+  z.nxc     = ctx->c.nx / 2;
+  z.P       = ctx->c.nx / 2;
+  z.narr    = 1;
+  z.lstride = lrows * z.P;
+  z.bstride = brows * z.P;
+  return KW_LAUNCH_ZPASS((k_zfused<LEN, Z_SHIFT>), len, dim3(z_tiles(z.nxc, len), lines, 1), z);
+}
+
 // computeVelocityShiftInX/Y/Z + the two 1-D transforms around it (KSpaceFirstOrderSolver.cpp:2714-2735,
 // SolverCudaKernels.cu:2617-2710) in one kernel per axis: out = F_axis^-1{ H .* F_axis{in} }, H = full-length Hermitian
 // filter with the 1/N of the transform pair folded in (see kwave_hip.h)
@@ -1265,23 +1278,7 @@ kw_status kw_fused_shift_velocity(kw_ctx* ctx, int axis, const float* in, float*
                               hipMemcpyDeviceToDevice, ctx->stream));
     KW_TRY(xstart_bytes(ctx, KW_ZSHIFT_SLOT, snd, rcv, chunk * sizeof(float)));
     KW_TRY(xwait_one(ctx, KW_ZSHIFT_SLOT));
-    ZArgs z{};
-    z.in[0]   = reinterpret_cast<const float2*>(rcv);
-    z.out[0]  = reinterpret_cast<float2*>(rcv);
-    z.dd[2]   = reinterpret_cast<const float2*>(filter);
-    z.tw      = f.tw[2];
-    z.nxc     = c.nx / 2;
-    z.P       = c.nx / 2;
-    z.ny      = nyl;
-    z.nz      = f.nz_global;
-    z.narr    = 1;
-    z.lstride = nyl * z.P;
-    z.bstride = z.P;
-    const uint32_t nl = nl_z(f.nz_global);
-    const dim3 grid((z.nxc + nl - 1) / nl, nyl, 1);
-#define M(LEN) LAUNCH((k_zfused<LEN, Z_SHIFT>), grid, dim3((Geo<LEN, nl_z(LEN)>::THREADS)), z)
-    KW_LEN_SWITCH(f.nz_global, M)
-#undef M
+    KW_TRY(launch_zshift(ctx, rcv, rcv, filter, 2, f.nz_global, nyl, nyl, 1));
     KW_TRY(xstart_bytes(ctx, KW_ZSHIFT_SLOT, rcv, snd, chunk * sizeof(float)));
     KW_TRY(xwait_one(ctx, KW_ZSHIFT_SLOT));
     for (uint32_t q = 0; q < P; q++)
@@ -1310,26 +1307,8 @@ kw_status kw_fused_shift_velocity(kw_ctx* ctx, int axis, const float* in, float*
     return KW_OK;
   }
   // y / z: the real array is read as nx/2 complex columns; lines run along the axis with the matching stride
-  ZArgs z{};
-  z.in[0]  = reinterpret_cast<const float2*>(in);
-  z.out[0] = reinterpret_cast<float2*>(out);
-  z.dd[2]  = reinterpret_cast<const float2*>(filter);
-  z.tw     = f.tw[axis];
-  z.nxc    = c.nx / 2;
-  z.P      = c.nx / 2;
-  z.ny     = c.ny;
-  z.nz     = c.nz;
-  z.narr   = 1;
-  const uint32_t len   = (axis == 1) ? c.ny : c.nz;
-  const uint32_t lines = (axis == 1) ? c.nz : c.ny;
-  z.lstride = (axis == 1) ? z.P : c.ny * z.P;
-  z.bstride = (axis == 1) ? c.ny * z.P : z.P;
-  const uint32_t nl = nl_z(len);
-  const dim3 grid((z.nxc + nl - 1) / nl, lines, 1);
-#define M(LEN) LAUNCH((k_zfused<LEN, Z_SHIFT>), grid, dim3((Geo<LEN, nl_z(LEN)>::THREADS)), z)
-  KW_LEN_SWITCH(len, M)
-#undef M
-  return KW_OK;
+  if (axis == 1) return launch_zshift(ctx, in, out, filter, 1, c.ny, c.nz, 1, c.ny);
+  return launch_zshift(ctx, in, out, filter, 2, c.nz, c.ny, c.ny, 1);
 }
 
 // scaleSource body (KSpaceFirstOrderSolver.cpp:2346-2351): scaled <- ifftn(sourceKappa*fftn(scaled))/N, in place

@@ -61,8 +61,8 @@ __device__ __forceinline__ float2 recon_pick(const float2& t0, const float2& t1,
 
 // =====================================================================================================================
 // z-pass of the reconstruction: tile (ky = blockIdx.y, kx tile = blockIdx.x; the side array's blocks as in tile_coord) of
-// scratch array 0, in place.  k_zfused_time's geometry, addressing and exchange; between the forward and the inverse
-// transform, where thread (c, j) holds the bins m = j + R1 k2 of column c:
+// scratch array 0, in place, on the line-tile steps (kw_fused.hip).  Its own: between the forward and the inverse
+// transform, where row thread (c, j) holds the bins m = j + R1 k2 of column c:
 //   1. it writes T[m] = w X[m] back into row j of the exchange buffer, at the cell of bin m
 //      (lds[(m % R1) SF + (m / R1) NL + c]) — the cells it read last itself, so no barrier is needed before the write
 //   2. a barrier
@@ -70,51 +70,32 @@ __device__ __forceinline__ float2 recon_pick(const float2& t0, const float2& t1,
 //      m' <= M are read (the cells of the upper half are written and never looked at: T[m'] is the lower half's)
 //   4. a second barrier, before inverse_from_regs overwrites the buffer
 // No LDS beyond Geo::LDSB, nothing read from memory but the lines.
+//   load | barrier (twiddles) | fwd_cols | barrier | fwd_rows -> 1. | barrier | 3. | barrier | inverse_from_regs -> store
 // =====================================================================================================================
 template<int L> __global__ __launch_bounds__((Geo<L, nl_z(L)>::THREADS)) void k_zfused_recon(ZReconArgs a)
 {
   using G = Geo<L, nl_z(L)>;
   constexpr int R1 = G::R1, R2 = G::R2;
-  constexpr bool WA = (R2 == G::TPL) || ((G::NL * R2) % 64 == 0 && 64 % G::NL == 0); // step-A participants: whole waves
   constexpr uint32_t M = L / 2;
   __shared__ float2 lds[G::LDSB];
   __shared__ float2 twl[G::TWN];
   load_twiddles<L>(twl, a.tw);
-  const int       c     = threadIdx.x % G::NL;
-  const int       j     = threadIdx.x / G::NL;
-  const TileCoord tc    = tile_coord<G::NL>(a.nxc, a.P, a.side_off, gridDim.y, c);
-  if (tc.dead) return;
-  const uint32_t ky     = tc.pos;
-  const bool     valid  = tc.valid;
-  const uint32_t zstr   = a.ny * tc.pitch;
-  const uint32_t base   = ky * tc.pitch + (tc.side ? 0u : tc.kx) + tc.off;
-  const uint32_t basel  = ky * tc.pitch + tc.col + tc.off;
+  const LineTile t      = line_tile<G>(a.nxc, a.P, a.side_off, a.ny, 1u);
+  if (t.tc.dead) return;
+  const int      c      = t.c, j = t.j;
 
   float2 v[R1];
-  if (ACTW(R2, j))
-  {
-    const float2* in = a.s;
-    const uint32_t lb = (basel + static_cast<uint32_t>(j) * zstr) * static_cast<uint32_t>(sizeof(float2));
-#pragma unroll
-    for (int n1 = 0; n1 < R1; n1++) v[n1] = ld_uni<WA>(in, static_cast<uint64_t>(n1 * R2) * zstr, lb);
-  }
+  if (ACTW(R2, j)) load_lines<G>(v, a.s, t);
   lds_barrier(); // twiddle table visible (the loads above stay in flight across it)
 
-  if (ACTW(R2, j))
-  {
-    step_a<L, kFwd>(v, j, twl);
-#pragma unroll
-    for (int k1 = 0; k1 < R1; k1++) lds[k1 * G::SF + j * G::NL + c] = v[k1];
-  }
+  if (ACTW(R2, j)) fwd_cols<L, kFwd, G::NL>(v, lds, c, j, twl);
   lds_barrier();
   float2 X[R2];
   // the true column: the side array holds bin Ex/2 = a.nxc; pad lanes (never stored) take the last main column
-  const double rho2 = recon_rho2(a.dkx, a.dky, a.dk2, a.ex, a.ny, tc.side ? a.nxc : tc.col, ky);
+  const double rho2 = recon_rho2(a.dkx, a.dky, a.dk2, a.ex, a.ny, t.tc.side ? a.nxc : t.tc.col, t.pos);
   if (ACTW(R1, j))
   {
-#pragma unroll
-    for (int n2 = 0; n2 < R2; n2++) X[n2] = lds[j * G::SF + n2 * G::NL + c];
-    Dft<R2, kFwd>::run(X);
+    fwd_rows<L, kFwd, G::NL>(X, lds, c, j);
 #pragma unroll
     for (int k2 = 0; k2 < R2; k2++)
     {
@@ -148,14 +129,7 @@ template<int L> __global__ __launch_bounds__((Geo<L, nl_z(L)>::THREADS)) void k_
 
   float2 r[R1];
   inverse_from_regs<L, false, G::NL>(X, r, lds, c, j, twl);
-  if (ACTW(R2, j) && valid)
-  {
-    float2* out = a.s;
-    uint32_t ob = base + static_cast<uint32_t>(j) * zstr;
-    asm volatile("" : "+v"(ob));
-#pragma unroll
-    for (int q2 = 0; q2 < R1; q2++) st_uni<WA>(out, static_cast<uint64_t>(R2 * q2) * zstr, ob * static_cast<uint32_t>(sizeof(float2)), r[q2]);
-  }
+  store_lines<G>(a.s, t, r);
 }
 
 struct ReconMix
@@ -254,12 +228,7 @@ kw_status zfused_recon(kw_ctx* ctx, float2* s, const kw_plane_recon_op* op)
   a.nz       = c.nz;
   a.side_off = f.side_off;
   a.nearest  = op->interp == 1 ? 1u : 0u;
-  const uint32_t side_tile = (f.side_off != 0) ? 1u : 0u;
-  const dim3 grid(z_tiles(f.P, c.nz) + side_tile, c.ny, 1);
-#define M(LEN) LAUNCH((k_zfused_recon<LEN>), grid, dim3((Geo<LEN, nl_z(LEN)>::THREADS)), a)
-  KW_LEN_SWITCH(c.nz, M)
-#undef M
-  return KW_OK;
+  return KW_LAUNCH_ZPASS((k_zfused_recon<LEN>), c.nz, z_pass_grid(ctx, nl_z(c.nz)), a);
 }
 
 } // namespace kwfused

@@ -34,7 +34,7 @@ def main():
                                                                           os.path.join(CSRC, "kw_angular_time.hip"),
                                                                           os.path.join(CSRC, "kw_plane_recon.hip")]
         texts = list(pool.map(compile_one, [(length, src, tmp, extra) for src in srcs]))
-    pat = re.compile(r"Function Name: (\S+).*?VGPRs: (\d+).*?AGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+).*?"
+    pat = re.compile(r"Function Name: (\S+).*?SGPRs: (\d+).*?VGPRs: (\d+).*?AGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+).*?"
                      r"Occupancy \[waves/SIMD\]: (\d+).*?LDS Size \[bytes/block\]: (\d+)", re.S)
     for txt in texts:
         if "error:" in txt:
@@ -42,7 +42,8 @@ def main():
         for m in pat.finditer(txt):
             dn = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip()
             dn = re.sub(r"\(.*\)$", "", dn.replace("(anonymous namespace)::", "").replace("void ", ""))
-            print(f"{dn:52s} vgpr {m.group(2):>4s} agpr {m.group(3):>3s} scratch {m.group(4):>4s} occ {m.group(5)} lds {m.group(6)}")
+            print(f"{dn:52s} sgpr {m.group(2):>3s} vgpr {m.group(3):>4s} agpr {m.group(4):>3s} scratch {m.group(5):>4s} occ {m.group(6)} "
+                  f"lds {m.group(7)}")
 
 
 if __name__ == "__main__":
