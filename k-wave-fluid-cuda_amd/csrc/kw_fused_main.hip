@@ -300,7 +300,8 @@ kw_status xwait(kw_ctx* ctx, int slot)
 {
   const auto& f = ctx->fused;
   KW_TRY(xwait_one(ctx, slot));
-  if (f.side_off != 0 && f.exchange_start != nullptr) KW_TRY(xwait_one(ctx, slot + KW_COMM_SLOTS)); // callback pair: the side piece
+  // callbacks (a start / wait pair, or a piece callback on the whole-array schedule): the side piece went on a slot of its own
+  if (f.side_off != 0 && (f.exchange_start != nullptr || f.exchange_piece != nullptr)) KW_TRY(xwait_one(ctx, slot + KW_COMM_SLOTS));
   return KW_OK;
 }
 kw_status xwait_one(kw_ctx* ctx, int slot)

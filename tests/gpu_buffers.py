@@ -19,15 +19,17 @@ DT, RHO0, C2, BONA, TAU, ETA = 0.7, 1.3, 2.1, 0.6, 0.8, 0.45
 DT_RHO0_SG = (0.9, 1.1, 0.75)
 
 
-def set_constants(dev, nx, ny, nz, **extra):
-    """kw_set_constants for an nx x ny x nz grid with the scalar media above; `extra` sets further fields (sources)"""
+def set_constants(dev, nx, ny, nz, nz_global=None, **extra):
+    """kw_set_constants for an nx x ny x nz grid with the scalar media above; `extra` sets further fields (sources).
+    nz_global: the context is one Z-slab of nz planes out of nz_global, whose transforms span the global grid"""
     from kwave_amd import capi
+    nzg = nz if nz_global is None else nz_global
     k = capi.Constants()
     k.nx, k.ny, k.nz, k.n_elements = nx, ny, nz, nx * ny * nz
     k.nx_complex, k.ny_complex, k.nz_complex = nx // 2 + 1, ny, nz
     k.n_elements_complex = (nx // 2 + 1) * ny * nz
-    k.fft_divider = 1.0 / (nx * ny * nz)
-    k.fft_divider_x, k.fft_divider_y, k.fft_divider_z = 1.0 / nx, 1.0 / ny, 1.0 / nz
+    k.fft_divider = 1.0 / (nx * ny * nzg)
+    k.fft_divider_x, k.fft_divider_y, k.fft_divider_z = 1.0 / nx, 1.0 / ny, 1.0 / nzg
     k.dt, k.dt_by_2, k.c2, k.rho0, k.dt_rho0 = DT, DT / 2, C2, RHO0, DT * RHO0
     k.dt_rho0_sgx, k.dt_rho0_sgy, k.dt_rho0_sgz = DT_RHO0_SG
     k.b_on_a, k.absorb_tau, k.absorb_eta = BONA, TAU, ETA

@@ -86,7 +86,7 @@ RAGGED_SIDE_GRIDS = list(dict.fromkeys([(RAGGED_NX, RAGGED_POSITIONS, n) for n i
 
 
 def _g(x):
-    return x.ptr if isinstance(x, Guarded) else x
+    return x.ptr if hasattr(x, "ptr") else x
 
 
 # ---- operators ----------------------------------------------------------------------------------------------------------
@@ -192,35 +192,14 @@ class Checker:
 class Grid:
     def __init__(self, syn, dims, plane_kernels=1, seed=0):
         import kwave_amd  # noqa: F401
-        from kwave_amd import capi
         self.nx, self.ny, self.nz = nx, ny, nz = dims
         self.shape = (nz, ny, nx)
         self.two_d = nz == 1
         self.rng = np.random.default_rng(seed + 7919 * nx + 31 * ny + nz)
-        self.dev = d = capi.Device()
-        set_constants(d, nx, ny, nz)
-        t = capi.default_tuning()
-        t.plane_kernels = plane_kernels
-        d.call("set_tuning", C.addressof(t))
-        ok = C.c_int()
-        d.call("fused_supported", C.byref(ok))
-        assert ok.value == 1, dims
-        d.call("fused_create")
-        n = C.c_size_t()
-        # a plane of the pipeline's layout: rows of Nx/2 bins and the x-Nyquist column behind them (the side array), or
-        # rows of Nx/2 + 1 bins padded to whole 16-column tiles
-        d.call("fused_angular_elems", C.byref(n))
-        assert n.value in ((nx // 2 + 1) * ny, (nx // 2 + 1 + 15) // 16 * 16 * ny), (dims, n.value)
-        self.side = n.value == (nx // 2 + 1) * ny and (nx // 2 + 1) % 16 != 0
-        d.call("fused_reduced_elems", C.byref(n))
+        n = self.open(plane_kernels)
         self.ops = make_operators(syn, self.rng, nx, ny, nz)
-        self.padded = {}
-        for name in ("kappa", "source_kappa", "nabla1", "nabla2"):
-            src = Guarded(d, self.ops[name])
-            dst = Guarded(d, np.full(n.value, np.nan, dtype=np.float32))
-            d.call("fused_import_reduced", dst.ptr, src.ptr)
-            self.padded[name] = dst
-        self.dd = {k: Guarded(d, v) for k, v in self.ops.items() if k.startswith("dd")}
+        self.padded = {name: self.import_reduced(self.ops[name], n) for name in ("kappa", "source_kappa", "nabla1", "nabla2")}
+        self.dd = {k: self.vector(v) for k, v in self.ops.items() if k.startswith("dd")}
         b = lambda v, a: v.reshape([-1 if i == 2 - a else 1 for i in range(3)])  # noqa: E731  (x, y, z) -> [nz][ny][nx]
         # fp64 views of the float32 operators, broadcast over [nz][ny][nx(/2+1)]
         self.k64 = {k: self.ops[k].astype(np.float64) for k in ("kappa", "source_kappa", "nabla1", "nabla2")}
@@ -228,6 +207,40 @@ class Grid:
         self.dd_neg = [b(knp._c(self.ops[k]), a) for a, k in enumerate(("ddx_k_shift_neg_r", "ddy_k_shift_neg", "ddz_k_shift_neg"))]
         self.bcast = b
         self.readonly = []
+
+    # the device side of the set-up, which a slab grid (test_gpu_slab_stages.SlabGrid) spreads over its ranks
+    def open(self, plane_kernels):
+        """creates self.dev with the pipeline ready, sets self.side; returns the floats of one imported reduced array"""
+        from kwave_amd import capi
+        nx, ny, nz = self.nx, self.ny, self.nz
+        self.dev = d = capi.Device()
+        set_constants(d, nx, ny, nz)
+        t = capi.default_tuning()
+        t.plane_kernels = plane_kernels
+        d.call("set_tuning", C.addressof(t))
+        ok = C.c_int()
+        d.call("fused_supported", C.byref(ok))
+        assert ok.value == 1, (nx, ny, nz)
+        d.call("fused_create")
+        n = C.c_size_t()
+        # a plane of the pipeline's layout: rows of Nx/2 bins and the x-Nyquist column behind them (the side array), or
+        # rows of Nx/2 + 1 bins padded to whole 16-column tiles
+        d.call("fused_angular_elems", C.byref(n))
+        assert n.value in ((nx // 2 + 1) * ny, (nx // 2 + 1 + 15) // 16 * 16 * ny), ((nx, ny, nz), n.value)
+        self.side = n.value == (nx // 2 + 1) * ny and (nx // 2 + 1) % 16 != 0
+        d.call("fused_reduced_elems", C.byref(n))
+        return n.value
+
+    def import_reduced(self, host, n):
+        """a reduced operator [nz][ny][nx/2+1] in the pipeline's layout (n floats)"""
+        src = Guarded(self.dev, host)
+        dst = Guarded(self.dev, np.full(n, np.nan, dtype=np.float32))
+        self.dev.call("fused_import_reduced", dst.ptr, src.ptr)
+        return dst
+
+    def vector(self, host):
+        """a derivative vector"""
+        return Guarded(self.dev, host)
 
     # inputs
     def noise(self, scale=1.0):
