@@ -884,7 +884,8 @@ KW_API kw_status kw_angular_time_reduce(kw_ctx* ctx, const float* vol, uint32_t 
  * kw_fused_plane_recon: vol_out [nz][ny][nx] <- 2 irfftn(G) of vol_even [nz][ny][nx]: x-forward and y-forward of the one array,
  *   ONE launch k_zfused_recon (lines forward along t; T written back into the exchange buffer; a barrier; every bin gathers
  *   T[i0], T[i0 + 1] of its own line from LDS; inverse along t — no operator array, no index table in memory), the y-inverse
- *   and the storing x-inverse.  vol_out may be vol_even.  Single GPU, nz > 1: KW_ERR_INVALID in slab mode or for Nz == 1.
+ *   and the storing x-inverse.  vol_out may be vol_even.  Single GPU, nz > 1: KW_ERR_INVALID in slab mode or for Nz == 1
+ *   (2-D records: kw_fused_line_recon below).
  *   The stage does NOT check that vol_even is even in t: for a volume that is not, S[m] != S[Lt - m], the spectrum handed to
  *   the real inverse is not Hermitian and the result is not the inverse transform of G.
  * kw_plane_recon_mix: the twin: out_spec <- G on the natural [nz][ny][nx/2 + 1] half-spectrum of kw_fft_r2c_3d, out of place
@@ -905,6 +906,50 @@ KW_API kw_status kw_plane_recon_embed(kw_ctx* ctx, float* vol, const float* src,
                                       uint32_t nx, uint32_t ny, uint32_t nt);
 KW_API kw_status kw_plane_recon_crop(kw_ctx* ctx, float* out, const float* vol, uint32_t ex, uint32_t ey, uint32_t lt,
                                      uint32_t nx, uint32_t ny, uint32_t planes, int32_t positivity);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Batched k-space line reconstruction (what k-Wave's kspaceLineRecon computes, frame by frame): F records p[t][y] of a
+ * linear array to the F images p0[x][y] that produced them, x_j = j c0 dt (csrc/kw_line_recon.hip, host/LineRecon.cpp,
+ * DESIGN.md "k-space line reconstruction").  One frame is the plane reconstruction above with ONE lateral axis: the record
+ * embedded mirrored in time in a zero plane v [Lt][Ey], S = fft2(v), and
+ *     dk = 2 pi / (Lt dt c0);   ky = 2 pi / (Ey dy) * min(i, Ey - i);   rho2 = (ky * ky) / (dk * dk)          (float64)
+ * with w, f, the interpolants, "G = 0 where f > M" and the float64 / float32 split exactly as documented there
+ * (recon_w, recon_f, recon_scale, recon_pick: csrc/kw_recon_device.h, one copy for both operators);
+ *     out = crop( positivity( 2 irfft2(G) ) ),  scale = 2 / (Lt Ey).   Frames are independent.
+ *
+ * Frames mode of the fused context.  kw_fused_set_frames(ctx, 1), before kw_fused_create (KW_ERR_STATE after it,
+ *   KW_ERR_INVALID on a slab context): the constants (nx, ny, nz) = (Ey, Lt, F) then describe F independent planes — the
+ *   sensor axis where the pipeline has x (contiguous, real-to-complex), t on y, the frame on z with NO transform along z and
+ *   any F >= 1.  kw_fused_supported asks for fast-path nx and ny, the 2^32 index limits and, for the ten x lengths without
+ *   masked x kernels, (ny nz) % (2 nl_x(nx)) == 0; also for nz <= 65535 (the frame is a block index) and P ny nz < 2^29
+ *   (P = nx/2 + 1 rounded up to 16): the pass along t addresses a frame's lines by 32-bit byte offsets, so one scratch array
+ *   ends below 4 GiB.  A frames context allocates ONE scratch array, the one its stage uses
+ *   (kw_fused_create_with_scratch: s[0] alone is looked at).  The x-Nyquist side array is kept under the usual rule and is then
+ *   [F][Lt].  Every other kw_fused_* stage, import and size query returns KW_ERR_INVALID on such a context ("frames mode").
+ * kw_fused_line_recon: vol_out [F][Lt][Ey] <- 2 irfft2(G) of every plane of vol_even [F][Lt][Ey], three launches: the
+ *   x-forward over all Lt F rows (a masked last tile where the row count asks for one), ONE launch k_yfused_line_recon
+ *   (lines along t, tile position = the frame; k_zfused_recon's weight, barrier order and gather from LDS; rho2 from the
+ *   column alone — no operator array, no index table) and the storing x-inverse.  No y-pass.  vol_out may be vol_even.
+ *   op: kw_plane_recon_op with dx = the sensor pitch; dy is ignored.  KW_ERR_INVALID outside frames mode.  As for the plane
+ *   stage, the evenness of vol_even in t is not checked.
+ * kw_fft_create_plans_frames / kw_fft_r2c_frames / kw_fft_c2r_frames: nz batched 2-D real transforms of (nx, ny), natural
+ *   layout [nz][ny][nx/2 + 1], any sizes; the 3-D plans are independent of them.
+ * kw_line_recon_mix: the twin: out_spec <- G on those half-spectra, out of place (it gathers); any nx, ny, nz.  A context
+ *   without bins: KW_OK, nothing launched.
+ * kw_line_recon_embed: vol [frames][lt][ey] <- src [frames][nt][ny] mirrored along t, zero elsewhere; lt >= 2 nt - 1.
+ * kw_line_recon_crop: out [frames][depth][ny] <- the corner of every plane of vol, depth <= lt; positivity as above.
+ *   Both exact; 16-byte accesses when ey and ny are multiples of 4 and the pointers are 16-byte aligned; zero points: KW_OK.
+ * ---------------------------------------------------------------------------------------------------------------- */
+KW_API kw_status kw_fused_set_frames(kw_ctx* ctx, int on);
+KW_API kw_status kw_fused_line_recon(kw_ctx* ctx, const float* vol_even, const kw_plane_recon_op* op, float* vol_out);
+KW_API kw_status kw_fft_create_plans_frames(kw_ctx* ctx);
+KW_API kw_status kw_fft_r2c_frames(kw_ctx* ctx, const float* in, float* out);
+KW_API kw_status kw_fft_c2r_frames(kw_ctx* ctx, float* in, float* out);
+KW_API kw_status kw_line_recon_mix(kw_ctx* ctx, float* out_spec, const float* spec, const kw_plane_recon_op* op, float scale);
+KW_API kw_status kw_line_recon_embed(kw_ctx* ctx, float* vol, const float* src, uint32_t ey, uint32_t lt, uint32_t frames,
+                                     uint32_t ny, uint32_t nt);
+KW_API kw_status kw_line_recon_crop(kw_ctx* ctx, float* out, const float* vol, uint32_t ey, uint32_t lt, uint32_t frames,
+                                    uint32_t ny, uint32_t depth, int32_t positivity);
 
 #ifdef __cplusplus
 }

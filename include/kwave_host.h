@@ -387,9 +387,9 @@ KWH_API void*    kwh_angular_time_context(kwh_angular_time* s);
  * Refused, naming the parameter: Nx Ny Nt (0), dx dy dt c0 (not positive), planes (above Nt), interp (neither), Ex Ey
  * (missing, below N), Lt (below 2 Nt - 1), E (2^32 points or more).
  * Of kwh_options the calls read device_idx and fused_kernels.  kwh_plane_recon_plan validates and completes (Ex, Ey, Lt)
- * without a device.  Not built: 2-D (kspaceLineRecon), heterogeneous media, Z-slabs, HDF5 files and the command line,
- * graphs, a half-length (DCT) time transform that would use the evenness, the x- and y-inverse restricted to the crop,
- * other interpolants.
+ * without a device.  2-D records: kwh_line_recon_* below.  Not built: heterogeneous media, Z-slabs, HDF5 files and the
+ * command line, graphs, a half-length (DCT) time transform that would use the evenness, the x- and y-inverse restricted
+ * to the crop, other interpolants.
  * ---------------------------------------------------------------------------------------------------------------- */
 typedef struct kwh_plane_recon kwh_plane_recon;
 typedef struct kwh_plane_recon_config
@@ -416,6 +416,57 @@ KWH_API int      kwh_plane_recon_get(kwh_plane_recon* s, const char* name, float
 KWH_API int      kwh_plane_recon_get_scalar(kwh_plane_recon* s, const char* name, double* out);
 /* the underlying kw_ctx* (include/kwave_hip.h) */
 KWH_API void*    kwh_plane_recon_context(kwh_plane_recon* s);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Batched k-space line reconstruction (what k-Wave's kspaceLineRecon computes, frame by frame): `frames` records p[t][y] of
+ * a linear array, sampled at t_n = n dt, to the images p0[x][y], x_j = j c0 dt, j < depth <= Nt, of a homogeneous medium —
+ * the plane reconstruction above with one lateral axis (kwave_hip.h "Batched k-space line reconstruction").
+ * Public names follow k-Wave: y is the sensor axis, t is time, x is depth.  The result is frames x depth x Ny.
+ *   ey (0 = Ny): the expanded sensor axis, not below Ny.
+ *   lt (0 = default): as for the plane reconstruction — the smallest fast-path length at or above 2 Nt - 1, or 2 Nt - 1
+ *   itself when there is none (above 1024) or with fused_kernels off.  A given lt is not below 2 Nt - 1.
+ *   depth (0 = Nt).  interp: 0 linear, 1 nearest.  positivity != 0: the result is clamped at 0.
+ *   chunk_frames (0 = default): the frames that one context holds; default all frames, capped so that one chunk stays
+ *   inside the index limits of the pass along t: P Lt chunk_frames < 2^29 bins (P = Ey/2 + 1 rounded up to 16; 4 GiB of
+ *   spectrum) and at most 65535 frames.  A run goes chunk by chunk through that one context; a shorter last chunk runs as a full
+ *   one whose surplus frames are zero records and are not copied out.  Frames are independent: on the fused path a frame's
+ *   result does not depend on the chunking.
+ *   The fused stage runs when the frames context of one chunk is supported (Ey and Lt fast-path lengths; for the ten
+ *   lengths of Ey without masked x kernels, Lt chunk_frames a multiple of 16), the rocFFT twin otherwise.
+ * Refused, naming the parameter: Ny Nt frames (0), dy dt c0 (not positive), depth (above Nt), interp (neither), Ey (below
+ * Ny), Lt (below 2 Nt - 1), chunk_frames (above frames, above 65535, or too many bins), E (one frame of 2^29 bins or more).
+ * Of kwh_options the calls read device_idx and fused_kernels.  kwh_line_recon_plan validates and completes
+ * (Ey, Lt, depth, chunk_frames) without a device.  Not built: heterogeneous media, Z-slabs, HDF5 files and the command
+ * line, graphs, the 2-D forms of the three projectors, frames spread over several GPUs.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct kwh_line_recon kwh_line_recon;
+typedef struct kwh_line_recon_config
+{
+  uint64_t ny, nt;          /* one frame */
+  uint64_t frames;          /* F >= 1 */
+  double   dy, dt;          /* [m], [s] */
+  double   c0;              /* [m/s] */
+  uint64_t ey;              /* expanded sensor axis; 0 = Ny */
+  uint64_t lt;              /* length of the mirrored record; 0 = default */
+  uint64_t depth;           /* 1 ... Nt; 0 = Nt */
+  uint64_t chunk_frames;    /* 1 ... frames; 0 = default */
+  int32_t  interp;          /* 0 = linear, 1 = nearest */
+  int32_t  positivity;
+} kwh_line_recon_config;
+/* out_sizes: (Ey, Lt, depth, chunk_frames) */
+KWH_API int      kwh_line_recon_plan(const kwh_line_recon_config* config, const kwh_options* options,
+                                     uint64_t out_sizes[4], int32_t* out_fast_path);
+KWH_API int      kwh_line_recon_create(const kwh_line_recon_config* config, const kwh_options* options,
+                                       kwh_line_recon** out);
+KWH_API int      kwh_line_recon_destroy(kwh_line_recon* s);
+/* p: Ny * Nt * frames floats on the host ([frames][Nt][Ny]); the result [frames][depth][Ny] stays on the device */
+KWH_API int      kwh_line_recon_run(kwh_line_recon* s, const float* p);
+/* "p0" of the last run; n = Ny * depth * frames (checked) */
+KWH_API int      kwh_line_recon_get(kwh_line_recon* s, const char* name, float* dst, uint64_t n);
+/* "fused_pipeline", "Ey", "Lt", "depth", "frames", "chunk_frames", "dx", "runs" */
+KWH_API int      kwh_line_recon_get_scalar(kwh_line_recon* s, const char* name, double* out);
+/* the underlying kw_ctx* (include/kwave_hip.h) */
+KWH_API void*    kwh_line_recon_context(kwh_line_recon* s);
 
 #ifdef __cplusplus
 }

@@ -212,6 +212,14 @@ _SIG: Dict[str, list] = {
     "kw_plane_recon_mix": [_P, _P, _P, _P, C.c_float],
     "kw_plane_recon_embed": [_P, _P, _P] + [C.c_uint32] * 6,
     "kw_plane_recon_crop": [_P, _P, _P] + [C.c_uint32] * 6 + [C.c_int32],
+    "kw_fused_set_frames": [_P, C.c_int],
+    "kw_fused_line_recon": [_P, _P, _P, _P],
+    "kw_fft_create_plans_frames": [_P],
+    "kw_fft_r2c_frames": [_P, _P, _P],
+    "kw_fft_c2r_frames": [_P, _P, _P],
+    "kw_line_recon_mix": [_P, _P, _P, _P, C.c_float],
+    "kw_line_recon_embed": [_P, _P, _P] + [C.c_uint32] * 5,
+    "kw_line_recon_crop": [_P, _P, _P] + [C.c_uint32] * 5 + [C.c_int32],
 }
 
 class PlaneReconOp(C.Structure):

@@ -56,7 +56,7 @@ static kw_status ensure_setup(kw_ctx* ctx)
 static kw_status bind_work(kw_ctx* ctx)
 {
   kw_fft_plan* plans[] = { &ctx->r2c_3d, &ctx->c2r_3d, &ctx->r2c_1d[0], &ctx->r2c_1d[1], &ctx->r2c_1d[2],
-                           &ctx->c2r_1d[0], &ctx->c2r_1d[1], &ctx->c2r_1d[2] };
+                           &ctx->c2r_1d[0], &ctx->c2r_1d[1], &ctx->c2r_1d[2], &ctx->r2c_frames, &ctx->c2r_frames };
   size_t need = 0;
   for (kw_fft_plan* p : plans)
     if (p->plan && p->work > need) need = p->work;
@@ -133,6 +133,22 @@ kw_status kw_fft_create_plans_3d(kw_ctx* ctx)
   st = make_plan(ctx->r2c_3d, rocfft_transform_type_real_forward, dims, lengths, 1, nullptr, 0, nullptr, 0);
   if (st != KW_OK) return st;
   st = make_plan(ctx->c2r_3d, rocfft_transform_type_real_inverse, dims, lengths, 1, nullptr, 0, nullptr, 0);
+  if (st != KW_OK) return st;
+  return bind_work(ctx);
+}
+
+// nz independent 2-D real transforms of (nx, ny): one batched plan pair, planes nx * ny reals / (nx/2 + 1) * ny bins apart
+kw_status kw_fft_create_plans_frames(kw_ctx* ctx)
+{
+  KW_CHECK_CONSTS(ctx);
+  KW_HIP(hipSetDevice(ctx->device));
+  kw_status st = ensure_setup(ctx);
+  if (st != KW_OK) return st;
+  size_t lengths[2] = { ctx->c.nx, ctx->c.ny };
+  const size_t dims = lengths[1] == 1 ? 1 : 2;
+  st = make_plan(ctx->r2c_frames, rocfft_transform_type_real_forward, dims, lengths, ctx->c.nz, nullptr, 0, nullptr, 0);
+  if (st != KW_OK) return st;
+  st = make_plan(ctx->c2r_frames, rocfft_transform_type_real_inverse, dims, lengths, ctx->c.nz, nullptr, 0, nullptr, 0);
   if (st != KW_OK) return st;
   return bind_work(ctx);
 }
@@ -226,6 +242,8 @@ kw_status kw_fft_destroy_plans(kw_ctx* ctx)
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   plan_free(ctx->r2c_3d);
   plan_free(ctx->c2r_3d);
+  plan_free(ctx->r2c_frames);
+  plan_free(ctx->c2r_frames);
   for (int a = 0; a < 3; a++)
   {
     plan_free(ctx->r2c_1d[a]);
@@ -259,6 +277,30 @@ kw_status kw_fft_c2r_3d(kw_ctx* ctx, float* in, float* out)
   void* ib[1] = { (void*)in };
   void* ob[1] = { (void*)out };
   KW_FFT(rocfft_execute(ctx->c2r_3d.plan, ib, ob, ctx->c2r_3d.info));
+  return KW_OK;
+}
+
+kw_status kw_fft_r2c_frames(kw_ctx* ctx, const float* in, float* out)
+{
+  KW_CHECK_CONSTS(ctx);
+  KW_PROF(ctx, "fft_r2c_frames");
+  KW_REQUIRE(in != nullptr && out != nullptr);
+  if (!ctx->r2c_frames.plan) { kw_set_error("kw_fft_r2c_frames: plans not created (kw_fft_create_plans_frames)"); return KW_ERR_STATE; }
+  void* ib[1] = { (void*)in };
+  void* ob[1] = { (void*)out };
+  KW_FFT(rocfft_execute(ctx->r2c_frames.plan, ib, ob, ctx->r2c_frames.info));
+  return KW_OK;
+}
+
+kw_status kw_fft_c2r_frames(kw_ctx* ctx, float* in, float* out)
+{
+  KW_CHECK_CONSTS(ctx);
+  KW_PROF(ctx, "fft_c2r_frames");
+  KW_REQUIRE(in != nullptr && out != nullptr);
+  if (!ctx->c2r_frames.plan) { kw_set_error("kw_fft_c2r_frames: plans not created (kw_fft_create_plans_frames)"); return KW_ERR_STATE; }
+  void* ib[1] = { (void*)in };
+  void* ob[1] = { (void*)out };
+  KW_FFT(rocfft_execute(ctx->c2r_frames.plan, ib, ob, ctx->c2r_frames.info));
   return KW_OK;
 }
 

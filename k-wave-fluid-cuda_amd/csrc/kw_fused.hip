@@ -218,6 +218,9 @@ kw_status zfused_time(kw_ctx* ctx, const float2* in, float2* out, const kw_angul
 // the z-pass of kw_fused_plane_recon: lines of `s` forward along t, the weight, the gather from w to kz along each line,
 // the inverse, in place (kw_plane_recon.hip)
 kw_status zfused_recon(kw_ctx* ctx, float2* s, const kw_plane_recon_op* op);
+// the pass along t of kw_fused_line_recon (frames context): lines of `s` along y, one frame per tile position, the plane
+// reconstruction's weight and gather with rho2 of the column alone, in place (kw_line_recon.hip; op->dx = the sensor pitch)
+kw_status yfused_line_recon(kw_ctx* ctx, float2* s, const kw_plane_recon_op* op);
 // the tuning probes of kw_fused_probe that launch no pipeline kernel (kw_fused_probe.hip)
 kw_status probe_patterns(kw_ctx* ctx, int which, const float* op);
 
@@ -498,8 +501,8 @@ template<int L, int DIR> __device__ __forceinline__ void step_a(float2 (&v)[Fac<
 // four-step transform through the block's buffer lds[G::LDSB].  A kernel's body keeps what is its own — which arrays,
 // what happens to a bin between the transforms — and the order of loads, barriers and stores.
 // On the steps: k_zfused_split, k_zfused_pair_split (kw_cw.hip), k_zfused_time (kw_angular_time.hip), k_zfused_recon
-// (kw_plane_recon.hip); k_ypass and k_ypass_split take the tile and keep their RowAddr loads and stores.  k_zfused,
-// k_zfused_pair (kw_cw.hip) and k_yinv_angular (kw_angular.hip) spell the same steps out in their bodies: assembled from
+// (kw_plane_recon.hip), k_yfused_line_recon (kw_line_recon.hip); k_ypass and k_ypass_split take the tile and keep their
+// RowAddr loads and stores.  k_zfused, k_zfused_pair (kw_cw.hip) and k_yinv_angular (kw_angular.hip) spell the same steps out in their bodies: assembled from
 // the functions below the compiler allocates their guarded (non-whole-wave) and spilling instantiations differently — an
 // occupancy step lost at some lengths, scratch bytes gained at others — so they stay as they were written.  A change to
 // a step below is a change to those three bodies as well.
@@ -565,6 +568,9 @@ __device__ __forceinline__ uint32_t op_run_base(const LineTile& t, uint32_t Pop,
 }
 
 // Column thread: its R1 line elements x[n1 * R2 + j].  PIN as in ld_uni: G::WA wherever the guard can split a wave.
+// The lane part of the address is a 32-bit BYTE offset that holds the whole line position (t.basel): the array must end
+// below 2^29 elements wherever the line position is not bounded by a line length — a 3-D grid's is (every axis is at most
+// 1024 long), a frames context's is not, hence the limit in kw_fused_supported.  store_lines: the same.
 template<class G, bool PIN = G::WA>
 __device__ __forceinline__ void load_lines(float2 (&v)[G::R1], const float2* __restrict__ in, const LineTile& t)
 {

@@ -64,6 +64,8 @@ __global__ void k_import_reduced_side(float* __restrict__ dst, const float* __re
   }
 }
 
+#define KW_FRAMES_MAX 65535u /* frames of a frames context: the frame is blockIdx.y of the pass along t */
+
 bool supported_len(uint32_t n)
 {
 #define X(LEN) if (n == LEN) return true;
@@ -76,6 +78,11 @@ bool supported_len(uint32_t n)
   do {                                                                                                                 \
     KW_CHECK_CONSTS(ctx);                                                                                              \
     if (!(ctx)->fused.ready) { kw_set_error("%s: kw_fused_create has not been called", __func__); return KW_ERR_STATE; } \
+    if ((ctx)->fused.frames)                                                                                           \
+    {                                                                                                                  \
+      kw_set_error("%s: not on a context in frames mode (kw_fused_set_frames): kw_fused_line_recon is its one stage", __func__); \
+      return KW_ERR_INVALID;                                                                                           \
+    }                                                                                                                  \
   } while (0)
 
 #define KW_TRY(call) KW_TRY_STATUS(call)
@@ -692,6 +699,7 @@ kw_status alloc_scratch(kw_ctx* ctx, void* const s[3], void* const t[3])
   f.owns_scratch     = (s == nullptr);
   for (int i = 0; i < 3; i++)
   {
+    if (f.frames && i > 0) break; // the one stage of a frames context works on s[0] alone
     if (f.owns_scratch)
     {
       KW_HIP(hipMalloc(reinterpret_cast<void**>(&f.s[i]), elems * sizeof(float2)));
@@ -731,11 +739,12 @@ kw_status create_impl(kw_ctx* ctx, void* const s[3], void* const t[3])
   auto& f = ctx->fused;
   f.slab = slab.slab; f.nranks = slab.nranks; f.rank = slab.rank; f.exchange = slab.exchange; f.exchange_user = slab.exchange_user;
   f.exchange_start = slab.exchange_start; f.exchange_wait = slab.exchange_wait; f.exchange_piece = slab.exchange_piece;
+  f.frames = slab.frames;
   KW_HIP(hipSetDevice(ctx->device));
   const kw_constants& c = ctx->c;
   f.nz_global = (f.slab) ? slab.nz_global : c.nz;
   f.nyl       = c.ny / f.nranks;
-  f.two_d     = (!f.slab && c.nz == 1);
+  f.two_d     = (!f.slab && !f.frames && c.nz == 1); // (frames mode: x-pass, the pass along y by frames, x-pass, for any Nz)
   if (f.two_d)
   { // 2-D: the z-pass kernels run along y — one "row" per plane, lines of Ny elements with stride P
     f.nz_global = c.ny;
@@ -779,7 +788,7 @@ kw_status create_impl(kw_ctx* ctx, void* const s[3], void* const t[3])
   }
   KW_TRY(alloc_scratch(ctx, s, t));
   const uint32_t lens[3] = { c.nx, c.ny, f.nz_global };
-  for (int i = 0; i < 3; i++)
+  for (int i = 0; i < (f.frames ? 2 : 3); i++) // (frames mode: no transform along z)
   {
     std::vector<float2> tw(lens[i]);
     for (uint32_t m = 0; m < lens[i]; m++)
@@ -793,7 +802,7 @@ kw_status create_impl(kw_ctx* ctx, void* const s[3], void* const t[3])
   }
   f.split512 = (ctx->tuning.split512 != 0);
   // whole-plane x kernels (k_xinv PLANE): square planes of 32 / 64, one GPU, 3-D
-  f.plane = (ctx->tuning.plane_kernels != 0) && !f.slab && !f.two_d && c.nx == c.ny && plane_len(static_cast<int>(c.nx)) &&
+  f.plane = (ctx->tuning.plane_kernels != 0) && !f.slab && !f.two_d && !f.frames && c.nx == c.ny && plane_len(static_cast<int>(c.nx)) &&
             supported_len(c.nx);
   if (f.plane)
   {
@@ -814,6 +823,7 @@ kw_status kw_fused_set_slab(kw_ctx* ctx, uint32_t nranks, uint32_t rank, uint32_
   KW_CHECK_CTX(ctx);
   KW_REQUIRE(nranks >= 1 && rank < nranks);
   if (ctx->fused.ready) { kw_set_error("kw_fused_set_slab: must be called before kw_fused_create"); return KW_ERR_STATE; }
+  if (ctx->fused.frames) { kw_set_error("kw_fused_set_slab: the context is in frames mode (kw_fused_set_frames)"); return KW_ERR_INVALID; }
   uint32_t comm_ranks = 0, comm_rank = 0;
   KW_TRY(kw_comm_info(ctx, &comm_ranks, &comm_rank, nullptr));
   if (fn == nullptr && nranks > 1 && comm_ranks == 0)
@@ -856,6 +866,16 @@ kw_status kw_fused_set_slab_pieces(kw_ctx* ctx, kw_exchange_piece_fn start, kw_e
   return KW_OK;
 }
 
+// frames mode: the z axis of the constants is a batch of independent planes [ny][nx] (kw_fused_line_recon)
+kw_status kw_fused_set_frames(kw_ctx* ctx, int on)
+{
+  KW_CHECK_CTX(ctx);
+  if (ctx->fused.ready) { kw_set_error("kw_fused_set_frames: must be called before kw_fused_create"); return KW_ERR_STATE; }
+  if (on && ctx->fused.slab) { kw_set_error("kw_fused_set_frames: the context is in slab mode (kw_fused_set_slab)"); return KW_ERR_INVALID; }
+  ctx->fused.frames = (on != 0);
+  return KW_OK;
+}
+
 kw_status kw_fused_supported(kw_ctx* ctx, int* out)
 {
   KW_CHECK_CONSTS(ctx);
@@ -866,10 +886,14 @@ kw_status kw_fused_supported(kw_ctx* ctx, int* out)
   // (the x kernels work on tiles of 2 * NL rows; a row count Ny * Nz that is no whole number of tiles ends in one masked tile)
   bool ok = supported_len(c.nx) && supported_len(c.ny) && supported_len(nzg);
   if (!f.slab && c.nz == 1) ok = supported_len(c.nx) && supported_len(c.ny); // 2-D: x-pass, fused y-pass, x-pass
+  if (f.frames) ok = supported_len(c.nx) && supported_len(c.ny) && c.nz <= KW_FRAMES_MAX; // no transform along z, any Nz >= 1
   if (f.slab) ok = ok && (nzg == c.nz * f.nranks) && (c.ny % f.nranks == 0);
   if (ok && !has_partial_x_tiles(static_cast<int>(c.nx))) ok = (c.ny * c.nz) % (2u * static_cast<uint32_t>(nl_x(c.nx))) == 0;
   const uint64_t P64 = (c.nx_complex + NLMAX - 1) / NLMAX * NLMAX;
   ok = ok && (P64 * c.ny * c.nz < (1ull << 32)) && (static_cast<uint64_t>(c.nx) * c.ny * c.nz < (1ull << 32));
+  // frames mode: the pass along t holds the frame's offset in the 32-bit BYTE offset of its lanes (load_lines, store_lines),
+  // so the scratch array, side array included, ends below 4 GiB: 2^29 complex elements
+  if (f.frames) ok = ok && (P64 * c.ny * c.nz < (1ull << 29));
   *out = ok ? 1 : 0;
   return KW_OK;
 }
@@ -1504,6 +1528,31 @@ kw_status kw_fused_plane_recon(kw_ctx* ctx, const float* vol_even, const kw_plan
   KW_TRY(forward_xy(ctx, 1, in1));
   KW_TRY(zfused_recon(ctx, S[0], op));
   KW_TRY(inverse_y(ctx, 1));
+  XinvArgs x{};
+  x.in[0]  = S[0];
+  x.out[0] = vol_out;
+  KW_TRY(launch_xinv<EPI_STORE>(ctx, 1, x));
+  return KW_OK;
+}
+
+// Batched k-space line reconstruction (kw_line_recon.hip), frames mode: the x-forward over all Ny * Nz rows, ONE launch of
+// k_yfused_line_recon (forward along t, weight, gather, inverse along t, each frame's lines apart), the storing x-inverse.
+kw_status kw_fused_line_recon(kw_ctx* ctx, const float* vol_even, const kw_plane_recon_op* op, float* vol_out)
+{
+  KW_CHECK_CONSTS(ctx);
+  if (!ctx->fused.ready) { kw_set_error("kw_fused_line_recon: kw_fused_create has not been called"); return KW_ERR_STATE; }
+  KW_PROF(ctx, "fused_line_recon");
+  KW_REQUIRE(vol_even && op && vol_out);
+  if (!ctx->fused.frames)
+  {
+    kw_set_error("kw_fused_line_recon: needs a context in frames mode (kw_fused_set_frames before kw_fused_create)");
+    return KW_ERR_INVALID;
+  }
+  KW_REQUIRE(op->dx > 0.0 && op->dt > 0.0 && op->c0 > 0.0 && (op->interp == 0 || op->interp == 1));
+  float2** S = ctx->fused.s;
+  const float* in1[1] = { vol_even };
+  KW_TRY(launch_xfwd(ctx, 1, in1, S));
+  KW_TRY(yfused_line_recon(ctx, S[0], op));
   XinvArgs x{};
   x.in[0]  = S[0];
   x.out[0] = vol_out;

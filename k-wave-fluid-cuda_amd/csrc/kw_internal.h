@@ -54,6 +54,7 @@ struct kw_ctx
   bool         fft_setup   = false;
   kw_fft_plan  r2c_3d, c2r_3d;
   kw_fft_plan  r2c_1d[3], c2r_1d[3];
+  kw_fft_plan  r2c_frames, c2r_frames;   // nz independent 2-D transforms of (nx, ny) (kw_fft_create_plans_frames)
   void*        fft_work       = nullptr; // one shared work buffer, sized for the largest plan
   size_t       fft_work_bytes = 0;
   // fused spectral pipeline (kw_fused*.hip): private padded spectral scratch + per-axis twiddle tables
@@ -87,6 +88,8 @@ struct kw_ctx
     // spectra (forward receive = z-pass in / out = backward send), so that the plane-local tail of a stage — backward
     // receive t[] -> y-inverse -> s[] -> x-inverse + epilogue -> chained x / y forward -> t[] -> forward send — runs per
     // chunk of planes while the other chunks are on the wire.
+    bool     frames = false;                       // kw_fused_set_frames: nz independent planes (ny x nx), no transform along z;
+                                                   // kw_fused_line_recon is the context's one stage
     bool     two_d = false;                        // Nz == 1: x-pass, fused pass along y (in the z-pass kernels' role), x-pass; no y-pass
     bool     pipelined = false;
     uint32_t xchunks   = 1;                        // plane chunks per array of the pipelined tail

@@ -4,7 +4,8 @@
 // (kwave_hip.h documents the definition and the order of the arithmetic).  The re-gridding from w to kz moves data between
 // the bins of one (kx, ky) line — the line the z-pass of the fused pipeline holds in LDS.
 //
-//   recon_w / recon_f    weight and gather position of one bin: shared by the fused kernel and the twin
+//   recon_w / recon_f    weight and gather position of one bin: shared by the fused kernel and the twin, and with the
+//                        line reconstruction (kw_recon_device.h, with recon_scale, recon_pick and the crop kernel)
 //   k_zfused_recon       the z-pass of kw_fused_plane_recon (kw_fused_main.hip): lines of scratch array 0 forward along t,
 //                        T written back into the exchange buffer, the gather from LDS, inverse along t, in place — no
 //                        operator array and no index table in memory
@@ -12,6 +13,7 @@
 //   kw_plane_recon_embed / _crop   the mirrored embedding of the record; the first planes of the domain crop, clamped on request
 #include "kw_elementwise.h"
 #include "kw_fused.hip"
+#include "kw_recon_device.h"
 
 namespace {
 
@@ -22,41 +24,6 @@ __device__ __forceinline__ double recon_rho2(double dkx, double dky, double dk2,
   const double kx = dkx * static_cast<double>(kw_folded(ix, ex));
   const double ky = dky * static_cast<double>(kw_folded(iy, ey));
   return ((kx * kx) + (ky * ky)) / dk2;
-}
-
-// w(rho2, m') * scale: sqrt(m'^2 - rho2) / m' on the propagating side, 1 at the origin, 0 elsewhere.  float64 up to the
-// square root, float32 from there; no contraction.  Real calls, not inlined, as time_h (kw_angular_time.hip): unrolled
-// over the R2 bins of a thread the float64 square roots would be scheduled side by side and cost the z-pass its registers.
-__device__ __attribute__((noinline)) float recon_w(double rho2, uint32_t mp, float scale)
-{
-#pragma clang fp contract(off)
-  const double md = static_cast<double>(mp);
-  const double d  = (md * md) - rho2;
-  if (mp == 0) return rho2 == 0.0 ? scale : 0.f;
-  if (d < 0.0) return 0.f;
-  return (static_cast<float>(sqrt(d)) / static_cast<float>(mp)) * scale;
-}
-
-// the gather position f = sqrt(m'^2 + rho2) of bin m', float64
-__device__ __attribute__((noinline)) double recon_f(double rho2, uint32_t mp)
-{
-#pragma clang fp contract(off)
-  const double md = static_cast<double>(mp);
-  return sqrt((md * md) + rho2);
-}
-
-__device__ __forceinline__ float2 recon_scale(const float2& x, float w)
-{
-#pragma clang fp contract(off)
-  return make_float2(w * x.x, w * x.y);
-}
-
-// G from the two neighbours T0 = T[i0], T1 = T[min(i0 + 1, M)] and a = f - i0
-__device__ __forceinline__ float2 recon_pick(const float2& t0, const float2& t1, float a, bool nearest)
-{
-#pragma clang fp contract(off)
-  if (nearest) return a < 0.5f ? t0 : t1;
-  return make_float2((a * (t1.x - t0.x)) + t0.x, (a * (t1.y - t0.y)) + t0.y);
 }
 
 // =====================================================================================================================
@@ -70,6 +37,8 @@ __device__ __forceinline__ float2 recon_pick(const float2& t0, const float2& t1,
 //      m' <= M are read (the cells of the upper half are written and never looked at: T[m'] is the lower half's)
 //   4. a second barrier, before inverse_from_regs overwrites the buffer
 // No LDS beyond Geo::LDSB, nothing read from memory but the lines.
+// k_yfused_line_recon (kw_line_recon.hip) is this body with lines along y and rho2 of the column alone: a change to the
+// weight, the gather or the barrier order here is a change there as well.
 //   load | barrier (twiddles) | fwd_cols | barrier | fwd_rows -> 1. | barrier | 3. | barrier | inverse_from_regs -> store
 // =====================================================================================================================
 template<int L> __global__ __launch_bounds__((Geo<L, nl_z(L)>::THREADS)) void k_zfused_recon(ZReconArgs a)
@@ -169,32 +138,6 @@ __global__ __launch_bounds__(256) void k_plane_recon_mix(float2* __restrict__ ou
       res = recon_pick(t0, t1, al, nearest);
     }
     out[e] = res;
-  }
-}
-
-__device__ __forceinline__ float recon_clamp(float x, bool positivity) { return (positivity && !(x > 0.f)) ? 0.f : x; }
-
-// out [nt][ny][nx] <- the corner of vol [lt][ey][ex] (nt = the planes), clamped at 0 on request
-template<int V> __global__ __launch_bounds__(256) void k_recon_crop(float* __restrict__ out, const float* __restrict__ vol, kw_record_dims d,
-                                                                    int positivity)
-{
-  const uint32_t nxv = d.nx / V;
-  const uint64_t n   = static_cast<uint64_t>(nxv) * d.ny * d.nt;
-  const bool     pos = positivity != 0;
-  for (uint64_t e = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; e < n;
-       e += static_cast<uint64_t>(gridDim.x) * blockDim.x)
-  {
-    const uint32_t ix = static_cast<uint32_t>(e % nxv) * V;
-    const uint64_t r  = e / nxv;
-    const uint32_t iy = static_cast<uint32_t>(r % d.ny), t = static_cast<uint32_t>(r / d.ny);
-    const uint64_t s  = (static_cast<uint64_t>(t) * d.ey + iy) * d.ex + ix;
-    if constexpr (V == 4)
-    {
-      float4 q = *reinterpret_cast<const float4*>(vol + s);
-      q.x = recon_clamp(q.x, pos); q.y = recon_clamp(q.y, pos); q.z = recon_clamp(q.z, pos); q.w = recon_clamp(q.w, pos);
-      *reinterpret_cast<float4*>(out + e * 4) = q;
-    }
-    else out[e] = recon_clamp(vol[s], pos);
   }
 }
 

@@ -54,6 +54,24 @@ bool DeviceGrid::choosePipeline(bool wantFused, const kw_constants* unfusedConst
   return mFused;
 }
 
+bool DeviceGrid::choosePipeline(bool wantFused, const std::function<void(bool)>& setMode, const std::function<void()>& makePlans)
+{
+  int fusedOk = 0;
+  if (wantFused)
+  {
+    setMode(true);
+    check(kw_fused_supported(mCtx, &fusedOk));
+  }
+  mFused = fusedOk != 0;
+  if (mFused) check(kw_fused_create(mCtx));
+  else
+  {
+    setMode(false);
+    makePlans();
+  }
+  return mFused;
+}
+
 void* DeviceGrid::bytes(size_t nBytes)
 {
   void* d = nullptr;

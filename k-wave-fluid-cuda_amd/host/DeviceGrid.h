@@ -1,9 +1,10 @@
 // DeviceGrid.h — the one owner of a kw_ctx for the operators that bring their own context (ThermalSolver, CwPropagator,
-// AngularSpectrum, AngularSpectrumTime, PlaneRecon): the context, its FFT pipeline and every device allocation, released
+// AngularSpectrum, AngularSpectrumTime, PlaneRecon, LineRecon): the context, its FFT pipeline and every device allocation, released
 // by the destructor.  Held as a member: when the enclosing constructor throws, what was built so far goes the same way.
 #ifndef KW_HOST_DEVICE_GRID_H
 #define KW_HOST_DEVICE_GRID_H
 #include <cstddef>
+#include <functional>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -35,6 +36,11 @@ class DeviceGrid
   /// the fused pipeline when wanted and supported for the constants set, the 3-D rocFFT plans otherwise — those for
   /// `unfusedConstants` where given (a pipeline and plans of different shapes); returns fused()
   bool choosePipeline(bool wantFused, const kw_constants* unfusedConstants = nullptr);
+
+  /// the same choice for a pipeline with a mode of its own (LineRecon's frames context): setMode(true) comes before the
+  /// support query, and where the pipeline is not taken setMode(false) and makePlans() replace the 3-D plans; both call
+  /// the device library themselves and report through check; returns fused()
+  bool choosePipeline(bool wantFused, const std::function<void(bool)>& setMode, const std::function<void()>& makePlans);
 
   void*  bytes(size_t nBytes);
   float* array(size_t nFloats) { return static_cast<float*>(bytes(nFloats * sizeof(float))); }

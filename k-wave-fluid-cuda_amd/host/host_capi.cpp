@@ -14,6 +14,7 @@
 #include "AngularSpectrum.h"
 #include "AngularSpectrumTime.h"
 #include "CwPropagator.h"
+#include "LineRecon.h"
 #include "PlaneRecon.h"
 #include "kwave_host.h"
 
@@ -208,6 +209,28 @@ static PlaneReconParameters kwh_plane_recon_parameters(const kwh_plane_recon_con
   p.c0 = c->c0;
   p.ex = c->ex; p.ey = c->ey; p.lt = c->lt;
   p.planes = c->planes;
+  p.interp = c->interp;
+  p.positivity = c->positivity != 0;
+  p.init(kwh_device_options(o));
+  return p;
+}
+
+/// a batched k-space line reconstruction with its completed parameters
+struct kwh_line_recon
+{
+  LineReconParameters        params;
+  std::unique_ptr<LineRecon> recon;
+};
+
+static LineReconParameters kwh_line_recon_parameters(const kwh_line_recon_config* c, const kwh_options* o)
+{
+  LineReconParameters p;
+  p.ny = c->ny; p.nt = c->nt; p.frames = c->frames;
+  p.dy = c->dy; p.dt = c->dt;
+  p.c0 = c->c0;
+  p.ey = c->ey; p.lt = c->lt;
+  p.depth = c->depth;
+  p.chunkFrames = c->chunk_frames;
   p.interp = c->interp;
   p.positivity = c->positivity != 0;
   p.init(kwh_device_options(o));
@@ -876,4 +899,66 @@ int kwh_plane_recon_get_scalar(kwh_plane_recon* s, const char* name, double* out
 }
 
 void* kwh_plane_recon_context(kwh_plane_recon* s) { return s ? s->recon->context() : nullptr; }
+
+// ---- batched k-space line reconstruction -----------------------------------------------------------------------------
+int kwh_line_recon_plan(const kwh_line_recon_config* config, const kwh_options* o, uint64_t out_sizes[4], int32_t* out_fast_path)
+{
+  KWH_TRY
+  if (!config || !o) throw std::invalid_argument("kwh_line_recon_plan: NULL argument");
+  const LineReconParameters p = kwh_line_recon_parameters(config, o);
+  if (out_sizes) { out_sizes[0] = p.ey; out_sizes[1] = p.lt; out_sizes[2] = p.depth; out_sizes[3] = p.chunkFrames; }
+  if (out_fast_path) *out_fast_path = p.fastPath ? 1 : 0;
+  KWH_CATCH
+}
+
+int kwh_line_recon_create(const kwh_line_recon_config* config, const kwh_options* o, kwh_line_recon** out)
+{
+  return kwh_create_handle("kwh_line_recon_create", config, o, out, [&](kwh_line_recon& s) {
+    s.params = kwh_line_recon_parameters(config, o);
+    s.recon.reset(new LineRecon(s.params));
+  });
+}
+
+int kwh_line_recon_destroy(kwh_line_recon* s)
+{
+  KWH_TRY
+  delete s;
+  KWH_CATCH
+}
+
+int kwh_line_recon_run(kwh_line_recon* s, const float* p)
+{
+  KWH_TRY
+  if (!s || !p) throw std::invalid_argument("kwh_line_recon_run: NULL argument");
+  s->recon->run(p);
+  KWH_CATCH
+}
+
+int kwh_line_recon_get(kwh_line_recon* s, const char* name, float* dst, uint64_t n)
+{
+  KWH_TRY
+  if (!s || !name || !dst) throw std::invalid_argument("kwh_line_recon_get: NULL argument");
+  s->recon->get(name, dst, n);
+  KWH_CATCH
+}
+
+int kwh_line_recon_get_scalar(kwh_line_recon* s, const char* name, double* out)
+{
+  KWH_TRY
+  if (!s || !name || !out) throw std::invalid_argument("kwh_line_recon_get_scalar: NULL argument");
+  const std::string n(name);
+  const LineReconParameters& p = s->recon->parameters();
+  if (n == "fused_pipeline") *out = s->recon->usesFusedPipeline() ? 1.0 : 0.0;
+  else if (n == "Ey") *out = static_cast<double>(p.ey);
+  else if (n == "Lt") *out = static_cast<double>(p.lt);
+  else if (n == "depth") *out = static_cast<double>(p.depth);
+  else if (n == "frames") *out = static_cast<double>(p.frames);
+  else if (n == "chunk_frames") *out = static_cast<double>(p.chunkFrames);
+  else if (n == "dx") *out = p.dx();
+  else if (n == "runs") *out = static_cast<double>(s->recon->runs());
+  else throw std::invalid_argument(std::string("unknown scalar ") + name);
+  KWH_CATCH
+}
+
+void* kwh_line_recon_context(kwh_line_recon* s) { return s ? s->recon->context() : nullptr; }
 }

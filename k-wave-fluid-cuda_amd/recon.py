@@ -1,4 +1,5 @@
-"""k-space plane reconstruction front-end (include/kwave_host.h "k-space plane reconstruction" -> lib/libkwave_host.so).
+"""k-space reconstruction front-ends (include/kwave_host.h "k-space plane reconstruction" and "Batched k-space line
+reconstruction" -> lib/libkwave_host.so).
 
 `PlaneRecon` takes the record p(x, y, t) of a planar sensor — a photoacoustic measurement, or the sensor plane of a
 time-loop run — and recovers the initial pressure p0(x, y, z) that produced it, what k-Wave's kspacePlaneRecon computes:
@@ -7,9 +8,12 @@ kz = sqrt((w / c)^2 - kx^2 - ky^2) with a weight, and one inverse 3-D FFT.  It i
 `angular.AngularSpectrumTime` carries forward.  On fast-path sizes the whole reconstruction is one round trip of the fused
 pipeline, the re-gridding done along the line its z-pass holds in LDS.  No CPU fallback: a missing library or device raises.
 
-Not built: 2-D (kspaceLineRecon), heterogeneous media, Z-slabs, HDF5 files and the command line, graphs, a half-length
-(DCT) time transform that would use the evenness of the mirrored record, the x- and y-inverse restricted to the crop, other
-interpolants.
+`LineRecon` is its 2-D form for a linear array, what k-Wave's kspaceLineRecon computes, batched: a stream of frames
+p(t, y) to the images p0(x, y), F frames in one round trip of the pipeline (a context whose z axis is the batch).
+
+Not built: heterogeneous media, Z-slabs, HDF5 files and the command line, graphs, the 2-D forms of the three projectors,
+frames spread over several GPUs; a half-length (DCT) time transform that would use the evenness of the mirrored record, the
+x- and y-inverse restricted to the crop, other interpolants.
 """
 from __future__ import annotations
 
@@ -31,6 +35,13 @@ class Config(C.Structure):
                 ("planes", C.c_uint64), ("interp", C.c_int32), ("positivity", C.c_int32)]
 
 
+class LineConfig(C.Structure):
+    """struct kwh_line_recon_config"""
+    _fields_ = [("ny", C.c_uint64), ("nt", C.c_uint64), ("frames", C.c_uint64), ("dy", C.c_double), ("dt", C.c_double),
+                ("c0", C.c_double), ("ey", C.c_uint64), ("lt", C.c_uint64), ("depth", C.c_uint64),
+                ("chunk_frames", C.c_uint64), ("interp", C.c_int32), ("positivity", C.c_int32)]
+
+
 def _lib() -> C.CDLL:
     global _bound
     L = load_host()
@@ -43,6 +54,14 @@ def _lib() -> C.CDLL:
         L.kwh_plane_recon_get_scalar.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_double)]
         L.kwh_plane_recon_context.restype = C.c_void_p
         L.kwh_plane_recon_context.argtypes = [C.c_void_p]
+        L.kwh_line_recon_plan.argtypes = [C.POINTER(LineConfig), C.POINTER(Options), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]
+        L.kwh_line_recon_create.argtypes = [C.POINTER(LineConfig), C.POINTER(Options), C.POINTER(C.c_void_p)]
+        L.kwh_line_recon_destroy.argtypes = [C.c_void_p]
+        L.kwh_line_recon_run.argtypes = [C.c_void_p, C.c_void_p]
+        L.kwh_line_recon_get.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint64]
+        L.kwh_line_recon_get_scalar.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_double)]
+        L.kwh_line_recon_context.restype = C.c_void_p
+        L.kwh_line_recon_context.argtypes = [C.c_void_p]
         _bound = True
     return L
 
@@ -167,6 +186,134 @@ class PlaneRecon:
     def close(self):
         if getattr(self, "_h", None):
             self.L.kwh_plane_recon_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _line_config(ny, dy, dt, nt, c0, frames, depth, interp, positivity, expanded, time_length, chunk_frames) -> LineConfig:
+    if int(ny) < 0 or int(nt) < 0 or int(frames) < 0:
+        raise ValueError(f"ny, nt and frames must not be negative, got {ny}, {nt}, {frames}")
+    if interp not in INTERP:
+        raise ValueError(f"interp must be one of {sorted(INTERP)}, got {interp!r}")
+    c = LineConfig()
+    c.ny, c.nt, c.frames = int(ny), int(nt), int(frames)
+    c.dy, c.dt, c.c0 = float(dy), float(dt), float(c0)
+    c.interp = INTERP[interp]
+    c.positivity = int(bool(positivity))
+    for name, field, value in (("depth", "depth", depth), ("expanded", "ey", expanded), ("time_length", "lt", time_length),
+                               ("chunk_frames", "chunk_frames", chunk_frames)):
+        if value is not None:
+            if int(value) <= 0:
+                raise ValueError(f"{name} must be positive, got {value}")
+            setattr(c, field, int(value))
+    return c
+
+
+def plan_line_recon(ny, dy, dt, nt, c0, frames=1, depth=None, interp="linear", positivity=False, expanded=None,
+                    time_length=None, chunk_frames=None, fused_kernels=True) -> Tuple[int, int, int, int, bool]:
+    """(Ey, Lt, depth, chunk_frames, fast path) of a line reconstruction, validated as LineRecon would, without a device"""
+    L = _lib()
+    c = _line_config(ny, dy, dt, nt, c0, frames, depth, interp, positivity, expanded, time_length, chunk_frames)
+    o = Options()
+    o.fused_kernels = int(bool(fused_kernels))
+    e, fast = (C.c_uint64 * 4)(), C.c_int32()
+    _check(L.kwh_line_recon_plan(C.byref(c), C.byref(o), e, C.byref(fast)))
+    return int(e[0]), int(e[1]), int(e[2]), int(e[3]), bool(fast.value)
+
+
+class LineRecon:
+    """Reconstruction of `frames` images from the records p (F, Nt, Ny) (y fastest) of a linear array sampled at
+    t_n = n dt: `run(p)` gives p0 on the rows x_j = j c0 dt, float32 (F, depth, Ny).  With frames == 1, (Nt, Ny) gives
+    (depth, Ny).  order="yt" takes the transposed records (F, Ny, Nt), as k-Wave's sensor_data(y, t).
+
+    ny = Ny, dy [m], dt [s], nt = Nt, c0 [m/s].  depth: default Nt.  interp: "linear" or "nearest".  positivity: clamp the
+    result at 0.  expanded = Ey: default Ny.  time_length = Lt >= 2 Nt - 1: default the smallest fast-path length at or above
+    2 Nt - 1, or 2 Nt - 1 itself with fused_kernels=False or above 1024.  chunk_frames: the frames that go through the pipeline
+    at once (default all, capped at 65535 frames and at 4 GiB of spectrum, 2^29 padded bins); a run goes chunk by chunk on one context, and a frame's result
+    does not depend on the chunking on the fused path.  The fused stage runs when Ey and Lt are fast-path lengths (and, for the
+    ten lengths of Ey without masked x kernels, Lt chunk_frames is a multiple of 16), the rocFFT twin otherwise."""
+
+    def __init__(self, ny, dy, dt, nt, c0, frames=1, depth=None, interp="linear", positivity=False, expanded=None,
+                 time_length=None, chunk_frames=None, order="ty", fused_kernels=True, device_idx=-1):
+        if order not in ("ty", "yt"):
+            raise ValueError(f"order must be 'ty' or 'yt', got {order!r}")
+        L = _lib()
+        c = _line_config(ny, dy, dt, nt, c0, frames, depth, interp, positivity, expanded, time_length, chunk_frames)
+        o = Options()
+        o.device_idx = int(device_idx)
+        o.fused_kernels = int(bool(fused_kernels))
+        self.L, self._h = L, None
+        h = C.c_void_p()
+        _check(L.kwh_line_recon_create(C.byref(c), C.byref(o), C.byref(h)))
+        self._h = h
+        self.ny, self.nt, self.frames = int(c.ny), int(c.nt), int(c.frames)
+        self.dy, self.dt, self.c0 = float(c.dy), float(c.dt), float(c.c0)
+        self.interp, self.positivity, self.order = interp, bool(positivity), order
+        self.depth = int(self._scalar("depth"))
+
+    def _scalar(self, name: str) -> float:
+        v = C.c_double()
+        _check(self.L.kwh_line_recon_get_scalar(self._h, name.encode(), C.byref(v)))
+        return float(v.value)
+
+    @property
+    def shape(self):
+        return (self.frames, self.depth, self.ny)
+
+    @property
+    def dx(self) -> float:
+        """row spacing c0 dt [m]"""
+        return self._scalar("dx")
+
+    @property
+    def expanded(self) -> int:
+        return int(self._scalar("Ey"))
+
+    @property
+    def time_length(self) -> int:
+        return int(self._scalar("Lt"))
+
+    @property
+    def chunk_frames(self) -> int:
+        return int(self._scalar("chunk_frames"))
+
+    @property
+    def fused(self) -> bool:
+        return self._scalar("fused_pipeline") != 0.0
+
+    @property
+    def runs(self) -> int:
+        return int(self._scalar("runs"))
+
+    @property
+    def ctx(self):
+        return C.c_void_p(self.L.kwh_line_recon_context(self._h))
+
+    def run(self, p) -> np.ndarray:
+        """p0 for the records p: float32 (F, depth, Ny), or (depth, Ny) for one frame handed in as a 2-D array"""
+        a = np.asarray(p, dtype=np.float32)
+        single = a.ndim == 2 and self.frames == 1
+        if single:
+            a = a[None]
+        want = (self.frames, self.nt, self.ny) if self.order == "ty" else (self.frames, self.ny, self.nt)
+        if a.shape != want:
+            raise ValueError(f"p must be {'(F, Nt, Ny)' if self.order == 'ty' else '(F, Ny, Nt)'} = {want}, got {a.shape}")
+        if self.order == "yt":
+            a = a.transpose(0, 2, 1)
+        a = np.ascontiguousarray(a)
+        _check(self.L.kwh_line_recon_run(self._h, a.ctypes.data))
+        out = np.empty(self.shape, dtype=np.float32)
+        _check(self.L.kwh_line_recon_get(self._h, b"p0", out.ctypes.data, out.size))
+        return out[0] if single else out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.L.kwh_line_recon_destroy(self._h)
             self._h = None
 
     def __del__(self):

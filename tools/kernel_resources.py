@@ -27,12 +27,13 @@ def main():
     extra = sys.argv[2:]
     with tempfile.TemporaryDirectory() as tmp, concurrent.futures.ThreadPoolExecutor(8) as pool:
         # the fused pipeline's code objects, and those of the CW propagator and the angular-spectrum projectors (the pair
-        # z-pass, the CW projector's y-inverse, the time-domain projector's z-pass and the plane reconstruction's z-pass are kernels of that
-        # pipeline)
+        # z-pass, the CW projector's y-inverse, the time-domain projector's z-pass, the plane reconstruction's z-pass and
+        # the line reconstruction's pass along t are kernels of that pipeline)
         srcs = sorted(glob.glob(os.path.join(CSRC, "kw_fused_*.hip"))) + [os.path.join(CSRC, "kw_cw.hip"),
                                                                           os.path.join(CSRC, "kw_angular.hip"),
                                                                           os.path.join(CSRC, "kw_angular_time.hip"),
-                                                                          os.path.join(CSRC, "kw_plane_recon.hip")]
+                                                                          os.path.join(CSRC, "kw_plane_recon.hip"),
+                                                                          os.path.join(CSRC, "kw_line_recon.hip")]
         texts = list(pool.map(compile_one, [(length, src, tmp, extra) for src in srcs]))
     pat = re.compile(r"Function Name: (\S+).*?SGPRs: (\d+).*?VGPRs: (\d+).*?AGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+).*?"
                      r"Occupancy \[waves/SIMD\]: (\d+).*?LDS Size \[bytes/block\]: (\d+)", re.S)
