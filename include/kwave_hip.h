@@ -951,6 +951,62 @@ KW_API kw_status kw_line_recon_embed(kw_ctx* ctx, float* vol, const float* src, 
 KW_API kw_status kw_line_recon_crop(kw_ctx* ctx, float* out, const float* vol, uint32_t ey, uint32_t lt, uint32_t frames,
                                     uint32_t ny, uint32_t depth, int32_t positivity);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Exact k-space propagator (what k-Wave's kspaceSecondOrder computes): an initial pressure p0[z][y][x] in a homogeneous
+ * medium, lossless or power-law absorbing, to the pressure at any time t >= 0 with no time loop (csrc/kw_second_order.hip,
+ * host/SecondOrder.cpp, DESIGN.md "Exact k-space propagator").  The grid of kw_set_constants is (nx, ny, nz) =
+ * (Ex, Ey, Ez), the expanded periodic grid into whose corner p0 is embedded.
+ *     p(., ., .; t) = irfftn( rfftn(p0 embedded) H(|k|; t) ),   |k|^2 = (kx^2 + ky^2) + kz^2         axes (z, y, x)
+ *     bins are counted k? = 2 pi / (n? d?) * min(i, n? - i)
+ *     lossless:  H = cos(c0 |k| t)
+ *     absorbing: per mode p'' + 2 gamma p' + Omega^2 p = 0, p(0) = P0, p'(0) = 0 — the equation that the time loop's
+ *                equation of state (absorb_tau on -d rho/dt, absorb_eta subtracted) gives for a homogeneous medium;
+ *                a = alpha_coeff 100 (1e-6 / 2 pi)^y / (20 log10 e)  [Np (rad/s)^-y m^-1], converted on the host
+ *       g = a c0^y |k|^(y-1)    T = tan(pi y / 2) (0 for y = 2)    B = 1 - 2 g T - g^2    r = sqrt(B)
+ *       gamma = c0 |k| g        w_d = c0 |k| r
+ *       H = exp(-gamma t) (cos(w_d t) + (g / r) sin(w_d t));    |k| = 0: H = 1
+ *     Underdamped modes only: the caller keeps B >= 1/4 on every bin (SecondOrderParameters refuses alpha_coeff otherwise).
+ * H is real and depends on |k| only, so the half-spectrum stays Hermitian and one real array is enough.
+ *
+ * H per bin is ONE device function (second_h) for the fused kernel and the twin, without contraction into fma:
+ *   float64: kx, ky, kz from the bin counts;  kr2 = (kx*kx) + (ky*ky);  k2 = kr2 + (kz*kz);  k = sqrt(k2);  k2 == 0: H = divider
+ *            absorbing: s = k (y = 2), sqrt(k) (y = 1.5) or pow(k, y - 1);  g = ac * s with ac = a c0^y from the host;
+ *                       B = (1 - (twoT * g)) - (g*g) with twoT = 2 T from the host;  r = sqrt(B);  lossless: r = 1
+ *            turns = ((k * r) * ct) / 2 pi with ct = c0 * t from the host;  word = uint32(rint((turns - floor(turns)) * 2^32))
+ *   float32: angle = float(int32(word)) * (2 pi 2^-32), one sincosf (cosf when lossless; the hardware sine is not used);
+ *            absorbing: E = exp2f(-float(((k * g) * ct) * log2(e)));  q = float(g / r);  H = (E * (cos + (q * sin))) * divider
+ *            lossless:  H = cos * divider;        out = (H * x.x, H * x.y)
+ *   |k|^(y-1) is evaluated once, in float64, for the phase and for E alike.  A float32 product c0 |k| t would be several
+ *   1e-3 rad off at 10^4 turns; the phase word is exact to 2^-33 turns.
+ *
+ * kw_fused_second_order_elems: complex values of one scratch array = the size of `kept`.
+ * kw_fused_second_order_forward: kept <- the (kx, ky, z) half-spectrum of vol [nz][ny][nx]: x-forward and y-forward, then a
+ *   copy of scratch array 0, side array included — kw_fused_angular_time_forward's operation, one implementation.
+ * kw_fused_second_order_time: vol_out [nz][ny][nx] <- the pressure at op->t: one launch k_zfused_second_order (lines of
+ *   `kept` forward along z, H formed in registers from the column, the row and the bin m — no operator array, no table in
+ *   memory —, inverse along z into scratch array 0; divider = 1 / (nx ny nz)), the y-inverse and the storing x-inverse.
+ *   `kept` is not written.  Both: single GPU, nz > 1: KW_ERR_INVALID in slab mode, for Nz == 1 and on a frames context.
+ * kw_second_order_mix: the twin: out_spec <- spec H on the natural [nz][ny][nx/2 + 1] half-spectrum of kw_fft_r2c_3d, out
+ *   of place, for kw_fft_c2r_3d (grids off the fast path; any nx, ny, nz, odd ones included).  A context without bins:
+ *   KW_OK, nothing launched.
+ * Embedding and crop: kw_angular_time_embed and kw_plane_recon_crop (a 3-D corner either way).  Sensor records and the
+ * aggregates over the output times: kw_sample_index and kw_sample_all on the volume and on the crop.
+ * Not built: dp0/dt as a second initial condition and time-varying sources, heterogeneous media, 2-D (Nz == 1) and its
+ * batched form on a frames context, Z-slabs, several output times per z-pass, inverse passes restricted to the crop or to
+ * the sensor points, particle velocity.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct kw_second_order_op {   /* H of one time */
+  double  dx, dy, dz, c0, t;          /* [m], [m], [m], [m/s], [s]; t >= 0 */
+  double  a, alpha_power;             /* a [Np (rad/s)^-y m^-1] and y; read when absorbing != 0 */
+  int32_t absorbing;                  /* 0 = lossless */
+  int32_t reserved;                   /* 0 */
+} kw_second_order_op;
+KW_API kw_status kw_fused_second_order_elems(kw_ctx* ctx, size_t* out_elems);
+KW_API kw_status kw_fused_second_order_forward(kw_ctx* ctx, const float* vol, float* kept);
+KW_API kw_status kw_fused_second_order_time(kw_ctx* ctx, const float* kept, const kw_second_order_op* op, float* vol_out);
+KW_API kw_status kw_second_order_mix(kw_ctx* ctx, float* out_spec, const float* spec, const kw_second_order_op* op,
+                                     float divider);
+
 #ifdef __cplusplus
 }
 #endif

@@ -468,6 +468,66 @@ KWH_API int      kwh_line_recon_get_scalar(kwh_line_recon* s, const char* name, 
 /* the underlying kw_ctx* (include/kwave_hip.h) */
 KWH_API void*    kwh_line_recon_context(kwh_line_recon* s);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Exact k-space propagator (what k-Wave's kspaceSecondOrder computes): an initial pressure p0[z][y][x] on the domain
+ * Nx x Ny x Nz of a homogeneous medium, lossless or with power-law absorption alpha_coeff f^alpha_power (dB / (MHz^y cm),
+ * with its dispersion), to the pressure at any time t >= 0 — exactly, with no time loop, no CFL limit and no accumulated
+ * stepping error.  p0 is transformed once; every output time costs one multiply by the real H(|k|; t) and one inverse
+ * transform (kwave_hip.h "Exact k-space propagator").
+ *   E (0 0 0 = default): the expanded periodic grid into whose corner the domain is embedded.  Default, with t_max > 0: per
+ *   axis the smallest fast-path length at or above N + ceil(c0 t_max / d), or that number itself where there is none (above
+ *   1024) or with fused_kernels off.  Given sides: all three, not below N; E = N is the periodic box.  t_max is then not read.
+ *   The box is periodic: the result inside the domain is the free-space one for c0 t <= min over axes of (E - N) d; the
+ *   scalar "t_free" reports that time.  Later times are not refused.
+ *   Absorption: underdamped modes only — alpha_coeff is refused when B = 1 - 2 g tan(pi y / 2) - g^2, g = a c0^y |k|^(y-1),
+ *   is below 1/4 at the smallest non-zero or at the largest |k| of the grid (B is concave in |k|^(y-1)).
+ *   sensor_index: n_sensor 0-based flat indices into the domain [Nz][Ny][Nx]; kwh_second_order_run samples them at every
+ *   time.  flags: which aggregates over the output times of a run are kept, each on the domain.
+ * Refused, naming the parameter: Nx Ny Nz (0), dx dy dz c0 (not positive), t_max (not positive while the sides are by
+ * default), alpha_coeff (< 0, the B rule), alpha_power (outside 0 <= y < 3, y = 1), Ex Ey Ez (missing, below N), E (2^32 points
+ * or more), sensor_index (NULL, an entry outside the domain), t (negative or not finite), n_times (0).
+ * Of kwh_options the calls read device_idx and fused_kernels.  kwh_second_order_plan validates and completes (Ex, Ey, Ez)
+ * and the fast-path flag without a device.  Not built: dp0/dt as a second initial condition and time-varying sources,
+ * heterogeneous media, 2-D (Nz == 1) and its batched form, Z-slabs, HDF5 files and the command line, graphs, several
+ * output times per z-pass, inverse passes restricted to the crop or to the sensor points, particle velocity outputs.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define KWH_SECOND_ORDER_P_MAX   1
+#define KWH_SECOND_ORDER_P_MIN   2
+#define KWH_SECOND_ORDER_P_RMS   4
+#define KWH_SECOND_ORDER_P_FINAL 8
+typedef struct kwh_second_order kwh_second_order;
+typedef struct kwh_second_order_config
+{
+  uint64_t nx, ny, nz;      /* the domain */
+  double   dx, dy, dz;      /* [m] */
+  double   c0;              /* [m/s] */
+  double   alpha_coeff;     /* [dB / (MHz^y cm)]; 0 = lossless */
+  double   alpha_power;     /* y */
+  double   t_max;           /* [s]; sizes the default sides; 0 with given sides */
+  uint64_t ex, ey, ez;      /* expanded sides; 0 0 0 = default */
+  uint64_t n_sensor;
+  const uint64_t* sensor_index; /* n_sensor indices into [Nz][Ny][Nx] */
+  int32_t  flags;           /* KWH_SECOND_ORDER_P_* */
+  int32_t  pad_;
+} kwh_second_order_config;
+KWH_API int      kwh_second_order_plan(const kwh_second_order_config* config, const kwh_options* options,
+                                       uint64_t out_expanded[3], int32_t* out_fast_path);
+KWH_API int      kwh_second_order_create(const kwh_second_order_config* config, const kwh_options* options,
+                                         kwh_second_order** out);
+KWH_API int      kwh_second_order_destroy(kwh_second_order* s);
+/* p0: Nx * Ny * Nz floats on the host ([Nz][Ny][Nx]): embed, transform, keep; may be called again */
+KWH_API int      kwh_second_order_set_p0(kwh_second_order* s, const float* p0);
+/* the pressure at time t; the crop [Nz][Ny][Nx] stays on the device ("p") and goes to dst where dst is not NULL */
+KWH_API int      kwh_second_order_field(kwh_second_order* s, double t, float* dst);
+/* every time in the given order: row i of the record, the aggregates */
+KWH_API int      kwh_second_order_run(kwh_second_order* s, const double* times, uint64_t n_times);
+/* "p_raw" [n_times][n_sensor], "p_max", "p_min", "p_rms", "p_final" of the last run, "p" (the last field); n checked */
+KWH_API int      kwh_second_order_get(kwh_second_order* s, const char* name, float* dst, uint64_t n);
+/* "fused_pipeline", "Ex", "Ey", "Ez", "t_free", "runs" */
+KWH_API int      kwh_second_order_get_scalar(kwh_second_order* s, const char* name, double* out);
+/* the underlying kw_ctx* (include/kwave_hip.h) */
+KWH_API void*    kwh_second_order_context(kwh_second_order* s);
+
 #ifdef __cplusplus
 }
 #endif

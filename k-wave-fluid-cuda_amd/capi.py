@@ -208,6 +208,10 @@ _SIG: Dict[str, list] = {
     "kw_angular_time_mix": [_P, _P, _P, _P, C.c_float],
     "kw_angular_time_embed": [_P, _P, _P] + [C.c_uint32] * 6,
     "kw_angular_time_reduce": [_P, _P] + [C.c_uint32] * 6 + [_P, _P, _P],
+    "kw_fused_second_order_elems": [_P, C.POINTER(C.c_size_t)],
+    "kw_fused_second_order_forward": [_P, _P, _P],
+    "kw_fused_second_order_time": [_P, _P, _P, _P],
+    "kw_second_order_mix": [_P, _P, _P, _P, C.c_float],
     "kw_fused_plane_recon": [_P, _P, _P, _P],
     "kw_plane_recon_mix": [_P, _P, _P, _P, C.c_float],
     "kw_plane_recon_embed": [_P, _P, _P] + [C.c_uint32] * 6,
@@ -232,6 +236,12 @@ class AngularTimeOp(C.Structure):
     """struct kw_angular_time_op: H of one plane of the time-domain angular-spectrum projector"""
     _fields_ = [("dx", C.c_double), ("dy", C.c_double), ("dt", C.c_double), ("c0", C.c_double), ("z", C.c_double),
                 ("ak", C.c_void_p), ("restriction", C.c_int32), ("retarded", C.c_int32)]
+
+
+class SecondOrderOp(C.Structure):
+    """struct kw_second_order_op: H of one output time of the exact k-space propagator"""
+    _fields_ = [("dx", C.c_double), ("dy", C.c_double), ("dz", C.c_double), ("c0", C.c_double), ("t", C.c_double),
+                ("a", C.c_double), ("alpha_power", C.c_double), ("absorbing", C.c_int32), ("reserved", C.c_int32)]
 
 
 ELEMENT_CHUNK = 1024  # KW_ELEMENT_CHUNK

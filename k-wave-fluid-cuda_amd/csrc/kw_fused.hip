@@ -215,6 +215,9 @@ kw_status yinv_angular(kw_ctx* ctx, AngArgs a);
 // the z-pass of kw_fused_angular_time_plane: one spectrum forward along t, H of the plane formed in registers, the inverse
 // (kw_angular_time.hip): lines of `in` (the kept spectrum) to `out`
 kw_status zfused_time(kw_ctx* ctx, const float2* in, float2* out, const kw_angular_time_op* op);
+// the z-pass of kw_fused_second_order_time: one spectrum forward along z, the real H(|k|; t) formed in registers, the inverse
+// (kw_second_order.hip): lines of `in` (the kept spectrum) to `out`
+kw_status zfused_second_order(kw_ctx* ctx, const float2* in, float2* out, const kw_second_order_op* op);
 // the z-pass of kw_fused_plane_recon: lines of `s` forward along t, the weight, the gather from w to kz along each line,
 // the inverse, in place (kw_plane_recon.hip)
 kw_status zfused_recon(kw_ctx* ctx, float2* s, const kw_plane_recon_op* op);
@@ -500,8 +503,8 @@ template<int L, int DIR> __device__ __forceinline__ void step_a(float2 (&v)[Fac<
 // What a y- or z-pass kernel is assembled from: the block's tile, the line loads and stores, and the two exchanges of a
 // four-step transform through the block's buffer lds[G::LDSB].  A kernel's body keeps what is its own — which arrays,
 // what happens to a bin between the transforms — and the order of loads, barriers and stores.
-// On the steps: k_zfused_split, k_zfused_pair_split (kw_cw.hip), k_zfused_time (kw_angular_time.hip), k_zfused_recon
-// (kw_plane_recon.hip), k_yfused_line_recon (kw_line_recon.hip); k_ypass and k_ypass_split take the tile and keep their
+// On the steps: k_zfused_split, k_zfused_pair_split (kw_cw.hip), k_zfused_time (kw_angular_time.hip), k_zfused_second_order
+// (kw_second_order.hip), k_zfused_recon (kw_plane_recon.hip), k_yfused_line_recon (kw_line_recon.hip); k_ypass and k_ypass_split take the tile and keep their
 // RowAddr loads and stores.  k_zfused, k_zfused_pair (kw_cw.hip) and k_yinv_angular (kw_angular.hip) spell the same steps out in their bodies: assembled from
 // the functions below the compiler allocates their guarded (non-whole-wave) and spilling instantiations differently — an
 // occupancy step lost at some lengths, scratch bytes gained at others — so they stay as they were written.  A change to

@@ -1479,17 +1479,24 @@ kw_status kw_fused_angular_time_elems(kw_ctx* ctx, size_t* out)
   return KW_OK;
 }
 
+// kept <- the (kx, ky, z) half-spectrum of vol: the x- and y-forward of the one array, then a copy of scratch array 0, side
+// array included (kw_fused_angular_time_forward and kw_fused_second_order_forward, after their own checks)
+static kw_status keep_forward_xy(kw_ctx* ctx, const float* vol, float* kept)
+{
+  const float* in1[1] = { vol };
+  KW_TRY(forward_xy(ctx, 1, in1));
+  const size_t elems = static_cast<size_t>(ctx->fused.Palloc) * ctx->c.ny * ctx->c.nz;
+  KW_HIP(hipMemcpyAsync(kept, ctx->fused.s[0], elems * sizeof(float2), hipMemcpyDeviceToDevice, ctx->stream));
+  return KW_OK;
+}
+
 kw_status kw_fused_angular_time_forward(kw_ctx* ctx, const float* vol, float* kept)
 {
   KW_FUSED_READY(ctx);
   KW_PROF(ctx, "fused_angular_time_forward");
   KW_REQUIRE(vol && kept);
   KW_ANGULAR_TIME_3D(ctx, "kw_fused_angular_time_forward")
-  const float* in1[1] = { vol };
-  KW_TRY(forward_xy(ctx, 1, in1));
-  const size_t elems = static_cast<size_t>(ctx->fused.Palloc) * ctx->c.ny * ctx->c.nz;
-  KW_HIP(hipMemcpyAsync(kept, ctx->fused.s[0], elems * sizeof(float2), hipMemcpyDeviceToDevice, ctx->stream));
-  return KW_OK;
+  return keep_forward_xy(ctx, vol, kept);
 }
 
 kw_status kw_fused_angular_time_plane(kw_ctx* ctx, const float* kept, const kw_angular_time_op* op, float* vol_out)
@@ -1501,6 +1508,44 @@ kw_status kw_fused_angular_time_plane(kw_ctx* ctx, const float* kept, const kw_a
   KW_REQUIRE(op->dx > 0.0 && op->dy > 0.0 && op->dt > 0.0 && op->c0 > 0.0 && op->z >= 0.0);
   float2** S = ctx->fused.s;
   KW_TRY(zfused_time(ctx, reinterpret_cast<const float2*>(kept), S[0], op));
+  KW_TRY(inverse_y(ctx, 1));
+  XinvArgs x{};
+  x.in[0]  = S[0];
+  x.out[0] = vol_out;
+  KW_TRY(launch_xinv<EPI_STORE>(ctx, 1, x));
+  return KW_OK;
+}
+
+// Exact k-space propagator (kw_second_order.hip): the projector's shape with the volume's own z axis — the (kx, ky, z)
+// half-spectrum of the embedded p0 kept aside, every output time one z-pass k_zfused_second_order that reads it, the
+// y-inverse and the storing x-inverse.
+kw_status kw_fused_second_order_elems(kw_ctx* ctx, size_t* out)
+{
+  KW_FUSED_READY(ctx);
+  KW_REQUIRE(out != nullptr);
+  *out = static_cast<size_t>(ctx->fused.Palloc) * ctx->c.ny * ctx->c.nz;
+  return KW_OK;
+}
+
+kw_status kw_fused_second_order_forward(kw_ctx* ctx, const float* vol, float* kept)
+{
+  KW_FUSED_READY(ctx);
+  KW_PROF(ctx, "fused_second_order_forward");
+  KW_REQUIRE(vol && kept);
+  KW_ANGULAR_TIME_3D(ctx, "kw_fused_second_order_forward")
+  return keep_forward_xy(ctx, vol, kept);
+}
+
+kw_status kw_fused_second_order_time(kw_ctx* ctx, const float* kept, const kw_second_order_op* op, float* vol_out)
+{
+  KW_FUSED_READY(ctx);
+  KW_PROF(ctx, "fused_second_order_time");
+  KW_REQUIRE(kept && op && vol_out);
+  KW_ANGULAR_TIME_3D(ctx, "kw_fused_second_order_time")
+  KW_REQUIRE(op->dx > 0.0 && op->dy > 0.0 && op->dz > 0.0 && op->c0 > 0.0 && op->t >= 0.0);
+  KW_REQUIRE(op->absorbing == 0 || (op->a >= 0.0 && op->alpha_power >= 0.0 && op->alpha_power != 1.0));
+  float2** S = ctx->fused.s;
+  KW_TRY(zfused_second_order(ctx, reinterpret_cast<const float2*>(kept), S[0], op));
   KW_TRY(inverse_y(ctx, 1));
   XinvArgs x{};
   x.in[0]  = S[0];

@@ -1,0 +1,223 @@
+// kw_second_order.hip — device code of the exact k-space propagator (DESIGN.md "Exact k-space propagator"): an initial
+// pressure p0[z][y][x] in a homogeneous medium, lossless or power-law absorbing, carried to any time t by
+//   p(., ., .; t) = irfftn( rfftn(p0 embedded in Ez x Ey x Ex) H(|k|; t) )
+// The forward half runs once (kw_fused_second_order_forward keeps the (kx, ky, z) half-spectrum), and every output time costs
+// one z-pass that forms H in registers, one y-inverse and one x-inverse.
+//
+//   second_h               H of one bin (kwave_hip.h documents the order): shared by the fused kernel and the twin
+//   k_zfused_second_order  the z-pass of kw_fused_second_order_time (kw_fused_main.hip): lines of the kept spectrum forward
+//                          along z, times H, inverse along z into scratch array 0 — k_zfused_time's shape with a real H of
+//                          all three bin indices, no operator array and no table in memory
+//   kw_second_order_mix    the same H on the natural [Ez][Ey][Ex/2 + 1] spectrum of kw_fft_r2c_3d (rocFFT path, and the twin)
+// H is real and depends on |k| only, so the half-spectrum stays Hermitian.  Embedding, crop, sensor records and the
+// aggregates over the output times use kw_angular_time_embed, kw_plane_recon_crop and the samplers.
+#include "kw_elementwise.h"
+#include "kw_fused.hip"
+
+namespace {
+
+// what H needs besides the bin: the constants of one output time, float64 on the host
+struct SecondH
+{
+  double   dkx, dky, dkz;   // 2 pi / (E? d?)
+  double   ct;              // c0 t
+  double   ac, twoT, ym1;   // a c0^y, 2 tan(pi y / 2) (0 for y = 2), y - 1
+  float    divider;
+  uint32_t ex, ey, ez;
+  uint32_t absorbing, power;  // power: how |k|^(y-1) is formed — kPowGeneral pow(), kPowStokes y = 2: |k|, kPowHalf y = 1.5: sqrt
+};
+
+enum : uint32_t { kPowGeneral = 0, kPowStokes = 1, kPowHalf = 2 };
+
+// kx^2 + ky^2 of column ix (0 ... Ex/2) and row iy, float64
+__device__ __forceinline__ double second_kr2(double dkx, double dky, uint32_t ex, uint32_t ey, uint32_t ix, uint32_t iy)
+{
+#pragma clang fp contract(off)
+  const double kx = dkx * static_cast<double>(kw_folded(ix, ex));
+  const double ky = dky * static_cast<double>(kw_folded(iy, ey));
+  return (kx * kx) + (ky * ky);
+}
+
+// H(|k|; t) * divider of bin m along z (kwave_hip.h "Exact k-space propagator"): float64 up to the phase word and the
+// exponent of the decay, float32 from there; no contraction.
+// A real call, not inlined, as time_h (kw_angular_time.hip): unrolled over the R2 bins of a thread the two float64 square
+// roots, the float64 power and the sincosf would multiply the z-pass's registers; called, the kernel keeps the registers
+// of k_zfused's multiply plus the callee's.  The constants are read from LDS (the caller's copy): a by-value or
+// by-reference struct would go through scratch memory on every call.
+typedef const __attribute__((address_space(3))) SecondH* SecondHLds;
+__device__ __attribute__((noinline)) float second_h(SecondHLds g, double kr2, uint32_t m)
+{
+#pragma clang fp contract(off)
+  const double kz = g->dkz * static_cast<double>(kw_folded(m, g->ez));
+  const double k2 = kr2 + (kz * kz);
+  const float  divider = g->divider;
+  if (k2 == 0.0) return divider;
+  const double k  = sqrt(k2);
+  const double ct = g->ct;
+  if (g->absorbing == 0)
+  {
+    const uint32_t word = kw_phase_word((k * ct) / kTwoPi);
+    const float    ang  = static_cast<float>(static_cast<int32_t>(word)) * 1.4629180792671596e-9f;
+    return cosf(ang) * divider;
+  }
+  const uint32_t pw   = g->power;
+  const double   s    = pw == kPowStokes ? k : (pw == kPowHalf ? sqrt(k) : pow(k, g->ym1));
+  const double   gg   = g->ac * s;
+  const double   B    = (1.0 - (g->twoT * gg)) - (gg * gg);
+  const double   r    = sqrt(B);
+  const uint32_t word = kw_phase_word(((k * r) * ct) / kTwoPi);
+  const float    ang  = static_cast<float>(static_cast<int32_t>(word)) * 1.4629180792671596e-9f;
+  float sn, cs;
+  sincosf(ang, &sn, &cs);
+  const float E = exp2f(-static_cast<float>(((k * gg) * ct) * kLog2e));
+  const float q = static_cast<float>(gg / r);
+  return (E * (cs + (q * sn))) * divider;
+}
+
+// =====================================================================================================================
+// z-pass of the propagator: tile (ky = blockIdx.y, kx tile = blockIdx.x; the side array's blocks as in tile_coord) of the
+// kept spectrum, on the line-tile steps (kw_fused.hip), in k_zfused_time's order.  Its own:
+//   - the lines are read from a.in (the kept spectrum) and written to a.out (scratch array 0): a.in survives for the next
+//     output time
+//   - after the forward transform row thread (c, j) holds the bins m = j + R1 k2 along z; it forms H(kx of its column, ky,
+//     m) there and scales both parts.  Nothing is read from memory for it.  second_h is called, not inlined (see there);
+//     its constants are staged in LDS once per block.
+//   load | barrier (twiddles, gsh) | fwd_cols | barrier | fwd_rows -> H | inverse_from_regs -> store
+// =====================================================================================================================
+struct ZSecondArgs
+{
+  const float2* in;   // the kept (kx, ky, z) half-spectrum, scratch layout (rows [z][ky][P], side array at side_off)
+  float2*       out;  // scratch array 0
+  const float2* tw;
+  SecondH       g;
+  uint32_t      nxc, P, side_off;
+};
+
+template<int L> __global__ __launch_bounds__((Geo<L, nl_z(L)>::THREADS)) void k_zfused_second_order(ZSecondArgs a)
+{
+  using G = Geo<L, nl_z(L)>;
+  constexpr int R1 = G::R1, R2 = G::R2;
+  __shared__ float2  lds[G::LDSB];
+  __shared__ float2  twl[G::TWN];
+  __shared__ SecondH gsh;
+  load_twiddles<L>(twl, a.tw);
+  const LineTile t = line_tile<G>(a.nxc, a.P, a.side_off, a.g.ey, 1u);
+  if (t.tc.dead) return;
+  const int      c = t.c, j = t.j;
+  if (threadIdx.x == 0) gsh = a.g; // (published by the barrier that publishes the twiddle table)
+
+  float2 v[R1];
+  if (ACTW(R2, j)) load_lines<G>(v, a.in, t);
+  lds_barrier(); // twiddle table visible (the loads above stay in flight across it)
+
+  if (ACTW(R2, j)) fwd_cols<L, kFwd, G::NL>(v, lds, c, j, twl);
+  lds_barrier();
+  float2 X[R2];
+  if (ACTW(R1, j))
+  {
+    fwd_rows<L, kFwd, G::NL>(X, lds, c, j);
+    const SecondHLds gl = (SecondHLds)&gsh;
+    // the true column: the side array holds bin Ex/2 = a.nxc; pad lanes (never stored) take the last main column
+    const double kr2 = second_kr2(a.g.dkx, a.g.dky, a.g.ex, a.g.ey, t.tc.side ? a.nxc : t.tc.col, t.pos);
+#pragma unroll
+    for (int k2 = 0; k2 < R2; k2++)
+    {
+      const float h = second_h(gl, kr2, static_cast<uint32_t>(j + R1 * k2));
+      X[k2] = make_float2(h * X[k2].x, h * X[k2].y);
+    }
+  }
+
+  float2 r[R1];
+  inverse_from_regs<L, false, G::NL>(X, r, lds, c, j, twl);
+  store_lines<G>(a.out, t, r);
+}
+
+// the rocFFT twin: out[e] = spec[e] H on the natural [ez][ey][ex/2 + 1] half-spectrum, out of place
+__global__ __launch_bounds__(256) void k_second_order_mix(float2* __restrict__ out, const float2* __restrict__ spec, SecondH g)
+{
+  __shared__ SecondH gsh;
+  if (threadIdx.x == 0) gsh = g;
+  __syncthreads();
+  const SecondHLds gl = (SecondHLds)&gsh;
+  const uint32_t nxc = g.ex / 2 + 1;
+  const uint64_t n   = static_cast<uint64_t>(nxc) * g.ey * g.ez;
+  for (uint64_t e = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; e < n;
+       e += static_cast<uint64_t>(gridDim.x) * blockDim.x)
+  {
+    const uint32_t ix = static_cast<uint32_t>(e % nxc);
+    const uint64_t r  = e / nxc;
+    const uint32_t iy = static_cast<uint32_t>(r % g.ey), m = static_cast<uint32_t>(r / g.ey);
+    const float  h = second_h(gl, second_kr2(g.dkx, g.dky, g.ex, g.ey, ix, iy), m);
+    const float2 x = spec[e];
+    out[e] = make_float2(h * x.x, h * x.y);
+  }
+}
+
+// the constants of one output time on the grid (Ex, Ey, Ez) = (c.nx, c.ny, c.nz), float64 on the host
+SecondH time_constants(const kw_constants& c, const kw_second_order_op* op, float divider)
+{
+  SecondH g{};
+  g.dkx = kTwoPi / (static_cast<double>(c.nx) * op->dx);
+  g.dky = kTwoPi / (static_cast<double>(c.ny) * op->dy);
+  g.dkz = kTwoPi / (static_cast<double>(c.nz) * op->dz);
+  g.ct  = op->c0 * op->t;
+  g.divider = divider;
+  g.ex = c.nx; g.ey = c.ny; g.ez = c.nz;
+  g.absorbing = (op->absorbing != 0 && op->a > 0.0) ? 1u : 0u;
+  if (g.absorbing)
+  {
+    const double y = op->alpha_power;
+    g.power = y == 2.0 ? kPowStokes : (y == 1.5 ? kPowHalf : kPowGeneral);
+    g.ac   = op->a * pow(op->c0, y);
+    g.twoT = y == 2.0 ? 0.0 : 2.0 * tan(0.5 * kTwoPi * 0.5 * y);
+    g.ym1  = y - 1.0;
+  }
+  return g;
+}
+
+bool valid_op(const kw_second_order_op* op)
+{
+  if (!(op->dx > 0.0 && op->dy > 0.0 && op->dz > 0.0 && op->c0 > 0.0 && op->t >= 0.0)) return false;
+  return op->absorbing == 0 || (op->a >= 0.0 && op->alpha_power >= 0.0 && op->alpha_power != 1.0);
+}
+
+} // namespace
+
+namespace kwfused {
+
+// the z-pass of kw_fused_second_order_time: lines of `in` (the kept spectrum) to `out`, H of the time `op`
+kw_status zfused_second_order(kw_ctx* ctx, const float2* in, float2* out, const kw_second_order_op* op)
+{
+  const auto& f = ctx->fused;
+  const kw_constants& c = ctx->c;
+  KW_PROF(ctx, "k_zfused_second_order");
+  ZSecondArgs a{};
+  a.in = in; a.out = out;
+  a.tw = f.tw[2];
+  a.g  = time_constants(c, op, static_cast<float>(1.0 / (static_cast<double>(c.nx) * c.ny * c.nz)));
+  a.nxc      = f.nxm;
+  a.P        = f.P;
+  a.side_off = f.side_off;
+  return KW_LAUNCH_ZPASS((k_zfused_second_order<LEN>), c.nz, z_pass_grid(ctx, nl_z(c.nz)), a);
+}
+
+} // namespace kwfused
+
+extern "C" {
+
+kw_status kw_second_order_mix(kw_ctx* ctx, float* out_spec, const float* spec, const kw_second_order_op* op, float divider)
+{
+  KW_CHECK_CTX(ctx);
+  KW_PROF(ctx, "second_order_mix");
+  const kw_constants& c = ctx->c; // (a context without constants has no bins)
+  const uint64_t n = ctx->have_consts ? static_cast<uint64_t>(c.nx / 2 + 1) * c.ny * c.nz : 0;
+  if (n == 0) return KW_OK;
+  KW_REQUIRE(out_spec && spec && op && out_spec != spec);
+  KW_REQUIRE(valid_op(op));
+  const SecondH g = time_constants(c, op, divider);
+  hipLaunchKernelGGL(k_second_order_mix, dim3(capped_grid(ctx, n)), dim3(256), 0, ctx->stream,
+                     reinterpret_cast<float2*>(out_spec), reinterpret_cast<const float2*>(spec), g);
+  KW_LAUNCH_CHECK();
+  return KW_OK;
+}
+}

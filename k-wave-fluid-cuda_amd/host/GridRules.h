@@ -1,5 +1,5 @@
 // GridRules.h — the parameter rules that the operators with their own context share (CwParameters, AngularParameters,
-// AngularTimeParameters, PlaneReconParameters, LineReconParameters): the refusal that names the parameter, the size and sign checks, the fused
+// AngularTimeParameters, PlaneReconParameters, LineReconParameters, SecondOrderParameters): the refusal that names the parameter, the size and sign checks, the fused
 // pipeline's line lengths and the checks of an expanded grid.  No device call.
 #ifndef KW_HOST_GRID_RULES_H
 #define KW_HOST_GRID_RULES_H

@@ -1,0 +1,55 @@
+// SecondOrderParameters.h — input of the exact k-space propagator (SecondOrder): an initial pressure p0[z][y][x] on a
+// domain Nx x Ny x Nz, a homogeneous medium with optional power-law absorption, the expanded periodic grid, the sensor
+// points and the aggregates wanted, validated and completed without touching a device (DESIGN.md "Exact k-space
+// propagator").
+//
+//   default E_a (all three given sides 0): needs t_max > 0 — the smallest fast-path line length of the fused pipeline at or
+//   above M_a = N_a + ceil(c0 t_max / d_a); where an axis has none (above 1024) or with fusedKernels off, M_a itself.
+//   Given sides: all three, not below N_a, odd ones allowed; E = N is the periodic box.  t_max is then not read.
+//   tFree = min_a (E_a - N_a) d_a / c0: up to that time the result inside the domain is the free-space one.  Later times
+//   are not refused.
+//   absorption: a = alpha_coeff 100 (1e-6 / 2 pi)^y / (20 log10 e) [Np (rad/s)^-y m^-1], the time loop's conversion in
+//   float64; 0 <= y < 3, y != 1.  B = 1 - 2 g T - g^2 with g = a c0^y |k|^(y-1), T = tan(pi y / 2) (0 for y = 2) is concave
+//   in |k|^(y-1), so its minimum over the grid's bins is at the smallest non-zero or at the largest |k|: alpha_coeff is
+//   refused when B is below 1/4 at either.
+// A refusal names the parameter.
+#ifndef KW_HOST_SECOND_ORDER_PARAMETERS_H
+#define KW_HOST_SECOND_ORDER_PARAMETERS_H
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+#include "GridRules.h"
+
+class SecondOrderParameters
+{
+ public:
+  /// checks every parameter and fills in ex / ey / ez where they are 0; throws std::invalid_argument naming the parameter
+  void init(const DeviceOptions& options);
+  /// throws unless t is finite and >= 0
+  static void checkTime(double t);
+
+  DeviceOptions options;
+  size_t nx = 0, ny = 0, nz = 0;  ///< the domain
+  double dx = 0, dy = 0, dz = 0;  ///< [m]
+  double c0 = 0;                  ///< [m/s]
+  double alphaCoeff = 0;          ///< [dB / (MHz^y cm)]; 0: lossless
+  double alphaPower = 1.5;        ///< y
+  double tMax = 0;                ///< [s]; read for the default sides only
+  size_t ex = 0, ey = 0, ez = 0;  ///< expanded sides; all 0: by the rule
+  std::vector<uint64_t> sensorIndex; ///< 0-based flat indices into the domain [Nz][Ny][Nx]
+  bool   pMax = false, pMin = false, pRms = false, pFinal = false; ///< aggregates over the output times of a run
+
+  bool   fastPath = false;        ///< all three sides are fast-path lengths (and fusedKernels is on)
+  double a = 0;                   ///< [Np (rad/s)^-y m^-1]
+  double tFree = 0;               ///< [s]
+  double bSmallest = 1, bLargest = 1; ///< B at the smallest non-zero and at the largest |k| of the grid
+  size_t nDomain() const { return nx * ny * nz; }
+  size_t nExpanded() const { return ex * ey * ez; }
+  size_t nReduced() const { return (ex / 2 + 1) * ey * ez; }
+  /// B(|k|) of the completed parameters
+  double damping(double k) const;
+  /// the sensor points as indices into the expanded volume [Ez][Ey][Ex]
+  std::vector<uint64_t> expandedSensorIndex() const;
+};
+#endif

@@ -1,0 +1,209 @@
+"""Exact k-space propagator front-end (include/kwave_host.h "Exact k-space propagator" -> lib/libkwave_host.so).
+
+`SecondOrder` carries an initial pressure p0(x, y, z) in a homogeneous medium, lossless or power-law absorbing, to the
+pressure at any time t, what k-Wave's kspaceSecondOrder computes: one 3-D FFT of p0, then per output time one multiply by
+the real H(|k|; t) and one inverse transform.  There is no time loop, so there is no CFL limit and no stepping error: a
+snapshot at t = 40 us costs two transforms, a sensor record three passes per sample at any sampling interval.  The box is
+periodic; `t_free` is the time up to which the result inside the domain is the free-space one.  No CPU fallback: a missing
+library or device raises.
+
+Not built: dp0/dt as a second initial condition and time-varying sources, heterogeneous media, 2-D (Nz == 1) and its batched
+form, Z-slabs, HDF5 files and the command line, graphs, several output times per z-pass, inverse passes restricted to the
+crop or to the sensor points, particle velocity outputs.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Tuple
+
+import numpy as np
+
+from .solver import Options, _check, load_host
+
+_bound = False
+FLAGS = {"p_max": 1, "p_min": 2, "p_rms": 4, "p_final": 8}   # KWH_SECOND_ORDER_P_*
+RECORDS = ("p_raw",) + tuple(FLAGS)
+
+
+class Config(C.Structure):
+    """struct kwh_second_order_config"""
+    _fields_ = [("nx", C.c_uint64), ("ny", C.c_uint64), ("nz", C.c_uint64), ("dx", C.c_double), ("dy", C.c_double),
+                ("dz", C.c_double), ("c0", C.c_double), ("alpha_coeff", C.c_double), ("alpha_power", C.c_double),
+                ("t_max", C.c_double), ("ex", C.c_uint64), ("ey", C.c_uint64), ("ez", C.c_uint64), ("n_sensor", C.c_uint64),
+                ("sensor_index", C.POINTER(C.c_uint64)), ("flags", C.c_int32), ("pad_", C.c_int32)]
+
+
+def _lib() -> C.CDLL:
+    global _bound
+    L = load_host()
+    if not _bound:
+        L.kwh_second_order_plan.argtypes = [C.POINTER(Config), C.POINTER(Options), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]
+        L.kwh_second_order_create.argtypes = [C.POINTER(Config), C.POINTER(Options), C.POINTER(C.c_void_p)]
+        L.kwh_second_order_destroy.argtypes = [C.c_void_p]
+        L.kwh_second_order_set_p0.argtypes = [C.c_void_p, C.c_void_p]
+        L.kwh_second_order_field.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
+        L.kwh_second_order_run.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_uint64]
+        L.kwh_second_order_get.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint64]
+        L.kwh_second_order_get_scalar.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_double)]
+        L.kwh_second_order_context.restype = C.c_void_p
+        L.kwh_second_order_context.argtypes = [C.c_void_p]
+        _bound = True
+    return L
+
+
+def _config(n, d, c0, alpha_coeff, alpha_power, t_max, expanded, sensor_index, record):
+    n = tuple(int(v) for v in n)
+    d = tuple(float(v) for v in d)
+    if len(n) != 3 or len(d) != 3:
+        raise ValueError("n = (Nx, Ny, Nz) and d = (dx, dy, dz)")
+    if min(n) < 0:
+        raise ValueError(f"n must not be negative, got {n}")
+    record = (record,) if isinstance(record, str) else tuple(record)
+    unknown = [r for r in record if r not in RECORDS]
+    if unknown:
+        raise ValueError(f"record: {unknown} not among {RECORDS}")
+    c = Config()
+    c.nx, c.ny, c.nz = n
+    c.dx, c.dy, c.dz = d
+    c.c0 = float(c0)
+    c.alpha_coeff, c.alpha_power = float(alpha_coeff), float(alpha_power)
+    c.t_max = 0.0 if t_max is None else float(t_max)
+    if expanded is not None:
+        expanded = tuple(int(v) for v in expanded)
+        if len(expanded) != 3 or min(expanded) < 0:
+            raise ValueError("expanded = (Ex, Ey, Ez)")
+        c.ex, c.ey, c.ez = expanded
+    idx = np.zeros(0, dtype=np.uint64)
+    if sensor_index is not None and "p_raw" in record:
+        s = np.asarray(sensor_index).reshape(-1)
+        if s.size and s.min() < 0:
+            raise ValueError("sensor_index must not be negative")
+        idx = np.ascontiguousarray(s.astype(np.uint64))
+    c.n_sensor = int(idx.size)
+    c.sensor_index = idx.ctypes.data_as(C.POINTER(C.c_uint64)) if idx.size else None
+    c.flags = sum(FLAGS[r] for r in set(record) if r in FLAGS)
+    return c, idx
+
+
+class SecondOrder:
+    """The pressure at any time from an initial pressure p0 (Nz, Ny, Nx) (x fastest) in a homogeneous medium.
+
+    n = (Nx, Ny, Nz), d = (dx, dy, dz) [m], c0 [m/s].  alpha_coeff [dB / (MHz^y cm)] (0: lossless) and alpha_power y: power-law
+    absorption with its dispersion, underdamped modes only (a coefficient that damps a mode of the grid beyond B = 1/4 is
+    refused).  t_max [s] sizes the default expanded grid: per axis the smallest fast-path length >= N + ceil(c0 t_max / d);
+    expanded = (Ex, Ey, Ez) gives the sides instead (expanded = n: the periodic box).  sensor_index: 0-based flat indices
+    into the (Nz, Ny, Nx) array, sampled by run(); record: which of "p_raw", "p_max", "p_min", "p_rms", "p_final" run() keeps.
+
+    set_p0(p0), then field(t) -> (Nz, Ny, Nx) or run(times) -> the record (n_times, n_sensor); times in any order."""
+
+    def __init__(self, n, d, c0, alpha_coeff=0.0, alpha_power=1.5, t_max=None, expanded=None, sensor_index=None,
+                 record=("p_raw",), fused_kernels=True, device_idx=-1):
+        L = _lib()
+        c, idx = _config(n, d, c0, alpha_coeff, alpha_power, t_max, expanded, sensor_index, record)
+        o = Options()
+        o.device_idx = int(device_idx)
+        o.fused_kernels = int(bool(fused_kernels))
+        self.L, self._h = L, None
+        h = C.c_void_p()
+        _check(L.kwh_second_order_create(C.byref(c), C.byref(o), C.byref(h)))
+        self._h = h
+        self.nx, self.ny, self.nz = int(c.nx), int(c.ny), int(c.nz)
+        self.n_sensor = int(idx.size)
+        self.n_times = 0
+
+    @staticmethod
+    def plan(n, d, c0, alpha_coeff=0.0, alpha_power=1.5, t_max=None, expanded=None, sensor_index=None, record=("p_raw",),
+             fused_kernels=True) -> Tuple[Tuple[int, int, int], bool]:
+        """((Ex, Ey, Ez), fast path), validated as the constructor would, without a device"""
+        L = _lib()
+        c, _idx = _config(n, d, c0, alpha_coeff, alpha_power, t_max, expanded, sensor_index, record)
+        o = Options()
+        o.fused_kernels = int(bool(fused_kernels))
+        e, fast = (C.c_uint64 * 3)(), C.c_int32()
+        _check(L.kwh_second_order_plan(C.byref(c), C.byref(o), e, C.byref(fast)))
+        return (int(e[0]), int(e[1]), int(e[2])), bool(fast.value)
+
+    def _scalar(self, name: str) -> float:
+        v = C.c_double()
+        _check(self.L.kwh_second_order_get_scalar(self._h, name.encode(), C.byref(v)))
+        return float(v.value)
+
+    @property
+    def shape(self):
+        return (self.nz, self.ny, self.nx)
+
+    @property
+    def expanded(self) -> Tuple[int, int, int]:
+        return tuple(int(self._scalar(n)) for n in ("Ex", "Ey", "Ez"))
+
+    @property
+    def t_free(self) -> float:
+        """[s]: up to this time nothing has wrapped around the periodic box into the domain"""
+        return self._scalar("t_free")
+
+    @property
+    def fused(self) -> bool:
+        return self._scalar("fused_pipeline") != 0.0
+
+    @property
+    def runs(self) -> int:
+        return int(self._scalar("runs"))
+
+    @property
+    def ctx(self):
+        return C.c_void_p(self.L.kwh_second_order_context(self._h))
+
+    def _get(self, name: str, shape) -> np.ndarray:
+        out = np.empty(shape, dtype=np.float32)
+        _check(self.L.kwh_second_order_get(self._h, name.encode(), out.ctypes.data, out.size))
+        return out
+
+    def set_p0(self, p0):
+        """embed, transform and keep the initial pressure; may be called again"""
+        a = np.asarray(p0, dtype=np.float32)
+        if a.shape != self.shape:
+            raise ValueError(f"p0 must be (Nz, Ny, Nx) = {self.shape}, got {a.shape}")
+        a = np.ascontiguousarray(a)
+        _check(self.L.kwh_second_order_set_p0(self._h, a.ctypes.data))
+
+    def field(self, t: float) -> np.ndarray:
+        """the pressure at time t [s] on the domain: float32 (Nz, Ny, Nx)"""
+        out = np.empty(self.shape, dtype=np.float32)
+        _check(self.L.kwh_second_order_field(self._h, float(t), out.ctypes.data))
+        return out
+
+    def run(self, times) -> np.ndarray:
+        """every time of `times` [s] in the given order; returns the record float32 (n_times, n_sensor)"""
+        ta = np.ascontiguousarray(np.asarray(times, dtype=np.float64).reshape(-1))
+        _check(self.L.kwh_second_order_run(self._h, ta.ctypes.data_as(C.POINTER(C.c_double)), ta.size))
+        self.n_times = int(ta.size)
+        if self.n_sensor == 0:
+            return np.empty((self.n_times, 0), dtype=np.float32)
+        return self._get("p_raw", (self.n_times, self.n_sensor))
+
+    def p_max(self) -> np.ndarray:
+        """max over the output times of the last run"""
+        return self._get("p_max", self.shape)
+
+    def p_min(self) -> np.ndarray:
+        """min over the output times of the last run"""
+        return self._get("p_min", self.shape)
+
+    def p_rms(self) -> np.ndarray:
+        """root mean square over the output times of the last run"""
+        return self._get("p_rms", self.shape)
+
+    def p_final(self) -> np.ndarray:
+        """the field at the last output time of the last run"""
+        return self._get("p_final", self.shape)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.L.kwh_second_order_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

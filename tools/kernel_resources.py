@@ -27,11 +27,12 @@ def main():
     extra = sys.argv[2:]
     with tempfile.TemporaryDirectory() as tmp, concurrent.futures.ThreadPoolExecutor(8) as pool:
         # the fused pipeline's code objects, and those of the CW propagator and the angular-spectrum projectors (the pair
-        # z-pass, the CW projector's y-inverse, the time-domain projector's z-pass, the plane reconstruction's z-pass and
+        # z-pass, the CW projector's y-inverse, the time-domain projector's z-pass, the exact propagator's z-pass, the plane reconstruction's z-pass and
         # the line reconstruction's pass along t are kernels of that pipeline)
         srcs = sorted(glob.glob(os.path.join(CSRC, "kw_fused_*.hip"))) + [os.path.join(CSRC, "kw_cw.hip"),
                                                                           os.path.join(CSRC, "kw_angular.hip"),
                                                                           os.path.join(CSRC, "kw_angular_time.hip"),
+                                                                          os.path.join(CSRC, "kw_second_order.hip"),
                                                                           os.path.join(CSRC, "kw_plane_recon.hip"),
                                                                           os.path.join(CSRC, "kw_line_recon.hip")]
         texts = list(pool.map(compile_one, [(length, src, tmp, extra) for src in srcs]))
