@@ -18,24 +18,16 @@
 
 namespace {
 
-// what H needs besides the bin: a plain-data copy of the plane's constants (ZTimeArgs carries the same)
+// what H needs besides the bin: the constants of one plane, float64 on the host
 struct TimeH
 {
-  const double* ak;
-  double        dkx, dky, dk, z, cfac;
-  float         zl2e, divider;
+  const double* ak;           // Lt/2 + 1 values alpha(m') k(m') log2(e), or NULL
+  double        dkx, dky, dk; // 2 pi / (Ex dx), 2 pi / (Ey dy), 2 pi / (Lt dt c0)
+  double        z, cfac;      // plane distance; D^2/2 / (D^2/2 + z^2)
+  float         zl2e, divider; // float(z log2(e)); 1 / (Ex Ey Lt), or the twin's
   uint32_t      ex, ey, lt;
   uint32_t      restriction, retarded;
 };
-
-// kx^2 + ky^2 of column ix (0 ... Ex/2) and row iy, float64
-__device__ __forceinline__ double time_kr2(double dkx, double dky, uint32_t ex, uint32_t ey, uint32_t ix, uint32_t iy)
-{
-#pragma clang fp contract(off)
-  const double kx = dkx * static_cast<double>(kw_folded(ix, ex));
-  const double ky = dky * static_cast<double>(kw_folded(iy, ey));
-  return (kx * kx) + (ky * ky);
-}
 
 // H(kr2, m) * divider (kwave_hip.h "time-domain angular-spectrum projector"): float64 up to the phase word and the
 // restriction test, float32 from there; no contraction.
@@ -76,44 +68,42 @@ __device__ __attribute__((noinline)) float2 time_h(TimeHLds g, double kr2, uint3
   return make_float2(hr, hi);
 }
 
-__device__ __forceinline__ float2 time_mul(const float2& x, float hr, float hi)
-{
-#pragma clang fp contract(off)
-  return make_float2((hr * x.x) - (hi * x.y), (hr * x.y) + (hi * x.x));
-}
-
 // =====================================================================================================================
 // z-pass of the projector: tile (ky = blockIdx.y, kx tile = blockIdx.x; the side array's blocks as in tile_coord) of the
 // kept spectrum, on the line-tile steps (kw_fused.hip).  Its own:
 //   - the lines are read from a.in (the kept spectrum) and written to a.out (scratch array 0): a.in survives for the next
 //     plane
 //   - after the forward transform row thread (c, j) holds the bins m = j + R1 k2; it forms H(kx of its column, ky, m)
-//     there and multiplies.  Nothing but the Lt/2 + 1 values of a.ak is read for it.  time_h is called, not inlined (see
-//     there); its constants and a.ak are staged in LDS once per block.
+//     there and multiplies.  Nothing but the Lt/2 + 1 values of a.g.ak is read for it.  time_h is called, not inlined (see
+//     there); its constants and a.g.ak are staged in LDS once per block, and the staged copy points at the staged values.
 //   load | barrier (twiddles, aks, gsh) | fwd_cols | barrier | fwd_rows -> H | inverse_from_regs -> store
 // =====================================================================================================================
+struct ZTimeArgs
+{
+  const float2* in;   // the kept (kx, ky, t) half-spectrum, scratch layout (rows [t][ky][P], side array at side_off)
+  float2*       out;  // scratch array 0
+  PassGeo       geo;
+  TimeH         g;
+};
+
 template<int L> __global__ __launch_bounds__((Geo<L, nl_z(L)>::THREADS)) void k_zfused_time(ZTimeArgs a)
 {
   using G = Geo<L, nl_z(L)>;
   constexpr int R1 = G::R1, R2 = G::R2;
   __shared__ float2 lds[G::LDSB];
   __shared__ float2 twl[G::TWN];
-  __shared__ double aks[L / 2 + 1]; // a.ak, read once per block instead of once per bin
+  __shared__ double aks[L / 2 + 1]; // a.g.ak, read once per block instead of once per bin
   __shared__ TimeH  gsh;
-  load_twiddles<L>(twl, a.tw);
-  const LineTile t      = line_tile<G>(a.nxc, a.P, a.side_off, a.ny, 1u);
+  load_twiddles<L>(twl, a.geo.tw);
+  const LineTile t      = line_tile<G>(a.geo.nxc, a.geo.P, a.geo.side_off, a.g.ey, 1u);
   if (t.tc.dead) return;
   const int      c      = t.c, j = t.j;
-  if (a.ak != nullptr)
-    for (int e = threadIdx.x; e < L / 2 + 1; e += blockDim.x) aks[e] = a.ak[e];
+  if (a.g.ak != nullptr)
+    for (int e = threadIdx.x; e < L / 2 + 1; e += blockDim.x) aks[e] = a.g.ak[e];
   if (threadIdx.x == 0)
   {
-    TimeH g;
-    g.ak = (a.ak != nullptr) ? aks : nullptr;
-    g.dkx = a.dkx; g.dky = a.dky; g.dk = a.dk; g.z = a.z; g.cfac = a.cfac;
-    g.zl2e = a.zl2e; g.divider = a.divider;
-    g.ex = a.ex; g.ey = a.ny; g.lt = static_cast<uint32_t>(L);
-    g.restriction = a.restriction; g.retarded = a.retarded;
+    TimeH g = a.g;
+    g.ak = (a.g.ak != nullptr) ? aks : nullptr;
     gsh = g;
   } // (both published by the barrier that publishes the twiddle table)
 
@@ -128,13 +118,13 @@ template<int L> __global__ __launch_bounds__((Geo<L, nl_z(L)>::THREADS)) void k_
   {
     fwd_rows<L, kFwd, G::NL>(X, lds, c, j);
     const TimeHLds gl = (TimeHLds)&gsh;
-    // the true column: the side array holds bin Ex/2 = a.nxc; pad lanes (never stored) take the last main column
-    const double kr2 = time_kr2(a.dkx, a.dky, a.ex, a.ny, t.tc.side ? a.nxc : t.tc.col, t.pos);
+    // the true column: the side array holds bin Ex/2 = a.geo.nxc; pad lanes (never stored) take the last main column
+    const double kr2 = kw_kr2(a.g.dkx, a.g.dky, a.g.ex, a.g.ey, t.tc.side ? a.geo.nxc : t.tc.col, t.pos);
 #pragma unroll
     for (int k2 = 0; k2 < R2; k2++)
     {
       const float2 h = time_h(gl, kr2, static_cast<uint32_t>(j + R1 * k2));
-      X[k2] = time_mul(X[k2], h.x, h.y);
+      X[k2] = kw_times(X[k2], h.x, h.y);
     }
   }
 
@@ -146,21 +136,7 @@ template<int L> __global__ __launch_bounds__((Geo<L, nl_z(L)>::THREADS)) void k_
 // the rocFFT twin: out[e] = spec[e] H on the natural [lt][ey][ex/2 + 1] half-spectrum, out of place
 __global__ __launch_bounds__(256) void k_angular_time_mix(float2* __restrict__ out, const float2* __restrict__ spec, TimeH g)
 {
-  __shared__ TimeH gsh;
-  if (threadIdx.x == 0) gsh = g;
-  __syncthreads();
-  const TimeHLds gl = (TimeHLds)&gsh;
-  const uint32_t nxc = g.ex / 2 + 1;
-  const uint64_t n   = static_cast<uint64_t>(nxc) * g.ey * g.lt;
-  for (uint64_t e = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; e < n;
-       e += static_cast<uint64_t>(gridDim.x) * blockDim.x)
-  {
-    const uint32_t ix = static_cast<uint32_t>(e % nxc);
-    const uint64_t r  = e / nxc;
-    const uint32_t iy = static_cast<uint32_t>(r % g.ey), m = static_cast<uint32_t>(r / g.ey);
-    const float2 h = time_h(gl, time_kr2(g.dkx, g.dky, g.ex, g.ey, ix, iy), m);
-    out[e] = time_mul(spec[e], h.x, h.y);
-  }
+  half_spectrum_mix(out, spec, g, g.lt, [](TimeHLds gl, double kr2, uint32_t m) { return time_h(gl, kr2, m); });
 }
 
 // max_t / min_t and the series of the domain crop.  A block takes a tile of TP * V consecutive points (y, x) of the
@@ -251,22 +227,12 @@ namespace kwfused {
 // the z-pass of kw_fused_angular_time_plane: lines of `in` (the kept spectrum) to `out`, H of the plane `op`
 kw_status zfused_time(kw_ctx* ctx, const float2* in, float2* out, const kw_angular_time_op* op)
 {
-  const auto& f = ctx->fused;
   const kw_constants& c = ctx->c;
   KW_PROF(ctx, "k_zfused_time");
-  const TimeH g = plane_constants(c, op, static_cast<float>(1.0 / (static_cast<double>(c.nx) * c.ny * c.nz)));
   ZTimeArgs a{};
   a.in = in; a.out = out;
-  a.tw = f.tw[2];
-  a.ak = g.ak; a.dkx = g.dkx; a.dky = g.dky; a.dk = g.dk; a.z = g.z; a.cfac = g.cfac;
-  a.zl2e = g.zl2e; a.divider = g.divider;
-  a.restriction = g.restriction; a.retarded = g.retarded;
-  a.nxc      = f.nxm;
-  a.P        = f.P;
-  a.ex       = c.nx;
-  a.ny       = c.ny;
-  a.nz       = c.nz;
-  a.side_off = f.side_off;
+  a.geo = pass_geo(ctx, 2);
+  a.g   = plane_constants(c, op, static_cast<float>(1.0 / (static_cast<double>(c.nx) * c.ny * c.nz)));
   return KW_LAUNCH_ZPASS((k_zfused_time<LEN>), c.nz, z_pass_grid(ctx, nl_z(c.nz)), a);
 }
 
@@ -276,12 +242,7 @@ extern "C" {
 
 kw_status kw_angular_time_mix(kw_ctx* ctx, float* out_spec, const float* spec, const kw_angular_time_op* op, float divider)
 {
-  KW_CHECK_CTX(ctx);
-  KW_PROF(ctx, "angular_time_mix");
-  const kw_constants& c = ctx->c; // (a context without constants has no bins)
-  const uint64_t n = ctx->have_consts ? static_cast<uint64_t>(c.nx / 2 + 1) * c.ny * c.nz : 0;
-  if (n == 0) return KW_OK;
-  KW_REQUIRE(out_spec && spec && op && out_spec != spec);
+  KW_MIX_ENTRY(ctx, "angular_time_mix", c, n, out_spec, spec, op);
   KW_REQUIRE(c.nx % 2 == 0 && c.nz % 2 == 0);
   KW_REQUIRE(op->dx > 0.0 && op->dy > 0.0 && op->dt > 0.0 && op->c0 > 0.0 && op->z >= 0.0);
   const TimeH g = plane_constants(c, op, divider);

@@ -146,30 +146,12 @@ struct AngArgs
   float           divider; // 1 / (Ex Ey)
 };
 
-// the z-pass of the time-domain angular-spectrum projector (kw_angular_time.hip): H of one plane, formed per bin
-struct ZTimeArgs
+// the geometry of a pass over the scratch layout: what the operator passes (k_zfused_time, k_zfused_second_order,
+// k_zfused_recon, k_yfused_line_recon) take from the context (pass_geo)
+struct PassGeo
 {
-  const float2* in;   // the kept (kx, ky, t) half-spectrum, scratch layout (rows [t][ky][P], side array at side_off)
-  float2*       out;  // scratch array 0
-  const float2* tw;
-  const double* ak;   // Lt/2 + 1 values alpha(m') k(m') log2(e), or NULL
-  double        dkx, dky, dk; // 2 pi / (Ex dx), 2 pi / (Ey dy), 2 pi / (Lt dt c0)
-  double        z, cfac;      // plane distance; D^2/2 / (D^2/2 + z^2)
-  float         zl2e;         // float(z log2(e))
-  float         divider;      // 1 / (Ex Ey Lt)
-  uint32_t      nxc, P, ex, ny, nz, side_off; // ex = Ex (the bin counts along x)
-  uint32_t      restriction, retarded;
-};
-
-// the z-pass of the k-space plane reconstruction (kw_plane_recon.hip): weight and gather along the line, formed per bin
-struct ZReconArgs
-{
-  float2*       s;    // scratch array 0, in place (rows [t][ky][P], side array at side_off)
-  const float2* tw;
-  double        dkx, dky, dk2; // 2 pi / (Ex dx), 2 pi / (Ey dy), (2 pi / (Lt dt c0))^2
-  float         scale;         // 2 / (Ex Ey Lt)
-  uint32_t      nxc, P, ex, ny, nz, side_off; // ex = Ex (the bin counts along x)
-  uint32_t      nearest;
+  const float2* tw;                 // the twiddle table of the line's axis
+  uint32_t      nxc, P, side_off;   // columns of a row, row pitch, element offset of the x-Nyquist side array (0: none)
 };
 
 struct XshiftArgs
@@ -2020,6 +2002,12 @@ inline dim3 z_pass_grid(const kw_ctx* ctx, uint32_t nl, uint32_t nz = 1)
 {
   const auto& f = ctx->fused;
   return dim3((f.P + nl - 1u) / nl + (f.side_off != 0 ? 1u : 0u), f.nyl, nz);
+}
+// the geometry of an operator pass along `axis` (1: y, 2: z) over the context's scratch layout
+inline PassGeo pass_geo(const kw_ctx* ctx, int axis)
+{
+  const auto& f = ctx->fused;
+  return PassGeo{ f.tw[axis], f.nxm, f.P, f.side_off };
 }
 // Launch of z-pass kernel K at the runtime line length len (a kw_status): K names the kernel with LEN for its length,
 // as in  return KW_LAUNCH_ZPASS((k_zfused_pair<LEN>), f.nz_global, z_pass_grid(ctx, nl_z(f.nz_global)), a);

@@ -1336,6 +1336,24 @@ kw_status kw_fused_shift_velocity(kw_ctx* ctx, int axis, const float* in, float*
   return launch_zshift(ctx, in, out, filter, 2, c.nz, c.ny, c.ny, 1);
 }
 
+// The stages that run on one GPU and a 3-D grid only refuse anything else here; `what` names what the stage works on.
+static kw_status single_gpu_only(const kw_ctx* ctx, const char* name, const char* what = "3-D only")
+{
+  if (!(ctx->fused.slab || ctx->fused.two_d)) return KW_OK;
+  kw_set_error("%s: single GPU and %s (no Z-slabs, no Nz == 1)", name, what);
+  return KW_ERR_INVALID;
+}
+
+// scratch array 0 -> the real array `out`: the storing x-inverse, after the y-inverse where the stage has one
+static kw_status store_scratch0(kw_ctx* ctx, float* out, bool y_inverse = true)
+{
+  if (y_inverse) KW_TRY(inverse_y(ctx, 1));
+  XinvArgs x{};
+  x.in[0]  = ctx->fused.s[0];
+  x.out[0] = out;
+  return launch_xinv<EPI_STORE>(ctx, 1, x);
+}
+
 // scaleSource body (KSpaceFirstOrderSolver.cpp:2346-2351): scaled <- ifftn(sourceKappa*fftn(scaled))/N, in place
 kw_status kw_fused_scale_source(kw_ctx* ctx, float* scaled, const float* source_kappa_padded)
 {
@@ -1349,12 +1367,7 @@ kw_status kw_fused_scale_source(kw_ctx* ctx, float* scaled, const float* source_
   z.in[0] = S[0]; z.out[0] = S[0];
   z.op[0] = source_kappa_padded;
   KW_TRY(launch_zfused<Z_SOURCE>(ctx, 1, z));
-  KW_TRY(inverse_y(ctx, 1));
-  XinvArgs x{};
-  x.in[0] = S[0];
-  x.out[0] = scaled;
-  KW_TRY(launch_xinv<EPI_STORE>(ctx, 1, x));
-  return KW_OK;
+  return store_scratch0(ctx, scaled);
 }
 
 // CW field propagator (kw_cw.hip): the complex field re + i im through one 3-D round trip with the complex operator
@@ -1366,11 +1379,7 @@ kw_status kw_fused_cw_pair(kw_ctx* ctx, float* re, float* im, const float* g_re_
   KW_FUSED_READY(ctx);
   KW_PROF(ctx, "fused_cw_pair");
   KW_REQUIRE(re && im && g_re_padded && g_im_padded && re != im);
-  if (ctx->fused.slab || ctx->fused.two_d)
-  {
-    kw_set_error("kw_fused_cw_pair: single GPU and 3-D only (no Z-slabs, no Nz == 1)");
-    return KW_ERR_INVALID;
-  }
+  KW_TRY(single_gpu_only(ctx, __func__));
   float2** S = ctx->fused.s;
   const float* in2[2] = { re, im };
   KW_TRY(forward_xy(ctx, 2, in2));
@@ -1400,19 +1409,12 @@ kw_status kw_fused_angular_elems(kw_ctx* ctx, size_t* out)
   return KW_OK;
 }
 
-#define KW_ANGULAR_3D(ctx, name)                                                                                       \
-  if ((ctx)->fused.slab || (ctx)->fused.two_d)                                                                         \
-  {                                                                                                                    \
-    kw_set_error(name ": single GPU and a chunk of planes only (no Z-slabs, no Nz == 1)");                             \
-    return KW_ERR_INVALID;                                                                                             \
-  }
-
 kw_status kw_fused_angular_forward(kw_ctx* ctx, const float* re, const float* im, float* spec_re, float* spec_im)
 {
   KW_FUSED_READY(ctx);
   KW_PROF(ctx, "fused_angular_forward");
   KW_REQUIRE(re && im && spec_re && spec_im && spec_re != spec_im);
-  KW_ANGULAR_3D(ctx, "kw_fused_angular_forward")
+  KW_TRY(single_gpu_only(ctx, __func__, "a chunk of planes only"));
   const kw_constants& c = ctx->c;
   const auto& f = ctx->fused;
   const uint32_t rows_per_tile = 2u * static_cast<uint32_t>(nl_x(c.nx));
@@ -1443,7 +1445,7 @@ kw_status kw_fused_angular_planes(kw_ctx* ctx, const float* spec_re, const float
   KW_PROF(ctx, "fused_angular_planes");
   KW_REQUIRE(spec_re && spec_im && tables_imported && re && im && re != im);
   KW_REQUIRE(static_cast<uint64_t>(j0) + ctx->c.nz <= (1ull << 31));
-  KW_ANGULAR_3D(ctx, "kw_fused_angular_planes")
+  KW_TRY(single_gpu_only(ctx, __func__, "a chunk of planes only"));
   float2** S = ctx->fused.s;
   AngArgs a{};
   a.in[0]  = reinterpret_cast<const float2*>(spec_re);
@@ -1459,23 +1461,18 @@ kw_status kw_fused_angular_planes(kw_ctx* ctx, const float* spec_re, const float
   KW_TRY(launch_xinv<EPI_STORE>(ctx, 2, x));
   return KW_OK;
 }
-#undef KW_ANGULAR_3D
 
 // Time-domain angular-spectrum projector (kw_angular_time.hip).  The record [Lt][Ey][Ex] is transformed along x and y once
 // and the (kx, ky, t) half-spectrum kept aside; every plane is kw_fused_scale_source's second half with k_zfused_time as
 // its z-pass, reading the kept spectrum.
-#define KW_ANGULAR_TIME_3D(ctx, name)                                                                                  \
-  if ((ctx)->fused.slab || (ctx)->fused.two_d)                                                                         \
-  {                                                                                                                    \
-    kw_set_error(name ": single GPU and 3-D only (no Z-slabs, no Nz == 1)");                                           \
-    return KW_ERR_INVALID;                                                                                             \
-  }
+// complex values of a kept half-spectrum: scratch array 0, side array included
+static size_t kept_elems(const kw_ctx* ctx) { return static_cast<size_t>(ctx->fused.Palloc) * ctx->c.ny * ctx->c.nz; }
 
 kw_status kw_fused_angular_time_elems(kw_ctx* ctx, size_t* out)
 {
   KW_FUSED_READY(ctx);
   KW_REQUIRE(out != nullptr);
-  *out = static_cast<size_t>(ctx->fused.Palloc) * ctx->c.ny * ctx->c.nz;
+  *out = kept_elems(ctx);
   return KW_OK;
 }
 
@@ -1485,8 +1482,7 @@ static kw_status keep_forward_xy(kw_ctx* ctx, const float* vol, float* kept)
 {
   const float* in1[1] = { vol };
   KW_TRY(forward_xy(ctx, 1, in1));
-  const size_t elems = static_cast<size_t>(ctx->fused.Palloc) * ctx->c.ny * ctx->c.nz;
-  KW_HIP(hipMemcpyAsync(kept, ctx->fused.s[0], elems * sizeof(float2), hipMemcpyDeviceToDevice, ctx->stream));
+  KW_HIP(hipMemcpyAsync(kept, ctx->fused.s[0], kept_elems(ctx) * sizeof(float2), hipMemcpyDeviceToDevice, ctx->stream));
   return KW_OK;
 }
 
@@ -1495,7 +1491,7 @@ kw_status kw_fused_angular_time_forward(kw_ctx* ctx, const float* vol, float* ke
   KW_FUSED_READY(ctx);
   KW_PROF(ctx, "fused_angular_time_forward");
   KW_REQUIRE(vol && kept);
-  KW_ANGULAR_TIME_3D(ctx, "kw_fused_angular_time_forward")
+  KW_TRY(single_gpu_only(ctx, __func__));
   return keep_forward_xy(ctx, vol, kept);
 }
 
@@ -1504,16 +1500,10 @@ kw_status kw_fused_angular_time_plane(kw_ctx* ctx, const float* kept, const kw_a
   KW_FUSED_READY(ctx);
   KW_PROF(ctx, "fused_angular_time_plane");
   KW_REQUIRE(kept && op && vol_out);
-  KW_ANGULAR_TIME_3D(ctx, "kw_fused_angular_time_plane")
+  KW_TRY(single_gpu_only(ctx, __func__));
   KW_REQUIRE(op->dx > 0.0 && op->dy > 0.0 && op->dt > 0.0 && op->c0 > 0.0 && op->z >= 0.0);
-  float2** S = ctx->fused.s;
-  KW_TRY(zfused_time(ctx, reinterpret_cast<const float2*>(kept), S[0], op));
-  KW_TRY(inverse_y(ctx, 1));
-  XinvArgs x{};
-  x.in[0]  = S[0];
-  x.out[0] = vol_out;
-  KW_TRY(launch_xinv<EPI_STORE>(ctx, 1, x));
-  return KW_OK;
+  KW_TRY(zfused_time(ctx, reinterpret_cast<const float2*>(kept), ctx->fused.s[0], op));
+  return store_scratch0(ctx, vol_out);
 }
 
 // Exact k-space propagator (kw_second_order.hip): the projector's shape with the volume's own z axis — the (kx, ky, z)
@@ -1523,7 +1513,7 @@ kw_status kw_fused_second_order_elems(kw_ctx* ctx, size_t* out)
 {
   KW_FUSED_READY(ctx);
   KW_REQUIRE(out != nullptr);
-  *out = static_cast<size_t>(ctx->fused.Palloc) * ctx->c.ny * ctx->c.nz;
+  *out = kept_elems(ctx);
   return KW_OK;
 }
 
@@ -1532,7 +1522,7 @@ kw_status kw_fused_second_order_forward(kw_ctx* ctx, const float* vol, float* ke
   KW_FUSED_READY(ctx);
   KW_PROF(ctx, "fused_second_order_forward");
   KW_REQUIRE(vol && kept);
-  KW_ANGULAR_TIME_3D(ctx, "kw_fused_second_order_forward")
+  KW_TRY(single_gpu_only(ctx, __func__));
   return keep_forward_xy(ctx, vol, kept);
 }
 
@@ -1541,19 +1531,12 @@ kw_status kw_fused_second_order_time(kw_ctx* ctx, const float* kept, const kw_se
   KW_FUSED_READY(ctx);
   KW_PROF(ctx, "fused_second_order_time");
   KW_REQUIRE(kept && op && vol_out);
-  KW_ANGULAR_TIME_3D(ctx, "kw_fused_second_order_time")
+  KW_TRY(single_gpu_only(ctx, __func__));
   KW_REQUIRE(op->dx > 0.0 && op->dy > 0.0 && op->dz > 0.0 && op->c0 > 0.0 && op->t >= 0.0);
   KW_REQUIRE(op->absorbing == 0 || (op->a >= 0.0 && op->alpha_power >= 0.0 && op->alpha_power != 1.0));
-  float2** S = ctx->fused.s;
-  KW_TRY(zfused_second_order(ctx, reinterpret_cast<const float2*>(kept), S[0], op));
-  KW_TRY(inverse_y(ctx, 1));
-  XinvArgs x{};
-  x.in[0]  = S[0];
-  x.out[0] = vol_out;
-  KW_TRY(launch_xinv<EPI_STORE>(ctx, 1, x));
-  return KW_OK;
+  KW_TRY(zfused_second_order(ctx, reinterpret_cast<const float2*>(kept), ctx->fused.s[0], op));
+  return store_scratch0(ctx, vol_out);
 }
-#undef KW_ANGULAR_TIME_3D
 
 // k-space plane reconstruction (kw_plane_recon.hip): kw_fused_scale_source's round trip with k_zfused_recon as its z-pass —
 // the weight and the gather from w to kz happen along the line the z-pass holds in LDS.
@@ -1562,22 +1545,12 @@ kw_status kw_fused_plane_recon(kw_ctx* ctx, const float* vol_even, const kw_plan
   KW_FUSED_READY(ctx);
   KW_PROF(ctx, "fused_plane_recon");
   KW_REQUIRE(vol_even && op && vol_out);
-  if (ctx->fused.slab || ctx->fused.two_d)
-  {
-    kw_set_error("kw_fused_plane_recon: single GPU and 3-D only (no Z-slabs, no Nz == 1)");
-    return KW_ERR_INVALID;
-  }
+  KW_TRY(single_gpu_only(ctx, __func__));
   KW_REQUIRE(op->dx > 0.0 && op->dy > 0.0 && op->dt > 0.0 && op->c0 > 0.0 && (op->interp == 0 || op->interp == 1));
-  float2** S = ctx->fused.s;
   const float* in1[1] = { vol_even };
   KW_TRY(forward_xy(ctx, 1, in1));
-  KW_TRY(zfused_recon(ctx, S[0], op));
-  KW_TRY(inverse_y(ctx, 1));
-  XinvArgs x{};
-  x.in[0]  = S[0];
-  x.out[0] = vol_out;
-  KW_TRY(launch_xinv<EPI_STORE>(ctx, 1, x));
-  return KW_OK;
+  KW_TRY(zfused_recon(ctx, ctx->fused.s[0], op));
+  return store_scratch0(ctx, vol_out);
 }
 
 // Batched k-space line reconstruction (kw_line_recon.hip), frames mode: the x-forward over all Ny * Nz rows, ONE launch of
@@ -1598,11 +1571,7 @@ kw_status kw_fused_line_recon(kw_ctx* ctx, const float* vol_even, const kw_plane
   const float* in1[1] = { vol_even };
   KW_TRY(launch_xfwd(ctx, 1, in1, S));
   KW_TRY(yfused_line_recon(ctx, S[0], op));
-  XinvArgs x{};
-  x.in[0]  = S[0];
-  x.out[0] = vol_out;
-  KW_TRY(launch_xinv<EPI_STORE>(ctx, 1, x));
-  return KW_OK;
+  return store_scratch0(ctx, vol_out, false);
 }
 
 // Pass-level probe for tuning (tools/probe_passes.py): launches ONE pass over the scratch arrays, no physics.

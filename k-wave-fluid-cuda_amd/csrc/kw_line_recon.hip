@@ -9,8 +9,6 @@
 //                        array 0 along t (the pipeline's y), tile position = the frame; k_zfused_recon's body
 //   kw_line_recon_mix    the same on the natural [F][Lt][Ey/2 + 1] spectra of kw_fft_r2c_frames (rocFFT path, and the twin)
 //   kw_line_recon_embed / _crop   the mirrored embedding of the frames; the first rows of every image, clamped on request
-#include "kw_elementwise.h"
-#include "kw_fused.hip"
 #include "kw_recon_device.h"
 
 namespace {
@@ -41,8 +39,8 @@ template<int L> __global__ __launch_bounds__((Geo<L, nl_z(L)>::THREADS)) void k_
   constexpr uint32_t M = L / 2;
   __shared__ float2 lds[G::LDSB];
   __shared__ float2 twl[G::TWN];
-  load_twiddles<L>(twl, a.tw);
-  const LineTile t      = line_tile<G>(a.nxc, a.P, a.side_off, 1u, a.ny);
+  load_twiddles<L>(twl, a.geo.tw);
+  const LineTile t      = line_tile<G>(a.geo.nxc, a.geo.P, a.geo.side_off, 1u, a.ny);
   if (t.tc.dead) return;
   const int      c      = t.c, j = t.j;
 
@@ -53,8 +51,8 @@ template<int L> __global__ __launch_bounds__((Geo<L, nl_z(L)>::THREADS)) void k_
   if (ACTW(R2, j)) fwd_cols<L, kFwd, G::NL>(v, lds, c, j, twl);
   lds_barrier();
   float2 X[R2];
-  // the true column: the side array holds bin Ey/2 = a.nxc; pad lanes (never stored) take the last main column
-  const double rho2 = line_rho2(a.dkx, a.dk2, a.ex, t.tc.side ? a.nxc : t.tc.col);
+  // the true column: the side array holds bin Ey/2 = a.geo.nxc; pad lanes (never stored) take the last main column
+  const double rho2 = line_rho2(a.dkx, a.dk2, a.ex, t.tc.side ? a.geo.nxc : t.tc.col);
   if (ACTW(R1, j))
   {
     fwd_rows<L, kFwd, G::NL>(X, lds, c, j);
@@ -116,21 +114,9 @@ __global__ __launch_bounds__(256) void k_line_recon_mix(float2* __restrict__ out
     const uint32_t iy = static_cast<uint32_t>(e % nyc);
     const uint64_t r  = e / nyc;
     const uint32_t m  = static_cast<uint32_t>(r % g.lt);
-    const uint64_t col = e - static_cast<uint64_t>(m) * nyc; // bin 0 of the line
-    const uint32_t mp  = m <= M ? m : g.lt - m;
+    const uint32_t mp = m <= M ? m : g.lt - m;
     const double rho2 = line_rho2(g.dks, g.dk2, g.ey, iy);
-    const double f    = recon_f(rho2, mp);
-    float2 res = make_float2(0.f, 0.f);
-    if (f <= static_cast<double>(M))
-    {
-      const uint32_t i0 = static_cast<uint32_t>(f);
-      const uint32_t i1 = i0 + 1u <= M ? i0 + 1u : M;
-      const float    al = static_cast<float>(f - static_cast<double>(i0));
-      const float2   t0 = recon_scale(spec[col + static_cast<uint64_t>(i0) * nyc], recon_w(rho2, i0, g.scale));
-      const float2   t1 = recon_scale(spec[col + static_cast<uint64_t>(i1) * nyc], recon_w(rho2, i1, g.scale));
-      res = recon_pick(t0, t1, al, nearest);
-    }
-    out[e] = res;
+    out[e] = recon_gather(spec + (e - static_cast<uint64_t>(m) * nyc), nyc, rho2, mp, M, g.scale, nearest); // from bin 0 of the line
   }
 }
 
@@ -174,16 +160,12 @@ kw_status yfused_line_recon(kw_ctx* ctx, float2* s, const kw_plane_recon_op* op)
   const double dk = kTwoPi / (static_cast<double>(c.ny) * op->dt * op->c0);
   ZReconArgs a{};
   a.s   = s;
-  a.tw  = f.tw[1];
+  a.geo = pass_geo(ctx, 1);
   a.dkx = kTwoPi / (static_cast<double>(c.nx) * op->dx);
   a.dk2 = dk * dk;
   a.scale    = static_cast<float>(2.0 / (static_cast<double>(c.nx) * c.ny));
-  a.nxc      = f.nxm;
-  a.P        = f.P;
   a.ex       = c.nx;
   a.ny       = c.ny;
-  a.nz       = c.nz;
-  a.side_off = f.side_off;
   a.nearest  = op->interp == 1 ? 1u : 0u;
   // the tiles of a row, one more tile index for the side array's blocks, by the frames
   const dim3 grid(z_tiles(f.P, c.ny) + (f.side_off != 0 ? 1u : 0u), c.nz, 1);
@@ -196,12 +178,7 @@ extern "C" {
 
 kw_status kw_line_recon_mix(kw_ctx* ctx, float* out_spec, const float* spec, const kw_plane_recon_op* op, float scale)
 {
-  KW_CHECK_CTX(ctx);
-  KW_PROF(ctx, "line_recon_mix");
-  const kw_constants& c = ctx->c; // (a context without constants has no bins)
-  const uint64_t n = ctx->have_consts ? static_cast<uint64_t>(c.nx / 2 + 1) * c.ny * c.nz : 0;
-  if (n == 0) return KW_OK;
-  KW_REQUIRE(out_spec && spec && op && out_spec != spec);
+  KW_MIX_ENTRY(ctx, "line_recon_mix", c, n, out_spec, spec, op);
   KW_REQUIRE(op->dx > 0.0 && op->dt > 0.0 && op->c0 > 0.0 && (op->interp == 0 || op->interp == 1));
   const double dk = kTwoPi / (static_cast<double>(c.ny) * op->dt * op->c0);
   LineMix g{};

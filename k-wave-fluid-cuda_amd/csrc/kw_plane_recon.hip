@@ -5,14 +5,13 @@
 // the bins of one (kx, ky) line — the line the z-pass of the fused pipeline holds in LDS.
 //
 //   recon_w / recon_f    weight and gather position of one bin: shared by the fused kernel and the twin, and with the
-//                        line reconstruction (kw_recon_device.h, with recon_scale, recon_pick and the crop kernel)
+//                        line reconstruction (kw_recon_device.h, with recon_scale, recon_pick, the twins' recon_gather
+//                        and the crop kernel)
 //   k_zfused_recon       the z-pass of kw_fused_plane_recon (kw_fused_main.hip): lines of scratch array 0 forward along t,
 //                        T written back into the exchange buffer, the gather from LDS, inverse along t, in place — no
 //                        operator array and no index table in memory
 //   kw_plane_recon_mix   the same on the natural [Lt][Ey][Ex/2 + 1] spectrum of kw_fft_r2c_3d (rocFFT path, and the twin)
 //   kw_plane_recon_embed / _crop   the mirrored embedding of the record; the first planes of the domain crop, clamped on request
-#include "kw_elementwise.h"
-#include "kw_fused.hip"
 #include "kw_recon_device.h"
 
 namespace {
@@ -21,9 +20,7 @@ namespace {
 __device__ __forceinline__ double recon_rho2(double dkx, double dky, double dk2, uint32_t ex, uint32_t ey, uint32_t ix, uint32_t iy)
 {
 #pragma clang fp contract(off)
-  const double kx = dkx * static_cast<double>(kw_folded(ix, ex));
-  const double ky = dky * static_cast<double>(kw_folded(iy, ey));
-  return ((kx * kx) + (ky * ky)) / dk2;
+  return kw_kr2(dkx, dky, ex, ey, ix, iy) / dk2;
 }
 
 // =====================================================================================================================
@@ -48,8 +45,8 @@ template<int L> __global__ __launch_bounds__((Geo<L, nl_z(L)>::THREADS)) void k_
   constexpr uint32_t M = L / 2;
   __shared__ float2 lds[G::LDSB];
   __shared__ float2 twl[G::TWN];
-  load_twiddles<L>(twl, a.tw);
-  const LineTile t      = line_tile<G>(a.nxc, a.P, a.side_off, a.ny, 1u);
+  load_twiddles<L>(twl, a.geo.tw);
+  const LineTile t      = line_tile<G>(a.geo.nxc, a.geo.P, a.geo.side_off, a.ny, 1u);
   if (t.tc.dead) return;
   const int      c      = t.c, j = t.j;
 
@@ -60,8 +57,8 @@ template<int L> __global__ __launch_bounds__((Geo<L, nl_z(L)>::THREADS)) void k_
   if (ACTW(R2, j)) fwd_cols<L, kFwd, G::NL>(v, lds, c, j, twl);
   lds_barrier();
   float2 X[R2];
-  // the true column: the side array holds bin Ex/2 = a.nxc; pad lanes (never stored) take the last main column
-  const double rho2 = recon_rho2(a.dkx, a.dky, a.dk2, a.ex, a.ny, t.tc.side ? a.nxc : t.tc.col, t.pos);
+  // the true column: the side array holds bin Ex/2 = a.geo.nxc; pad lanes (never stored) take the last main column
+  const double rho2 = recon_rho2(a.dkx, a.dky, a.dk2, a.ex, a.ny, t.tc.side ? a.geo.nxc : t.tc.col, t.pos);
   if (ACTW(R1, j))
   {
     fwd_rows<L, kFwd, G::NL>(X, lds, c, j);
@@ -123,21 +120,9 @@ __global__ __launch_bounds__(256) void k_plane_recon_mix(float2* __restrict__ ou
     const uint32_t ix = static_cast<uint32_t>(e % nxc);
     const uint64_t r  = e / nxc;
     const uint32_t iy = static_cast<uint32_t>(r % g.ey), m = static_cast<uint32_t>(r / g.ey);
-    const uint64_t col = e - static_cast<uint64_t>(m) * pl;
-    const uint32_t mp  = m <= M ? m : g.lt - m;
+    const uint32_t mp = m <= M ? m : g.lt - m;
     const double rho2 = recon_rho2(g.dkx, g.dky, g.dk2, g.ex, g.ey, ix, iy);
-    const double f    = recon_f(rho2, mp);
-    float2 res = make_float2(0.f, 0.f);
-    if (f <= static_cast<double>(M))
-    {
-      const uint32_t i0 = static_cast<uint32_t>(f);
-      const uint32_t i1 = i0 + 1u <= M ? i0 + 1u : M;
-      const float    al = static_cast<float>(f - static_cast<double>(i0));
-      const float2   t0 = recon_scale(spec[col + static_cast<uint64_t>(i0) * pl], recon_w(rho2, i0, g.scale));
-      const float2   t1 = recon_scale(spec[col + static_cast<uint64_t>(i1) * pl], recon_w(rho2, i1, g.scale));
-      res = recon_pick(t0, t1, al, nearest);
-    }
-    out[e] = res;
+    out[e] = recon_gather(spec + (e - static_cast<uint64_t>(m) * pl), pl, rho2, mp, M, g.scale, nearest);
   }
 }
 
@@ -153,23 +138,18 @@ namespace kwfused {
 // the z-pass of kw_fused_plane_recon: the lines of `s` in place
 kw_status zfused_recon(kw_ctx* ctx, float2* s, const kw_plane_recon_op* op)
 {
-  const auto& f = ctx->fused;
   const kw_constants& c = ctx->c;
   KW_PROF(ctx, "k_zfused_recon");
   const double dk = kTwoPi / (static_cast<double>(c.nz) * op->dt * op->c0);
   ZReconArgs a{};
   a.s   = s;
-  a.tw  = f.tw[2];
+  a.geo = pass_geo(ctx, 2);
   a.dkx = kTwoPi / (static_cast<double>(c.nx) * op->dx);
   a.dky = kTwoPi / (static_cast<double>(c.ny) * op->dy);
   a.dk2 = dk * dk;
   a.scale    = static_cast<float>(2.0 / (static_cast<double>(c.nx) * c.ny * c.nz));
-  a.nxc      = f.nxm;
-  a.P        = f.P;
   a.ex       = c.nx;
   a.ny       = c.ny;
-  a.nz       = c.nz;
-  a.side_off = f.side_off;
   a.nearest  = op->interp == 1 ? 1u : 0u;
   return KW_LAUNCH_ZPASS((k_zfused_recon<LEN>), c.nz, z_pass_grid(ctx, nl_z(c.nz)), a);
 }
@@ -180,12 +160,7 @@ extern "C" {
 
 kw_status kw_plane_recon_mix(kw_ctx* ctx, float* out_spec, const float* spec, const kw_plane_recon_op* op, float scale)
 {
-  KW_CHECK_CTX(ctx);
-  KW_PROF(ctx, "plane_recon_mix");
-  const kw_constants& c = ctx->c; // (a context without constants has no bins)
-  const uint64_t n = ctx->have_consts ? static_cast<uint64_t>(c.nx / 2 + 1) * c.ny * c.nz : 0;
-  if (n == 0) return KW_OK;
-  KW_REQUIRE(out_spec && spec && op && out_spec != spec);
+  KW_MIX_ENTRY(ctx, "plane_recon_mix", c, n, out_spec, spec, op);
   KW_REQUIRE(op_ok(op));
   const double dk = kTwoPi / (static_cast<double>(c.nz) * op->dt * op->c0);
   ReconMix g{};

@@ -1,10 +1,12 @@
-// kw_recon_device.h — the per-bin arithmetic of the k-space reconstructions, shared by the plane reconstruction
-// (kw_plane_recon.hip: k_zfused_recon, k_plane_recon_mix) and the batched line reconstruction (kw_line_recon.hip:
-// k_yfused_line_recon, k_line_recon_mix), and the crop kernel of both.  kwave_hip.h "k-space plane reconstruction"
-// documents the definition and the order of the arithmetic; the two operators differ in rho2 alone.
+// kw_recon_device.h — what the k-space reconstructions share: the plane reconstruction (kw_plane_recon.hip:
+// k_zfused_recon, k_plane_recon_mix) and the batched line reconstruction (kw_line_recon.hip: k_yfused_line_recon,
+// k_line_recon_mix).  The per-bin arithmetic, the argument struct of the fused kernels, the gather of the rocFFT twins
+// (recon_gather) and the crop kernel.  kwave_hip.h "k-space plane reconstruction" documents the
+// definition and the order of the arithmetic; the two operators differ in rho2 and in the direction of their lines alone.
 #ifndef KW_RECON_DEVICE_H
 #define KW_RECON_DEVICE_H
 #include "kw_elementwise.h"
+#include "kw_fused.hip"
 
 #ifdef __HIPCC__
 namespace {
@@ -42,6 +44,35 @@ __device__ __forceinline__ float2 recon_pick(const float2& t0, const float2& t1,
 #pragma clang fp contract(off)
   if (nearest) return a < 0.5f ? t0 : t1;
   return make_float2((a * (t1.x - t0.x)) + t0.x, (a * (t1.y - t0.y)) + t0.y);
+}
+
+// the argument of the two fused passes (k_zfused_recon, k_yfused_line_recon): weight and gather along the line, formed per bin
+struct ZReconArgs
+{
+  float2*  s;             // scratch array 0, in place (rows [t][ky][P], side array at side_off; line pass: [frame][t][P])
+  PassGeo  geo;
+  double   dkx, dky, dk2; // 2 pi / (Ex dx), 2 pi / (Ey dy), (2 pi / (Lt dt c0))^2; line pass: dkx of the sensor axis, no dky
+  float    scale;         // 2 / (Ex Ey Lt); line pass: 2 / (Ey Lt)
+  uint32_t ex, ny;        // Ex (the bin counts along x), rows of a plane
+  uint32_t nearest;
+};
+
+// The gather of the rocFFT twins: G of bin m' of a line in memory whose bin i is line[i * stride]; M = Lt / 2
+__device__ __forceinline__ float2 recon_gather(const float2* __restrict__ line, uint64_t stride, double rho2, uint32_t mp,
+                                               uint32_t M, float scale, bool nearest)
+{
+  const double f = recon_f(rho2, mp);
+  float2 res = make_float2(0.f, 0.f);
+  if (f <= static_cast<double>(M))
+  {
+    const uint32_t i0 = static_cast<uint32_t>(f);
+    const uint32_t i1 = i0 + 1u <= M ? i0 + 1u : M;
+    const float    al = static_cast<float>(f - static_cast<double>(i0));
+    const float2   t0 = recon_scale(line[static_cast<uint64_t>(i0) * stride], recon_w(rho2, i0, scale));
+    const float2   t1 = recon_scale(line[static_cast<uint64_t>(i1) * stride], recon_w(rho2, i1, scale));
+    res = recon_pick(t0, t1, al, nearest);
+  }
+  return res;
 }
 
 __device__ __forceinline__ float recon_clamp(float x, bool positivity) { return (positivity && !(x > 0.f)) ? 0.f : x; }

@@ -29,15 +29,6 @@ struct SecondH
 
 enum : uint32_t { kPowGeneral = 0, kPowStokes = 1, kPowHalf = 2 };
 
-// kx^2 + ky^2 of column ix (0 ... Ex/2) and row iy, float64
-__device__ __forceinline__ double second_kr2(double dkx, double dky, uint32_t ex, uint32_t ey, uint32_t ix, uint32_t iy)
-{
-#pragma clang fp contract(off)
-  const double kx = dkx * static_cast<double>(kw_folded(ix, ex));
-  const double ky = dky * static_cast<double>(kw_folded(iy, ey));
-  return (kx * kx) + (ky * ky);
-}
-
 // H(|k|; t) * divider of bin m along z (kwave_hip.h "Exact k-space propagator"): float64 up to the phase word and the
 // exponent of the decay, float32 from there; no contraction.
 // A real call, not inlined, as time_h (kw_angular_time.hip): unrolled over the R2 bins of a thread the two float64 square
@@ -88,9 +79,8 @@ struct ZSecondArgs
 {
   const float2* in;   // the kept (kx, ky, z) half-spectrum, scratch layout (rows [z][ky][P], side array at side_off)
   float2*       out;  // scratch array 0
-  const float2* tw;
+  PassGeo       geo;
   SecondH       g;
-  uint32_t      nxc, P, side_off;
 };
 
 template<int L> __global__ __launch_bounds__((Geo<L, nl_z(L)>::THREADS)) void k_zfused_second_order(ZSecondArgs a)
@@ -100,8 +90,8 @@ template<int L> __global__ __launch_bounds__((Geo<L, nl_z(L)>::THREADS)) void k_
   __shared__ float2  lds[G::LDSB];
   __shared__ float2  twl[G::TWN];
   __shared__ SecondH gsh;
-  load_twiddles<L>(twl, a.tw);
-  const LineTile t = line_tile<G>(a.nxc, a.P, a.side_off, a.g.ey, 1u);
+  load_twiddles<L>(twl, a.geo.tw);
+  const LineTile t = line_tile<G>(a.geo.nxc, a.geo.P, a.geo.side_off, a.g.ey, 1u);
   if (t.tc.dead) return;
   const int      c = t.c, j = t.j;
   if (threadIdx.x == 0) gsh = a.g; // (published by the barrier that publishes the twiddle table)
@@ -117,8 +107,8 @@ template<int L> __global__ __launch_bounds__((Geo<L, nl_z(L)>::THREADS)) void k_
   {
     fwd_rows<L, kFwd, G::NL>(X, lds, c, j);
     const SecondHLds gl = (SecondHLds)&gsh;
-    // the true column: the side array holds bin Ex/2 = a.nxc; pad lanes (never stored) take the last main column
-    const double kr2 = second_kr2(a.g.dkx, a.g.dky, a.g.ex, a.g.ey, t.tc.side ? a.nxc : t.tc.col, t.pos);
+    // the true column: the side array holds bin Ex/2 = a.geo.nxc; pad lanes (never stored) take the last main column
+    const double kr2 = kw_kr2(a.g.dkx, a.g.dky, a.g.ex, a.g.ey, t.tc.side ? a.geo.nxc : t.tc.col, t.pos);
 #pragma unroll
     for (int k2 = 0; k2 < R2; k2++)
     {
@@ -135,22 +125,7 @@ template<int L> __global__ __launch_bounds__((Geo<L, nl_z(L)>::THREADS)) void k_
 // the rocFFT twin: out[e] = spec[e] H on the natural [ez][ey][ex/2 + 1] half-spectrum, out of place
 __global__ __launch_bounds__(256) void k_second_order_mix(float2* __restrict__ out, const float2* __restrict__ spec, SecondH g)
 {
-  __shared__ SecondH gsh;
-  if (threadIdx.x == 0) gsh = g;
-  __syncthreads();
-  const SecondHLds gl = (SecondHLds)&gsh;
-  const uint32_t nxc = g.ex / 2 + 1;
-  const uint64_t n   = static_cast<uint64_t>(nxc) * g.ey * g.ez;
-  for (uint64_t e = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; e < n;
-       e += static_cast<uint64_t>(gridDim.x) * blockDim.x)
-  {
-    const uint32_t ix = static_cast<uint32_t>(e % nxc);
-    const uint64_t r  = e / nxc;
-    const uint32_t iy = static_cast<uint32_t>(r % g.ey), m = static_cast<uint32_t>(r / g.ey);
-    const float  h = second_h(gl, second_kr2(g.dkx, g.dky, g.ex, g.ey, ix, iy), m);
-    const float2 x = spec[e];
-    out[e] = make_float2(h * x.x, h * x.y);
-  }
+  half_spectrum_mix(out, spec, g, g.ez, [](SecondHLds gl, double kr2, uint32_t m) { return second_h(gl, kr2, m); });
 }
 
 // the constants of one output time on the grid (Ex, Ey, Ez) = (c.nx, c.ny, c.nz), float64 on the host
@@ -188,16 +163,12 @@ namespace kwfused {
 // the z-pass of kw_fused_second_order_time: lines of `in` (the kept spectrum) to `out`, H of the time `op`
 kw_status zfused_second_order(kw_ctx* ctx, const float2* in, float2* out, const kw_second_order_op* op)
 {
-  const auto& f = ctx->fused;
   const kw_constants& c = ctx->c;
   KW_PROF(ctx, "k_zfused_second_order");
   ZSecondArgs a{};
   a.in = in; a.out = out;
-  a.tw = f.tw[2];
-  a.g  = time_constants(c, op, static_cast<float>(1.0 / (static_cast<double>(c.nx) * c.ny * c.nz)));
-  a.nxc      = f.nxm;
-  a.P        = f.P;
-  a.side_off = f.side_off;
+  a.geo = pass_geo(ctx, 2);
+  a.g   = time_constants(c, op, static_cast<float>(1.0 / (static_cast<double>(c.nx) * c.ny * c.nz)));
   return KW_LAUNCH_ZPASS((k_zfused_second_order<LEN>), c.nz, z_pass_grid(ctx, nl_z(c.nz)), a);
 }
 
@@ -207,12 +178,7 @@ extern "C" {
 
 kw_status kw_second_order_mix(kw_ctx* ctx, float* out_spec, const float* spec, const kw_second_order_op* op, float divider)
 {
-  KW_CHECK_CTX(ctx);
-  KW_PROF(ctx, "second_order_mix");
-  const kw_constants& c = ctx->c; // (a context without constants has no bins)
-  const uint64_t n = ctx->have_consts ? static_cast<uint64_t>(c.nx / 2 + 1) * c.ny * c.nz : 0;
-  if (n == 0) return KW_OK;
-  KW_REQUIRE(out_spec && spec && op && out_spec != spec);
+  KW_MIX_ENTRY(ctx, "second_order_mix", c, n, out_spec, spec, op);
   KW_REQUIRE(valid_op(op));
   const SecondH g = time_constants(c, op, divider);
   hipLaunchKernelGGL(k_second_order_mix, dim3(capped_grid(ctx, n)), dim3(256), 0, ctx->stream,
