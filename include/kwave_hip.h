@@ -985,15 +985,16 @@ KW_API kw_status kw_line_recon_crop(kw_ctx* ctx, float* out, const float* vol, u
  * kw_fused_second_order_time: vol_out [nz][ny][nx] <- the pressure at op->t: one launch k_zfused_second_order (lines of
  *   `kept` forward along z, H formed in registers from the column, the row and the bin m — no operator array, no table in
  *   memory —, inverse along z into scratch array 0; divider = 1 / (nx ny nz)), the y-inverse and the storing x-inverse.
- *   `kept` is not written.  Both: single GPU, nz > 1: KW_ERR_INVALID in slab mode, for Nz == 1 and on a frames context.
+ *   `kept` is not written.  Both: single GPU, nz > 1: KW_ERR_INVALID in slab mode, for Nz == 1 and on a frames context
+ *   (kw_fused_second_order_frames_* are that context's entries).
  * kw_second_order_mix: the twin: out_spec <- spec H on the natural [nz][ny][nx/2 + 1] half-spectrum of kw_fft_r2c_3d, out
  *   of place, for kw_fft_c2r_3d (grids off the fast path; any nx, ny, nz, odd ones included).  A context without bins:
  *   KW_OK, nothing launched.
  * Embedding and crop: kw_angular_time_embed and kw_plane_recon_crop (a 3-D corner either way).  Sensor records and the
  * aggregates over the output times: kw_sample_index and kw_sample_all on the volume and on the crop.
- * Not built: dp0/dt as a second initial condition and time-varying sources, heterogeneous media, 2-D (Nz == 1) and its
- * batched form on a frames context, Z-slabs, several output times per z-pass, inverse passes restricted to the crop or to
- * the sensor points, particle velocity.
+ * Not built: dp0/dt as a second initial condition and time-varying sources, heterogeneous media, Z-slabs, several output
+ * times per z-pass, inverse passes restricted to the crop or to the sensor points, particle velocity.  (2-D: the batched
+ * form on a frames context, below.)
  * ---------------------------------------------------------------------------------------------------------------- */
 typedef struct kw_second_order_op {   /* H of one time */
   double  dx, dy, dz, c0, t;          /* [m], [m], [m], [m/s], [s]; t >= 0 */
@@ -1006,6 +1007,47 @@ KW_API kw_status kw_fused_second_order_forward(kw_ctx* ctx, const float* vol, fl
 KW_API kw_status kw_fused_second_order_time(kw_ctx* ctx, const float* kept, const kw_second_order_op* op, float* vol_out);
 KW_API kw_status kw_second_order_mix(kw_ctx* ctx, float* out_spec, const float* spec, const kw_second_order_op* op,
                                      float divider);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Exact k-space propagator on frames: the batched 2-D form of the operator above (csrc/kw_second_order.hip,
+ * host/SecondOrderFrames.cpp, DESIGN.md "Exact k-space propagator on frames").  F independent planes p0[f][y][x] that
+ * share c0, the absorption and the output times; the grid of kw_set_constants is (nx, ny, nz) = (Ex, Ey, F), the fused
+ * pipeline a frames context (kw_fused_set_frames): no transform along z.  One frame is the 3-D operator with the z axis
+ * removed:
+ *     p_f(., .; t) = crop( irfft2( rfft2(p0_f embedded in Ey x Ex) H(|k|; t) ) ),   |k|^2 = (kx*kx) + (ky*ky)
+ *     bins are counted k? = 2 pi / (E? d?) * min(i, E? - i)
+ * H is the H above, formed by the same device function (second_h) in the fused pass and in the twin: the bin along y
+ * stands where the z bin does (dkz, ez := 2 pi / (Ey dy), Ey), kr2 = (kx*kx) of the column in float64 without contraction,
+ * k2 = kr2 + (ky*ky), divider = 1 / (Ex Ey).  op is kw_second_order_op; dz is not looked at, the other validations are the
+ * 3-D entries'.
+ *
+ * kw_fused_second_order_frames_elems: complex values of `kept` = one scratch array of the frames context: P Ey F and the
+ *   x-Nyquist side array [F][Ey].
+ * kw_fused_second_order_frames_forward: kept <- the (kx, y, frame) half-spectrum of vol [F][Ey][Ex]: the x-forward over
+ *   all Ey F rows (a masked last tile where the row count asks for one), then a copy of scratch array 0, side array included.
+ * kw_fused_second_order_frames_time: vol_out [F][Ey][Ex] <- every frame's pressure at op->t: ONE launch
+ *   k_yfused_second_order (tile position = the frame; lines of `kept` forward along y, H formed in registers from the
+ *   column and the bin — nothing read from memory for it —, inverse along y into scratch array 0; the side array's blocks
+ *   take the column Ex/2 at NL frames each, those past the last frame store nothing) and the storing x-inverse.  `kept` is
+ *   not written.
+ * The three return KW_ERR_STATE before kw_fused_create and KW_ERR_INVALID outside frames mode (3-D, 2-D and slab
+ * contexts); kw_fused_second_order_elems / _forward / _time keep refusing frames contexts.  kw_fused_supported's rules
+ * for a frames context hold (at most 65535 frames, the scratch array below 2^29 complex values).
+ * kw_second_order_frames_mix: the twin: out_spec <- spec H on the natural [F][Ey][Ex/2 + 1] half-spectra of
+ *   kw_fft_r2c_frames, out of place, for kw_fft_c2r_frames; any sizes, odd ones included.  A context without bins: KW_OK,
+ *   nothing launched.
+ * Embedding and crop: kw_angular_time_embed and kw_plane_recon_crop with the frame count in the slowest position.  The
+ * record: kw_sample_index on the expanded batch; the aggregates: kw_sample_all on the crop.
+ * Not built: dp0/dt as a second initial condition and time-varying sources, heterogeneous media, chunks of frames and
+ * frames over several GPUs, several output times per pass, an x-inverse restricted to the rows that hold sensors (the
+ * efficient form for a line sensor), particle velocity.
+ * ---------------------------------------------------------------------------------------------------------------- */
+KW_API kw_status kw_fused_second_order_frames_elems(kw_ctx* ctx, size_t* out_elems);
+KW_API kw_status kw_fused_second_order_frames_forward(kw_ctx* ctx, const float* vol, float* kept);
+KW_API kw_status kw_fused_second_order_frames_time(kw_ctx* ctx, const float* kept, const kw_second_order_op* op,
+                                                   float* vol_out);
+KW_API kw_status kw_second_order_frames_mix(kw_ctx* ctx, float* out_spec, const float* spec, const kw_second_order_op* op,
+                                            float divider);
 
 #ifdef __cplusplus
 }

@@ -488,8 +488,7 @@ KWH_API void*    kwh_line_recon_context(kwh_line_recon* s);
  * or more), sensor_index (NULL, an entry outside the domain), t (negative or not finite), n_times (0).
  * Of kwh_options the calls read device_idx and fused_kernels.  kwh_second_order_plan validates and completes (Ex, Ey, Ez)
  * and the fast-path flag without a device.  Not built: dp0/dt as a second initial condition and time-varying sources,
- * heterogeneous media, 2-D (Nz == 1) and its batched form, Z-slabs, HDF5 files and the command line, graphs, several
- * output times per z-pass, inverse passes restricted to the crop or to the sensor points, particle velocity outputs.
+ * heterogeneous media, Z-slabs, HDF5 files and the command line, graphs, several output times per z-pass, inverse passes restricted to the crop or to the sensor points, particle velocity outputs.
  * ---------------------------------------------------------------------------------------------------------------- */
 #define KWH_SECOND_ORDER_P_MAX   1
 #define KWH_SECOND_ORDER_P_MIN   2
@@ -527,6 +526,60 @@ KWH_API int      kwh_second_order_get(kwh_second_order* s, const char* name, flo
 KWH_API int      kwh_second_order_get_scalar(kwh_second_order* s, const char* name, double* out);
 /* the underlying kw_ctx* (include/kwave_hip.h) */
 KWH_API void*    kwh_second_order_context(kwh_second_order* s);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Exact k-space propagator on frames: the batched 2-D form of the propagator above — F independent initial pressures
+ * p0[f][y][x] on the domain Nx x Ny, each carried to any time t >= 0 as
+ *     p_f(., .; t) = crop( irfft2( rfft2(p0_f embedded in Ey x Ex) H(|k|; t) ) ),   |k|^2 = kx^2 + ky^2
+ * with the H of the 3-D operator (kwave_hip.h "Exact k-space propagator on frames").  The frames share c0, the
+ * absorption, the expanded plane, the output times and the sensor points; one pass serves the whole batch (the forward
+ * side of kwh_line_recon: what a linear array records for many phantoms, with the same c0, dt and grid).
+ *   E (0 0 = default): as above per axis, with t_max > 0; given sides: both, not below N.  "t_free" is taken over x and y.
+ *   Absorption: the B rule above on the 2-D grid's smallest non-zero and largest |k|.
+ *   frames: 1 ... 65535; there are no chunks of frames in this version.  A batch that the fused pipeline does not take for
+ *   its size runs on rocFFT, like any grid off the fast path.
+ *   sensor_index: n_sensor 0-based flat indices into ONE plane [Ny][Nx], applied to every frame.
+ * Refused, naming the parameter: Nx Ny frames (0; frames above 65535), dx dy c0 (not positive), t_max (not positive while
+ * the sides are by default), alpha_coeff (< 0, the B rule), alpha_power (outside 0 <= y < 3, y = 1), Ex Ey (missing, below N),
+ * E (2^32 points or more), sensor_index (NULL, an entry outside the plane), t (negative or not finite), n_times (0).
+ * flags: KWH_SECOND_ORDER_P_*.  kwh_second_order_frames_plan validates and completes (Ex, Ey) and the fast-path flag
+ * without a device.  Not built: dp0/dt as a second initial condition and time-varying sources, heterogeneous media,
+ * chunks of frames and frames over several GPUs, several output times per pass, an x-inverse restricted to the rows that
+ * hold sensors (the efficient form for a line sensor), particle velocity outputs, HDF5 files and the command line, graphs.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct kwh_second_order_frames kwh_second_order_frames;
+typedef struct kwh_second_order_frames_config
+{
+  uint64_t nx, ny;          /* the domain of one frame */
+  uint64_t frames;          /* F */
+  double   dx, dy;          /* [m] */
+  double   c0;              /* [m/s] */
+  double   alpha_coeff;     /* [dB / (MHz^y cm)]; 0 = lossless */
+  double   alpha_power;     /* y */
+  double   t_max;           /* [s]; sizes the default sides; 0 with given sides */
+  uint64_t ex, ey;          /* expanded sides; 0 0 = default */
+  uint64_t n_sensor;
+  const uint64_t* sensor_index; /* n_sensor indices into [Ny][Nx] */
+  int32_t  flags;           /* KWH_SECOND_ORDER_P_* */
+  int32_t  pad_;
+} kwh_second_order_frames_config;
+KWH_API int      kwh_second_order_frames_plan(const kwh_second_order_frames_config* config, const kwh_options* options,
+                                              uint64_t out_expanded[2], int32_t* out_fast_path);
+KWH_API int      kwh_second_order_frames_create(const kwh_second_order_frames_config* config, const kwh_options* options,
+                                                kwh_second_order_frames** out);
+KWH_API int      kwh_second_order_frames_destroy(kwh_second_order_frames* s);
+/* p0: Nx * Ny * F floats on the host ([F][Ny][Nx]): embed, transform, keep; may be called again */
+KWH_API int      kwh_second_order_frames_set_p0(kwh_second_order_frames* s, const float* p0);
+/* every frame's pressure at time t; the crop [F][Ny][Nx] stays on the device ("p") and goes to dst where dst is not NULL */
+KWH_API int      kwh_second_order_frames_field(kwh_second_order_frames* s, double t, float* dst);
+/* every time in the given order: row i of the record, the aggregates */
+KWH_API int      kwh_second_order_frames_run(kwh_second_order_frames* s, const double* times, uint64_t n_times);
+/* "p_raw" [n_times][F][n_sensor], "p_max", "p_min", "p_rms", "p_final" of the last run ([F][Ny][Nx]), "p"; n checked */
+KWH_API int      kwh_second_order_frames_get(kwh_second_order_frames* s, const char* name, float* dst, uint64_t n);
+/* "fused_pipeline", "Ex", "Ey", "frames", "t_free", "runs" */
+KWH_API int      kwh_second_order_frames_get_scalar(kwh_second_order_frames* s, const char* name, double* out);
+/* the underlying kw_ctx* (include/kwave_hip.h) */
+KWH_API void*    kwh_second_order_frames_context(kwh_second_order_frames* s);
 
 #ifdef __cplusplus
 }

@@ -147,7 +147,7 @@ struct AngArgs
 };
 
 // the geometry of a pass over the scratch layout: what the operator passes (k_zfused_time, k_zfused_second_order,
-// k_zfused_recon, k_yfused_line_recon) take from the context (pass_geo)
+// k_yfused_second_order, k_zfused_recon, k_yfused_line_recon) take from the context (pass_geo)
 struct PassGeo
 {
   const float2* tw;                 // the twiddle table of the line's axis
@@ -206,6 +206,9 @@ kw_status zfused_recon(kw_ctx* ctx, float2* s, const kw_plane_recon_op* op);
 // the pass along t of kw_fused_line_recon (frames context): lines of `s` along y, one frame per tile position, the plane
 // reconstruction's weight and gather with rho2 of the column alone, in place (kw_line_recon.hip; op->dx = the sensor pitch)
 kw_status yfused_line_recon(kw_ctx* ctx, float2* s, const kw_plane_recon_op* op);
+// the pass along y of kw_fused_second_order_frames_time (frames context): lines of `in` (the kept spectrum of the frames)
+// forward along y, the real H(|k|; t) of the plane formed in registers, the inverse, to `out` (kw_second_order.hip)
+kw_status yfused_second_order(kw_ctx* ctx, const float2* in, float2* out, const kw_second_order_op* op);
 // the tuning probes of kw_fused_probe that launch no pipeline kernel (kw_fused_probe.hip)
 kw_status probe_patterns(kw_ctx* ctx, int which, const float* op);
 
@@ -486,7 +489,7 @@ template<int L, int DIR> __device__ __forceinline__ void step_a(float2 (&v)[Fac<
 // four-step transform through the block's buffer lds[G::LDSB].  A kernel's body keeps what is its own — which arrays,
 // what happens to a bin between the transforms — and the order of loads, barriers and stores.
 // On the steps: k_zfused_split, k_zfused_pair_split (kw_cw.hip), k_zfused_time (kw_angular_time.hip), k_zfused_second_order
-// (kw_second_order.hip), k_zfused_recon (kw_plane_recon.hip), k_yfused_line_recon (kw_line_recon.hip); k_ypass and k_ypass_split take the tile and keep their
+// and k_yfused_second_order (kw_second_order.hip), k_zfused_recon (kw_plane_recon.hip), k_yfused_line_recon (kw_line_recon.hip); k_ypass and k_ypass_split take the tile and keep their
 // RowAddr loads and stores.  k_zfused, k_zfused_pair (kw_cw.hip) and k_yinv_angular (kw_angular.hip) spell the same steps out in their bodies: assembled from
 // the functions below the compiler allocates their guarded (non-whole-wave) and spilling instantiations differently — an
 // occupancy step lost at some lengths, scratch bytes gained at others — so they stay as they were written.  A change to

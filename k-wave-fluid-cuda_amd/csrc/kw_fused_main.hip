@@ -80,7 +80,7 @@ bool supported_len(uint32_t n)
     if (!(ctx)->fused.ready) { kw_set_error("%s: kw_fused_create has not been called", __func__); return KW_ERR_STATE; } \
     if ((ctx)->fused.frames)                                                                                           \
     {                                                                                                                  \
-      kw_set_error("%s: not on a context in frames mode (kw_fused_set_frames): kw_fused_line_recon is its one stage", __func__); \
+      kw_set_error("%s: not on a context in frames mode (kw_fused_set_frames): its stages are kw_fused_line_recon and kw_fused_second_order_frames_*", __func__); \
       return KW_ERR_INVALID;                                                                                           \
     }                                                                                                                  \
   } while (0)
@@ -1571,6 +1571,50 @@ kw_status kw_fused_line_recon(kw_ctx* ctx, const float* vol_even, const kw_plane
   const float* in1[1] = { vol_even };
   KW_TRY(launch_xfwd(ctx, 1, in1, S));
   KW_TRY(yfused_line_recon(ctx, S[0], op));
+  return store_scratch0(ctx, vol_out, false);
+}
+
+// Batched 2-D exact k-space propagator (kw_second_order.hip), frames mode: F planes [Ey][Ex], no transform along z.  The
+// (kx, y, frame) half-spectrum of the embedded p0 is kept aside; every output time is ONE launch of k_yfused_second_order
+// that reads it (forward along y, H, inverse along y into scratch array 0) and the storing x-inverse.
+#define KW_FRAMES_STAGE_READY(ctx)                                                                                     \
+  do {                                                                                                                 \
+    KW_CHECK_CONSTS(ctx);                                                                                              \
+    if (!(ctx)->fused.ready) { kw_set_error("%s: kw_fused_create has not been called", __func__); return KW_ERR_STATE; } \
+    if (!(ctx)->fused.frames)                                                                                          \
+    {                                                                                                                  \
+      kw_set_error("%s: needs a context in frames mode (kw_fused_set_frames before kw_fused_create)", __func__);       \
+      return KW_ERR_INVALID;                                                                                           \
+    }                                                                                                                  \
+  } while (0)
+
+kw_status kw_fused_second_order_frames_elems(kw_ctx* ctx, size_t* out)
+{
+  KW_FRAMES_STAGE_READY(ctx);
+  KW_REQUIRE(out != nullptr);
+  *out = kept_elems(ctx);
+  return KW_OK;
+}
+
+kw_status kw_fused_second_order_frames_forward(kw_ctx* ctx, const float* vol, float* kept)
+{
+  KW_FRAMES_STAGE_READY(ctx);
+  KW_PROF(ctx, "fused_second_order_frames_forward");
+  KW_REQUIRE(vol && kept);
+  const float* in1[1] = { vol };
+  KW_TRY(launch_xfwd(ctx, 1, in1, ctx->fused.s));
+  KW_HIP(hipMemcpyAsync(kept, ctx->fused.s[0], kept_elems(ctx) * sizeof(float2), hipMemcpyDeviceToDevice, ctx->stream));
+  return KW_OK;
+}
+
+kw_status kw_fused_second_order_frames_time(kw_ctx* ctx, const float* kept, const kw_second_order_op* op, float* vol_out)
+{
+  KW_FRAMES_STAGE_READY(ctx);
+  KW_PROF(ctx, "fused_second_order_frames_time");
+  KW_REQUIRE(kept && op && vol_out);
+  KW_REQUIRE(op->dx > 0.0 && op->dy > 0.0 && op->c0 > 0.0 && op->t >= 0.0); // (dz is not looked at)
+  KW_REQUIRE(op->absorbing == 0 || (op->a >= 0.0 && op->alpha_power >= 0.0 && op->alpha_power != 1.0));
+  KW_TRY(yfused_second_order(ctx, reinterpret_cast<const float2*>(kept), ctx->fused.s[0], op));
   return store_scratch0(ctx, vol_out, false);
 }
 

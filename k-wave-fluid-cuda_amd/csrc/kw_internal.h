@@ -89,7 +89,7 @@ struct kw_ctx
     // receive t[] -> y-inverse -> s[] -> x-inverse + epilogue -> chained x / y forward -> t[] -> forward send — runs per
     // chunk of planes while the other chunks are on the wire.
     bool     frames = false;                       // kw_fused_set_frames: nz independent planes (ny x nx), no transform along z;
-                                                   // kw_fused_line_recon is the context's one stage
+                                                   // kw_fused_line_recon and kw_fused_second_order_frames_* are the context's stages
     bool     two_d = false;                        // Nz == 1: x-pass, fused pass along y (in the z-pass kernels' role), x-pass; no y-pass
     bool     pipelined = false;
     uint32_t xchunks   = 1;                        // plane chunks per array of the pipelined tail

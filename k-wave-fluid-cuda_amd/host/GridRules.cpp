@@ -8,6 +8,8 @@
 
 namespace
 {
+const double kPi = 3.14159265358979323846;
+
 // KW_FUSED_LENGTHS of csrc/kw_fused.hip, ascending
 const size_t kFastLengths[] = { 16,  32,  48,  64,  72,  80,  96,  100, 108, 112, 120, 128, 140, 144, 160, 168,
                                 180, 192, 196, 200, 216, 224, 240, 252, 256, 280, 288, 300, 320, 324, 336, 360,
@@ -63,5 +65,27 @@ void defaultDoubledSides(size_t nx, size_t ny, size_t& ex, size_t& ey, bool fuse
   const bool fast = fusedKernels && nextFastLength(2 * nx) != 0 && nextFastLength(2 * ny) != 0;
   ex = fast ? nextFastLength(2 * nx) : 2 * nx;
   ey = fast ? nextFastLength(2 * ny) : 2 * ny;
+}
+
+size_t reachSide(size_t n, double d, double reach, bool fusedKernels)
+{
+  const double cells = std::ceil(reach / d);
+  if (!(cells < 4294967296.0)) refuse("t_max", "c0 t_max reaches over " + std::to_string(cells) + " grid points");
+  const size_t m    = n + static_cast<size_t>(cells);
+  const size_t fast = fusedKernels ? nextFastLength(m) : 0;
+  return fast != 0 ? fast : m;
+}
+
+double powerLawNepers(double alphaCoeff, double y)
+{
+  return alphaCoeff * 100.0 * std::pow(1.0e-6 / (2.0 * kPi), y) / (20.0 * std::log10(std::exp(1.0)));
+}
+
+double powerLawDamping(double a, double c0, double y, double k)
+{
+  if (!(a > 0.0) || !(k > 0.0)) return 1.0;
+  const double T = y == 2.0 ? 0.0 : std::tan(kPi * y / 2.0);
+  const double g = a * std::pow(c0, y) * std::pow(k, y - 1.0);
+  return 1.0 - 2.0 * g * T - g * g;
 }
 } // namespace GridRule

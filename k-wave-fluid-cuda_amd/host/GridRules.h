@@ -1,5 +1,5 @@
 // GridRules.h — the parameter rules that the operators with their own context share (CwParameters, AngularParameters,
-// AngularTimeParameters, PlaneReconParameters, LineReconParameters, SecondOrderParameters): the refusal that names the parameter, the size and sign checks, the fused
+// AngularTimeParameters, PlaneReconParameters, LineReconParameters, SecondOrderParameters, SecondOrderFramesParameters): the refusal that names the parameter, the size and sign checks, the fused
 // pipeline's line lengths and the checks of an expanded grid.  No device call.
 #ifndef KW_HOST_GRID_RULES_H
 #define KW_HOST_GRID_RULES_H
@@ -36,5 +36,12 @@ void checkGivenSides(size_t nx, size_t ny, size_t ex, size_t ey, bool requireEve
 /// the projectors' default sides: the fast-path length at or above 2 N on both axes; 2 N where an axis has none or with
 /// fusedKernels off
 void defaultDoubledSides(size_t nx, size_t ny, size_t& ex, size_t& ey, bool fusedKernels);
+/// the exact propagators' default side: N + ceil(reach / d) with reach = c0 t_max, and the fast-path length at or above it
+/// where there is one and it is wanted; refuses "t_max" when the reach is over 2^32 grid points
+size_t reachSide(size_t n, double d, double reach, bool fusedKernels);
+/// the exact propagators' absorption: a = alpha_coeff 100 (1e-6 / 2 pi)^y / (20 log10 e) [Np (rad/s)^-y m^-1], and
+/// B = 1 - 2 g T - g^2 with g = a c0^y k^(y-1), T = tan(pi y / 2) (0 for y = 2); B = 1 without absorption and at k = 0
+double powerLawNepers(double alphaCoeff, double y);
+double powerLawDamping(double a, double c0, double y, double k);
 } // namespace GridRule
 #endif

@@ -1,0 +1,61 @@
+// SecondOrderFrames.h — batched 2-D exact k-space propagator: F independent initial pressures p0[f][y][x] in a homogeneous
+// medium, lossless or power-law absorbing, to the pressure of each at any time with no time loop (DESIGN.md "Exact k-space
+// propagator on frames") — SecondOrder with the z axis removed and the frame count in its place.  Owns its context through
+// a DeviceGrid: the fused pipeline in frames mode (the z axis of the constants is the batch) where wanted and supported,
+// the batched 2-D rocFFT plans otherwise.
+//
+//   setP0: embed every p0 into its zero-filled plane Ey x Ex (kw_angular_time_embed, the frame in the slowest position),
+//         transform once and keep — fast path: kw_fused_second_order_frames_forward; others: kw_fft_r2c_frames
+//   field(t): fast path: kw_fused_second_order_frames_time; others: kw_second_order_frames_mix and kw_fft_c2r_frames — then
+//         the crop to the domain (kw_plane_recon_crop), which stays on the device
+//   run(times): SecondOrder's loop: per time the passes, the sample at the sensor points of every frame into row i of the
+//         record [n_times][F][n_sensor] (kw_sample_index on the expanded batch, indices translated once) and, where asked
+//         for, the crop and kw_sample_all into the running max, min, sum of squares and the final field.
+//
+// Device memory, E = Ex Ey F points, R = (Ex/2 + 1) Ey F bins, N = Nx Ny F: the batch 4 E, the kept spectrum (8 R; a scratch
+// array on the fast path) and the pipeline's scratch arrays (fast path) or one more spectrum 8 R (rocFFT); the crop 4 N and
+// 4 N per aggregate; the record 4 n_times F n_sensor.
+#ifndef KW_HOST_SECOND_ORDER_FRAMES_H
+#define KW_HOST_SECOND_ORDER_FRAMES_H
+#include <string>
+
+#include "DeviceGrid.h"
+#include "SecondOrderFramesParameters.h"
+
+class SecondOrderFrames
+{
+ public:
+  explicit SecondOrderFrames(const SecondOrderFramesParameters& parameters);
+  SecondOrderFrames(const SecondOrderFrames&) = delete;
+  SecondOrderFrames& operator=(const SecondOrderFrames&) = delete;
+
+  /// p0: Nx Ny F floats on the host, [F][Ny][Nx]; may be called again
+  void setP0(const float* p0);
+  /// every frame's pressure at time t on the domain; dst: Nx Ny F floats on the host or NULL (the crop stays on the device)
+  void field(double t, float* dst);
+  /// every time in the given order: the record's row, the aggregates
+  void run(const double* times, size_t nTimes);
+  /// "p_raw" [n_times][F][n_sensor], "p_max", "p_min", "p_rms", "p_final" of the last run, "p" (the last field computed)
+  void get(const std::string& name, float* dst, size_t n);
+  bool    usesFusedPipeline() const { return mGrid.fused(); }
+  size_t  runs() const { return mRuns; }
+  kw_ctx* context() const { return mGrid.ctx(); }
+  const SecondOrderFramesParameters& parameters() const { return mPar; }
+
+ private:
+  void propagate(double t); // mVol <- the expanded fields at time t
+  void crop();              // mP <- the domain corner of every plane of mVol
+
+  SecondOrderFramesParameters mPar;
+  DeviceGrid mGrid; // the context, the pipeline and every device array below
+  bool       mHaveInput = false, mHaveField = false;
+  size_t     mRuns = 0, mTimes = 0, mRawCapacity = 0;
+  float*     mVol = nullptr;    // F Ey Ex: the embedded p0, then each time's fields
+  float*     mKept = nullptr;   // the kept spectra
+  float*     mSpec = nullptr;   // rocFFT path: the spectra of one time
+  float*     mP = nullptr;      // the domain: p0 as handed in, then the crop
+  uint64_t*  mIndex = nullptr;  // the sensor points of every frame in the expanded batch
+  float*     mRaw = nullptr;    // [n_times][F][n_sensor]
+  float     *mMax = nullptr, *mMin = nullptr, *mRms = nullptr, *mFinal = nullptr; // the domain each, where asked for
+};
+#endif

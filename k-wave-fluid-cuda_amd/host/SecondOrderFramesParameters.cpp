@@ -1,5 +1,5 @@
-// SecondOrderParameters.cpp — validation of an exact k-space propagation and its size rules (no device call).
-#include "SecondOrderParameters.h"
+// SecondOrderFramesParameters.cpp — validation of a batched 2-D exact k-space propagation and its size rules (no device call).
+#include "SecondOrderFramesParameters.h"
 
 #include <algorithm>
 #include <cmath>
@@ -11,64 +11,51 @@ using namespace GridRule;
 namespace
 {
 const double kPi = 3.14159265358979323846;
-
+const size_t kFramesMax = 65535; // the frame is a block index of the fused pass (csrc/kw_fused_main.hip kw_fused_supported)
 } // namespace
 
-void SecondOrderParameters::checkTime(double t)
-{
-  if (!(t >= 0.0) || !std::isfinite(t)) refuse("t", std::to_string(t) + " is not a time >= 0");
-}
-
-double SecondOrderParameters::damping(double k) const { return powerLawDamping(a, c0, alphaPower, k); }
-
-void SecondOrderParameters::init(const DeviceOptions& opt)
+void SecondOrderFramesParameters::init(const DeviceOptions& opt)
 {
   options = opt;
   checkSize(nx, "Nx");
   checkSize(ny, "Ny");
-  checkSize(nz, "Nz");
+  if (frames == 0) refuse("frames", "0 is not a number of frames");
+  if (frames > kFramesMax)
+    refuse("frames", std::to_string(frames) + " is above " + std::to_string(kFramesMax) + ", the most one batch takes");
   checkPositive(dx, "dx", "spacing");
   checkPositive(dy, "dy", "spacing");
-  checkPositive(dz, "dz", "spacing");
   checkPositive(c0, "c0", "sound speed");
   if (!(alphaCoeff >= 0.0) || !std::isfinite(alphaCoeff))
     refuse("alpha_coeff", std::to_string(alphaCoeff) + " is not an absorption >= 0 in dB/(MHz^y cm)");
   if (!(alphaPower >= 0.0) || !(alphaPower < 3.0) || alphaPower == 1.0)
     refuse("alpha_power", std::to_string(alphaPower) + " is outside the power law's range 0 <= y < 3, y != 1");
 
-  if (ex == 0 && ey == 0 && ez == 0)
+  if (ex == 0 && ey == 0)
   {
     checkPositive(tMax, "t_max", "time (the default expanded sides are sized by it)");
     const double reach = c0 * tMax;
     ex = reachSide(nx, dx, reach, options.fusedKernels);
     ey = reachSide(ny, dy, reach, options.fusedKernels);
-    ez = reachSide(nz, dz, reach, options.fusedKernels);
   }
-  else
-  {
-    checkGivenSides(nx, ny, ex, ey, false);
-    if (ez == 0) refuse("Ez", "missing while the other sides of the expanded grid are given");
-    if (ez < nz) refuse("Ez", std::to_string(ez) + " is below N = " + std::to_string(nz));
-    if (ez >= (1ull << 31)) refuse("Ez", std::to_string(ez) + " is not a grid size");
-  }
-  checkTotal(ex, ey, ez);
-  fastPath = options.fusedKernels && isFastLength(ex) && isFastLength(ey) && isFastLength(ez);
-  tFree = std::min({ static_cast<double>(ex - nx) * dx, static_cast<double>(ey - ny) * dy, static_cast<double>(ez - nz) * dz }) / c0;
+  else checkGivenSides(nx, ny, ex, ey, false);
+  checkTotal(ex, ey, frames);
+  fastPath = options.fusedKernels && isFastLength(ex) && isFastLength(ey);
+  tFree = std::min(static_cast<double>(ex - nx) * dx, static_cast<double>(ey - ny) * dy) / c0;
 
-  const size_t n = nDomain();
+  const size_t n = nPlane();
   for (size_t i = 0; i < sensorIndex.size(); i++)
     if (sensorIndex[i] >= n)
       refuse("sensor_index", "sensor_index[" + std::to_string(i) + "] = " + std::to_string(sensorIndex[i]) +
-                               " is outside the domain of " + std::to_string(n) + " points");
+                               " is outside the plane of " + std::to_string(n) + " points");
 
   a = powerLawNepers(alphaCoeff, alphaPower);
   bSmallest = bLargest = 1.0;
   if (a > 0.0)
   {
-    const size_t e[3] = { ex, ey, ez };
-    const double d[3] = { dx, dy, dz };
+    const size_t e[2] = { ex, ey };
+    const double d[2] = { dx, dy };
     double kSmallest = 0.0, k2Largest = 0.0;
-    for (int i = 0; i < 3; i++)
+    for (int i = 0; i < 2; i++)
     {
       const double dk = 2.0 * kPi / (static_cast<double>(e[i]) * d[i]);
       if (e[i] > 1 && (kSmallest == 0.0 || dk < kSmallest)) kSmallest = dk;
@@ -85,14 +72,15 @@ void SecondOrderParameters::init(const DeviceOptions& opt)
   }
 }
 
-std::vector<uint64_t> SecondOrderParameters::expandedSensorIndex() const
+std::vector<uint64_t> SecondOrderFramesParameters::expandedSensorIndex() const
 {
-  std::vector<uint64_t> out(sensorIndex.size());
-  for (size_t i = 0; i < out.size(); i++)
-  {
-    const uint64_t s = sensorIndex[i];
-    const uint64_t x = s % nx, y = (s / nx) % ny, z = s / (nx * ny);
-    out[i] = (z * ey + y) * ex + x;
-  }
+  const size_t ns = sensorIndex.size();
+  std::vector<uint64_t> out(ns * frames);
+  for (size_t f = 0; f < frames; f++)
+    for (size_t i = 0; i < ns; i++)
+    {
+      const uint64_t s = sensorIndex[i];
+      out[f * ns + i] = (f * ey + s / nx) * ex + s % nx;
+    }
   return out;
 }

@@ -17,6 +17,7 @@
 #include "LineRecon.h"
 #include "PlaneRecon.h"
 #include "SecondOrder.h"
+#include "SecondOrderFrames.h"
 #include "kwave_host.h"
 
 static thread_local std::string g_err;
@@ -255,6 +256,33 @@ static SecondOrderParameters kwh_second_order_parameters(const kwh_second_order_
   p.alphaPower = c->alpha_power;
   p.tMax = c->t_max;
   p.ex = c->ex; p.ey = c->ey; p.ez = c->ez;
+  if (c->n_sensor != 0 && c->sensor_index == nullptr) throw std::invalid_argument("sensor_index: NULL with n_sensor > 0");
+  if (c->n_sensor != 0) p.sensorIndex.assign(c->sensor_index, c->sensor_index + c->n_sensor);
+  p.pMax   = (c->flags & KWH_SECOND_ORDER_P_MAX) != 0;
+  p.pMin   = (c->flags & KWH_SECOND_ORDER_P_MIN) != 0;
+  p.pRms   = (c->flags & KWH_SECOND_ORDER_P_RMS) != 0;
+  p.pFinal = (c->flags & KWH_SECOND_ORDER_P_FINAL) != 0;
+  p.init(kwh_device_options(o));
+  return p;
+}
+
+/// a batched 2-D exact k-space propagator with its completed parameters
+struct kwh_second_order_frames
+{
+  SecondOrderFramesParameters        params;
+  std::unique_ptr<SecondOrderFrames> propagator;
+};
+
+static SecondOrderFramesParameters kwh_second_order_frames_parameters(const kwh_second_order_frames_config* c, const kwh_options* o)
+{
+  SecondOrderFramesParameters p;
+  p.nx = c->nx; p.ny = c->ny; p.frames = c->frames;
+  p.dx = c->dx; p.dy = c->dy;
+  p.c0 = c->c0;
+  p.alphaCoeff = c->alpha_coeff;
+  p.alphaPower = c->alpha_power;
+  p.tMax = c->t_max;
+  p.ex = c->ex; p.ey = c->ey;
   if (c->n_sensor != 0 && c->sensor_index == nullptr) throw std::invalid_argument("sensor_index: NULL with n_sensor > 0");
   if (c->n_sensor != 0) p.sensorIndex.assign(c->sensor_index, c->sensor_index + c->n_sensor);
   p.pMax   = (c->flags & KWH_SECOND_ORDER_P_MAX) != 0;
@@ -1065,4 +1093,81 @@ int kwh_second_order_get_scalar(kwh_second_order* s, const char* name, double* o
 }
 
 void* kwh_second_order_context(kwh_second_order* s) { return s ? s->propagator->context() : nullptr; }
+
+// ---- batched 2-D exact k-space propagator -----------------------------------------------------------------------------
+int kwh_second_order_frames_plan(const kwh_second_order_frames_config* config, const kwh_options* o, uint64_t out_expanded[2],
+                                 int32_t* out_fast_path)
+{
+  KWH_TRY
+  if (!config || !o) throw std::invalid_argument("kwh_second_order_frames_plan: NULL argument");
+  const SecondOrderFramesParameters p = kwh_second_order_frames_parameters(config, o);
+  if (out_expanded) { out_expanded[0] = p.ex; out_expanded[1] = p.ey; }
+  if (out_fast_path) *out_fast_path = p.fastPath ? 1 : 0;
+  KWH_CATCH
+}
+
+int kwh_second_order_frames_create(const kwh_second_order_frames_config* config, const kwh_options* o, kwh_second_order_frames** out)
+{
+  return kwh_create_handle("kwh_second_order_frames_create", config, o, out, [&](kwh_second_order_frames& s) {
+    s.params = kwh_second_order_frames_parameters(config, o);
+    s.propagator.reset(new SecondOrderFrames(s.params));
+  });
+}
+
+int kwh_second_order_frames_destroy(kwh_second_order_frames* s)
+{
+  KWH_TRY
+  delete s;
+  KWH_CATCH
+}
+
+int kwh_second_order_frames_set_p0(kwh_second_order_frames* s, const float* p0)
+{
+  KWH_TRY
+  if (!s || !p0) throw std::invalid_argument("kwh_second_order_frames_set_p0: NULL argument");
+  s->propagator->setP0(p0);
+  KWH_CATCH
+}
+
+int kwh_second_order_frames_field(kwh_second_order_frames* s, double t, float* dst)
+{
+  KWH_TRY
+  if (!s) throw std::invalid_argument("kwh_second_order_frames_field: NULL propagator");
+  s->propagator->field(t, dst);
+  KWH_CATCH
+}
+
+int kwh_second_order_frames_run(kwh_second_order_frames* s, const double* times, uint64_t n_times)
+{
+  KWH_TRY
+  if (!s || (!times && n_times != 0)) throw std::invalid_argument("kwh_second_order_frames_run: NULL argument");
+  s->propagator->run(times, n_times);
+  KWH_CATCH
+}
+
+int kwh_second_order_frames_get(kwh_second_order_frames* s, const char* name, float* dst, uint64_t n)
+{
+  KWH_TRY
+  if (!s || !name || (!dst && n != 0)) throw std::invalid_argument("kwh_second_order_frames_get: NULL argument");
+  s->propagator->get(name, dst, n);
+  KWH_CATCH
+}
+
+int kwh_second_order_frames_get_scalar(kwh_second_order_frames* s, const char* name, double* out)
+{
+  KWH_TRY
+  if (!s || !name || !out) throw std::invalid_argument("kwh_second_order_frames_get_scalar: NULL argument");
+  const std::string n(name);
+  const SecondOrderFramesParameters& p = s->propagator->parameters();
+  if (n == "fused_pipeline") *out = s->propagator->usesFusedPipeline() ? 1.0 : 0.0;
+  else if (n == "Ex") *out = static_cast<double>(p.ex);
+  else if (n == "Ey") *out = static_cast<double>(p.ey);
+  else if (n == "frames") *out = static_cast<double>(p.frames);
+  else if (n == "t_free") *out = p.tFree;
+  else if (n == "runs") *out = static_cast<double>(s->propagator->runs());
+  else throw std::invalid_argument(std::string("unknown scalar ") + name);
+  KWH_CATCH
+}
+
+void* kwh_second_order_frames_context(kwh_second_order_frames* s) { return s ? s->propagator->context() : nullptr; }
 }

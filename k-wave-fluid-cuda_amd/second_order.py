@@ -7,9 +7,13 @@ snapshot at t = 40 us costs two transforms, a sensor record three passes per sam
 periodic; `t_free` is the time up to which the result inside the domain is the free-space one.  No CPU fallback: a missing
 library or device raises.
 
-Not built: dp0/dt as a second initial condition and time-varying sources, heterogeneous media, 2-D (Nz == 1) and its batched
-form, Z-slabs, HDF5 files and the command line, graphs, several output times per z-pass, inverse passes restricted to the
-crop or to the sensor points, particle velocity outputs.
+`SecondOrderFrames` is its batched 2-D form (kwave_host.h "Exact k-space propagator on frames"): F independent images
+p0(x, y) that share the medium, the expanded plane, the output times and the sensor points, each carried to any time by one
+2-D round trip — what a linear array records for many phantoms, the forward side of `recon.LineRecon`.
+
+Not built: dp0/dt as a second initial condition and time-varying sources, heterogeneous media, Z-slabs, chunks of frames and
+frames over several GPUs, HDF5 files and the command line, graphs, several output times per pass, inverse passes restricted
+to the crop, to the sensor points or to the rows that hold sensors, particle velocity outputs.
 """
 from __future__ import annotations
 
@@ -33,46 +37,69 @@ class Config(C.Structure):
                 ("sensor_index", C.POINTER(C.c_uint64)), ("flags", C.c_int32), ("pad_", C.c_int32)]
 
 
+class FramesConfig(C.Structure):
+    """struct kwh_second_order_frames_config"""
+    _fields_ = [("nx", C.c_uint64), ("ny", C.c_uint64), ("frames", C.c_uint64), ("dx", C.c_double), ("dy", C.c_double),
+                ("c0", C.c_double), ("alpha_coeff", C.c_double), ("alpha_power", C.c_double), ("t_max", C.c_double),
+                ("ex", C.c_uint64), ("ey", C.c_uint64), ("n_sensor", C.c_uint64), ("sensor_index", C.POINTER(C.c_uint64)),
+                ("flags", C.c_int32), ("pad_", C.c_int32)]
+
+
 def _lib() -> C.CDLL:
     global _bound
     L = load_host()
     if not _bound:
-        L.kwh_second_order_plan.argtypes = [C.POINTER(Config), C.POINTER(Options), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]
-        L.kwh_second_order_create.argtypes = [C.POINTER(Config), C.POINTER(Options), C.POINTER(C.c_void_p)]
-        L.kwh_second_order_destroy.argtypes = [C.c_void_p]
-        L.kwh_second_order_set_p0.argtypes = [C.c_void_p, C.c_void_p]
-        L.kwh_second_order_field.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
-        L.kwh_second_order_run.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_uint64]
-        L.kwh_second_order_get.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint64]
-        L.kwh_second_order_get_scalar.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_double)]
-        L.kwh_second_order_context.restype = C.c_void_p
-        L.kwh_second_order_context.argtypes = [C.c_void_p]
+        for name, cfg in (("kwh_second_order", Config), ("kwh_second_order_frames", FramesConfig)):
+            fn = lambda what: getattr(L, name + "_" + what)
+            fn("plan").argtypes = [C.POINTER(cfg), C.POINTER(Options), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]
+            fn("create").argtypes = [C.POINTER(cfg), C.POINTER(Options), C.POINTER(C.c_void_p)]
+            fn("destroy").argtypes = [C.c_void_p]
+            fn("set_p0").argtypes = [C.c_void_p, C.c_void_p]
+            fn("field").argtypes = [C.c_void_p, C.c_double, C.c_void_p]
+            fn("run").argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_uint64]
+            fn("get").argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint64]
+            fn("get_scalar").argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_double)]
+            fn("context").restype = C.c_void_p
+            fn("context").argtypes = [C.c_void_p]
         _bound = True
     return L
 
 
-def _config(n, d, c0, alpha_coeff, alpha_power, t_max, expanded, sensor_index, record):
+def _config(n, d, c0, alpha_coeff, alpha_power, t_max, expanded, sensor_index, record, frames=None):
+    """the 3-D config, or with `frames` the batched 2-D one; the sensor indices are returned to keep them alive"""
     n = tuple(int(v) for v in n)
     d = tuple(float(v) for v in d)
-    if len(n) != 3 or len(d) != 3:
-        raise ValueError("n = (Nx, Ny, Nz) and d = (dx, dy, dz)")
+    axes = 3 if frames is None else 2
+    if len(n) != axes or len(d) != axes:
+        raise ValueError("n = (Nx, Ny, Nz) and d = (dx, dy, dz)" if axes == 3 else "n = (Nx, Ny) and d = (dx, dy)")
     if min(n) < 0:
         raise ValueError(f"n must not be negative, got {n}")
     record = (record,) if isinstance(record, str) else tuple(record)
     unknown = [r for r in record if r not in RECORDS]
     if unknown:
         raise ValueError(f"record: {unknown} not among {RECORDS}")
-    c = Config()
-    c.nx, c.ny, c.nz = n
-    c.dx, c.dy, c.dz = d
+    if axes == 3:
+        c = Config()
+        c.nx, c.ny, c.nz = n
+        c.dx, c.dy, c.dz = d
+    else:
+        if int(frames) < 0:
+            raise ValueError(f"frames must not be negative, got {frames}")
+        c = FramesConfig()
+        c.nx, c.ny = n
+        c.dx, c.dy = d
+        c.frames = int(frames)
     c.c0 = float(c0)
     c.alpha_coeff, c.alpha_power = float(alpha_coeff), float(alpha_power)
     c.t_max = 0.0 if t_max is None else float(t_max)
     if expanded is not None:
         expanded = tuple(int(v) for v in expanded)
-        if len(expanded) != 3 or min(expanded) < 0:
-            raise ValueError("expanded = (Ex, Ey, Ez)")
-        c.ex, c.ey, c.ez = expanded
+        if len(expanded) != axes or min(expanded) < 0:
+            raise ValueError("expanded = (Ex, Ey, Ez)" if axes == 3 else "expanded = (Ex, Ey)")
+        if axes == 3:
+            c.ex, c.ey, c.ez = expanded
+        else:
+            c.ex, c.ey = expanded
     idx = np.zeros(0, dtype=np.uint64)
     if sensor_index is not None and "p_raw" in record:
         s = np.asarray(sensor_index).reshape(-1)
@@ -96,20 +123,28 @@ class SecondOrder:
 
     set_p0(p0), then field(t) -> (Nz, Ny, Nx) or run(times) -> the record (n_times, n_sensor); times in any order."""
 
+    _ENTRY = "kwh_second_order"   # the C entry points' common name (SecondOrderFrames: its own)
+
     def __init__(self, n, d, c0, alpha_coeff=0.0, alpha_power=1.5, t_max=None, expanded=None, sensor_index=None,
                  record=("p_raw",), fused_kernels=True, device_idx=-1):
-        L = _lib()
         c, idx = _config(n, d, c0, alpha_coeff, alpha_power, t_max, expanded, sensor_index, record)
+        self._create(c, idx, fused_kernels, device_idx)
+        self.nx, self.ny, self.nz = int(c.nx), int(c.ny), int(c.nz)
+
+    def _create(self, c, idx, fused_kernels, device_idx):
+        self.L, self._h = _lib(), None
         o = Options()
         o.device_idx = int(device_idx)
         o.fused_kernels = int(bool(fused_kernels))
-        self.L, self._h = L, None
         h = C.c_void_p()
-        _check(L.kwh_second_order_create(C.byref(c), C.byref(o), C.byref(h)))
+        _check(self._fn("create")(C.byref(c), C.byref(o), C.byref(h)))
         self._h = h
-        self.nx, self.ny, self.nz = int(c.nx), int(c.ny), int(c.nz)
         self.n_sensor = int(idx.size)
         self.n_times = 0
+
+    @classmethod
+    def _fn(cls, what: str):
+        return getattr(_lib(), cls._ENTRY + "_" + what)
 
     @staticmethod
     def plan(n, d, c0, alpha_coeff=0.0, alpha_power=1.5, t_max=None, expanded=None, sensor_index=None, record=("p_raw",),
@@ -125,7 +160,7 @@ class SecondOrder:
 
     def _scalar(self, name: str) -> float:
         v = C.c_double()
-        _check(self.L.kwh_second_order_get_scalar(self._h, name.encode(), C.byref(v)))
+        _check(self._fn("get_scalar")(self._h, name.encode(), C.byref(v)))
         return float(v.value)
 
     @property
@@ -151,11 +186,11 @@ class SecondOrder:
 
     @property
     def ctx(self):
-        return C.c_void_p(self.L.kwh_second_order_context(self._h))
+        return C.c_void_p(self._fn("context")(self._h))
 
     def _get(self, name: str, shape) -> np.ndarray:
         out = np.empty(shape, dtype=np.float32)
-        _check(self.L.kwh_second_order_get(self._h, name.encode(), out.ctypes.data, out.size))
+        _check(self._fn("get")(self._h, name.encode(), out.ctypes.data, out.size))
         return out
 
     def set_p0(self, p0):
@@ -164,22 +199,24 @@ class SecondOrder:
         if a.shape != self.shape:
             raise ValueError(f"p0 must be (Nz, Ny, Nx) = {self.shape}, got {a.shape}")
         a = np.ascontiguousarray(a)
-        _check(self.L.kwh_second_order_set_p0(self._h, a.ctypes.data))
+        _check(self._fn("set_p0")(self._h, a.ctypes.data))
 
     def field(self, t: float) -> np.ndarray:
         """the pressure at time t [s] on the domain: float32 (Nz, Ny, Nx)"""
         out = np.empty(self.shape, dtype=np.float32)
-        _check(self.L.kwh_second_order_field(self._h, float(t), out.ctypes.data))
+        _check(self._fn("field")(self._h, float(t), out.ctypes.data))
         return out
 
     def run(self, times) -> np.ndarray:
         """every time of `times` [s] in the given order; returns the record float32 (n_times, n_sensor)"""
         ta = np.ascontiguousarray(np.asarray(times, dtype=np.float64).reshape(-1))
-        _check(self.L.kwh_second_order_run(self._h, ta.ctypes.data_as(C.POINTER(C.c_double)), ta.size))
+        _check(self._fn("run")(self._h, ta.ctypes.data_as(C.POINTER(C.c_double)), ta.size))
         self.n_times = int(ta.size)
-        if self.n_sensor == 0:
-            return np.empty((self.n_times, 0), dtype=np.float32)
-        return self._get("p_raw", (self.n_times, self.n_sensor))
+        shape = self._record_shape()
+        return self._get("p_raw", shape) if self.n_sensor != 0 else np.empty(shape, dtype=np.float32)
+
+    def _record_shape(self):
+        return (self.n_times, self.n_sensor)
 
     def p_max(self) -> np.ndarray:
         """max over the output times of the last run"""
@@ -199,7 +236,7 @@ class SecondOrder:
 
     def close(self):
         if getattr(self, "_h", None):
-            self.L.kwh_second_order_destroy(self._h)
+            self._fn("destroy")(self._h)
             self._h = None
 
     def __del__(self):
@@ -207,3 +244,56 @@ class SecondOrder:
             self.close()
         except Exception:
             pass
+
+
+class SecondOrderFrames(SecondOrder):
+    """The pressure at any time from F independent initial pressures p0 (F, Ny, Nx) (x fastest) in one homogeneous medium:
+    SecondOrder in 2-D, batched — one pass serves all frames.
+
+    n = (Nx, Ny), d = (dx, dy) [m], c0 [m/s], frames = F (at most 65535).  alpha_coeff, alpha_power, t_max, record: as
+    SecondOrder, the B rule on the 2-D grid.  expanded = (Ex, Ey) gives the sides of the periodic plane (default: per axis the
+    smallest fast-path length >= N + ceil(c0 t_max / d)).  sensor_index: 0-based flat indices into ONE (Ny, Nx) plane,
+    sampled in every frame by run() — a row of the plane is a linear array.
+
+    set_p0(p0) takes (F, Ny, Nx), or (Ny, Nx) when frames == 1; field(t) -> (F, Ny, Nx); run(times) -> the record
+    (n_times, F, n_sensor), times in any order; p_max() / p_min() / p_rms() / p_final() -> (F, Ny, Nx)."""
+
+    _ENTRY = "kwh_second_order_frames"
+
+    def __init__(self, n, d, c0, frames, alpha_coeff=0.0, alpha_power=1.5, t_max=None, expanded=None, sensor_index=None,
+                 record=("p_raw",), fused_kernels=True, device_idx=-1):
+        c, idx = _config(n, d, c0, alpha_coeff, alpha_power, t_max, expanded, sensor_index, record, frames=frames)
+        self._create(c, idx, fused_kernels, device_idx)
+        self.nx, self.ny, self.frames = int(c.nx), int(c.ny), int(c.frames)
+
+    @staticmethod
+    def plan(n, d, c0, frames, alpha_coeff=0.0, alpha_power=1.5, t_max=None, expanded=None, sensor_index=None,
+             record=("p_raw",), fused_kernels=True) -> Tuple[Tuple[int, int], bool]:
+        """((Ex, Ey), fast path), validated as the constructor would, without a device"""
+        c, _idx = _config(n, d, c0, alpha_coeff, alpha_power, t_max, expanded, sensor_index, record, frames=frames)
+        o = Options()
+        o.fused_kernels = int(bool(fused_kernels))
+        e, fast = (C.c_uint64 * 2)(), C.c_int32()
+        _check(SecondOrderFrames._fn("plan")(C.byref(c), C.byref(o), e, C.byref(fast)))
+        return (int(e[0]), int(e[1])), bool(fast.value)
+
+    @property
+    def shape(self):
+        return (self.frames, self.ny, self.nx)
+
+    @property
+    def expanded(self) -> Tuple[int, int]:
+        return tuple(int(self._scalar(n)) for n in ("Ex", "Ey"))
+
+    def set_p0(self, p0):
+        """embed, transform and keep the initial pressures (F, Ny, Nx); (Ny, Nx) for a single frame; may be called again"""
+        a = np.asarray(p0, dtype=np.float32)
+        if self.frames == 1 and a.shape == self.shape[1:]:
+            a = a[None]
+        if a.shape != self.shape:
+            raise ValueError(f"p0 must be (F, Ny, Nx) = {self.shape}, got {a.shape}")
+        a = np.ascontiguousarray(a)
+        _check(self._fn("set_p0")(self._h, a.ctypes.data))
+
+    def _record_shape(self):
+        return (self.n_times, self.frames, self.n_sensor)

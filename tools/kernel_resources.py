@@ -27,7 +27,8 @@ def main():
     extra = sys.argv[2:]
     with tempfile.TemporaryDirectory() as tmp, concurrent.futures.ThreadPoolExecutor(8) as pool:
         # the fused pipeline's code objects, and those of the CW propagator and the angular-spectrum projectors (the pair
-        # z-pass, the CW projector's y-inverse, the time-domain projector's z-pass, the exact propagator's z-pass, the plane reconstruction's z-pass and
+        # z-pass, the CW projector's y-inverse, the time-domain projector's z-pass, the exact propagator's z-pass k_zfused_second_order and its
+        # batched 2-D pass along y k_yfused_second_order, the plane reconstruction's z-pass and
         # the line reconstruction's pass along t are kernels of that pipeline)
         srcs = sorted(glob.glob(os.path.join(CSRC, "kw_fused_*.hip"))) + [os.path.join(CSRC, "kw_cw.hip"),
                                                                           os.path.join(CSRC, "kw_angular.hip"),
