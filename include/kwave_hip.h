@@ -1039,8 +1039,8 @@ KW_API kw_status kw_second_order_mix(kw_ctx* ctx, float* out_spec, const float* 
  * Embedding and crop: kw_angular_time_embed and kw_plane_recon_crop with the frame count in the slowest position.  The
  * record: kw_sample_index on the expanded batch; the aggregates: kw_sample_all on the crop.
  * Not built: dp0/dt as a second initial condition and time-varying sources, heterogeneous media, chunks of frames and
- * frames over several GPUs, several output times per pass, an x-inverse restricted to the rows that hold sensors (the
- * efficient form for a line sensor), particle velocity.
+ * frames over several GPUs, particle velocity.  Several output times per pass and an x-inverse restricted to the rows that
+ * hold sensors: served for a single row by the line-sensor record below, not otherwise.
  * ---------------------------------------------------------------------------------------------------------------- */
 KW_API kw_status kw_fused_second_order_frames_elems(kw_ctx* ctx, size_t* out_elems);
 KW_API kw_status kw_fused_second_order_frames_forward(kw_ctx* ctx, const float* vol, float* kept);
@@ -1048,6 +1048,38 @@ KW_API kw_status kw_fused_second_order_frames_time(kw_ctx* ctx, const float* kep
                                                    float* vol_out);
 KW_API kw_status kw_second_order_frames_mix(kw_ctx* ctx, float* out_spec, const float* spec, const kw_second_order_op* op,
                                             float divider);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Line-sensor record of the propagator on frames: what the row y = r dy of every frame records at many output times, with
+ * no y-inverse and no x-inverse over the plane (csrc/kw_second_order_line.hip, host/SecondOrderFrames.cpp, DESIGN.md
+ * "Line-sensor record of the propagator on frames").  Any context with constants (nx, ny, nz) = (Ex, Ey, F), any sizes,
+ * odd ones included; the fused pipeline plays no part.
+ *     p_f(x, y_r; t) = irfft_x[ G_f(kx; t) ],  kx = 0 ... Ex/2
+ *     G_f(kx; t)     = sum over m = 0 ... Ey/2 of H(kx, m; t) Q_f(kx, m)
+ *     Q_f(kx, m)     = q_f(kx, m) + q_f(kx, Ey - m);  bins 0 and (Ey even) Ey/2 pair with themselves: q_f(kx, m) alone
+ *     q_f(kx, ky)    = rfft2(p0_f embedded)(kx, ky) exp(+2 pi i ky r / Ey) / (Ex Ey)
+ * H is the H of the section above, which depends on ky through min(ky, Ey - ky) only.
+ *
+ * kw_second_order_line_elems: complex values of Q: (Ex/2 + 1) (Ey/2 + 1) F.
+ * kw_second_order_line_prepare: q [Ex/2 + 1][Ey/2 + 1][F] <- the natural [F][Ey][Ex/2 + 1] spectra of kw_fft_r2c_frames.
+ *   The phase of bin ky: the integer (ky r) mod Ey exactly, angle = 2 pi (that / Ey) and its cosine and sine in float64,
+ *   each rounded to float32 once; q = ((X * phase) * divider) in float32 without contraction, divider = float(1 / (Ex Ey));
+ *   the fold adds the two terms.  row < Ey; Ey/2 + 1 <= 65535 (a block index).
+ * kw_second_order_line_record: g [F][n_times][Ex/2 + 1] (float2) <- Q, op (op->t is not looked at, op->dz neither) and the
+ *   DEVICE array times [n_times] of float64 seconds, each >= 0 and finite (the caller checks them; the kernel reads no
+ *   other memory by them), in any order.  ct = c0 * t in float64; per bin second_h's float64 expressions in its order —
+ *   ((k * r) * ct) / 2 pi to the phase word, ((k * g) * ct) * log2(e), g / r, the three power paths, H = 1 at k = 0, no
+ *   contraction — with the factors that do not depend on time formed once per bin and block (no table in memory).
+ *   An accumulator takes its bins in ascending m, one fmaf(H, Q, acc) each, from zero: the bits of G_f(kx; t) do not depend
+ *   on F, on the other times of the call or on n_times.  No atomics; nothing of size Ex Ey n_times exists.
+ *   1 <= n_times <= 65535 * 256.
+ * The x-inverse: kw_fft_c2r_frames on a context with constants (Ex, 1, F n_times) (a batched 1-D plan), then
+ * kw_plane_recon_crop of Ex to Nx.
+ * ---------------------------------------------------------------------------------------------------------------- */
+KW_API kw_status kw_second_order_line_elems(kw_ctx* ctx, size_t* out_elems);
+KW_API kw_status kw_second_order_line_prepare(kw_ctx* ctx, float* q, const float* spec, uint32_t row);
+KW_API kw_status kw_second_order_line_record(kw_ctx* ctx, float* g, const float* q, const kw_second_order_op* op,
+                                             const double* times, uint32_t n_times);
 
 #ifdef __cplusplus
 }

@@ -544,8 +544,9 @@ KWH_API void*    kwh_second_order_context(kwh_second_order* s);
  * E (2^32 points or more), sensor_index (NULL, an entry outside the plane), t (negative or not finite), n_times (0).
  * flags: KWH_SECOND_ORDER_P_*.  kwh_second_order_frames_plan validates and completes (Ex, Ey) and the fast-path flag
  * without a device.  Not built: dp0/dt as a second initial condition and time-varying sources, heterogeneous media,
- * chunks of frames and frames over several GPUs, several output times per pass, an x-inverse restricted to the rows that
- * hold sensors (the efficient form for a line sensor), particle velocity outputs, HDF5 files and the command line, graphs.
+ * chunks of frames and frames over several GPUs, particle velocity outputs, HDF5 files and the command line, graphs.
+ * Several output times per pass and an x-inverse restricted to the rows that hold sensors: for one row, the line-sensor
+ * record below.
  * ---------------------------------------------------------------------------------------------------------------- */
 typedef struct kwh_second_order_frames kwh_second_order_frames;
 typedef struct kwh_second_order_frames_config
@@ -580,6 +581,31 @@ KWH_API int      kwh_second_order_frames_get(kwh_second_order_frames* s, const c
 KWH_API int      kwh_second_order_frames_get_scalar(kwh_second_order_frames* s, const char* name, double* out);
 /* the underlying kw_ctx* (include/kwave_hip.h) */
 KWH_API void*    kwh_second_order_frames_context(kwh_second_order_frames* s);
+
+/* The line-sensor record: the pressure on ONE row y = row dy of every frame at many output times — what a linear array along
+ * x records for F phantoms, the input of kwh_line_recon in its order "ty" with x as the array axis — without the y-inverse
+ * and without the x-inverse over the plane (kwave_hip.h "Line-sensor record of the propagator on frames"): per output time
+ * and kx one sum over the folded ky bins, then one batched 1-D inverse over the record itself.
+ *   set_line_row: 0 <= row < Ny, in effect from the next set_p0 on; -1 switches the record off and frees its arrays.
+ *     Refused as "line_row" otherwise.
+ *   set_line_chunk_times: how many output times one pass takes (it bounds G [F][times][Ex/2 + 1]); 0: the default, as many
+ *     as fit 256 MiB, one at the least.  Refused as "line_chunk_times" when Ex F times reaches 2^32.  The scalars
+ *     "line_row" and "line_chunk_times" report what is in effect.
+ *   line_record: dst [F][n_times][Nx] floats on the host, x fastest, or NULL (the passes run, nothing is copied); times in
+ *     any order, each >= 0 and finite; t = 0 gives the row of p0.  Refused: "line_record: no line row set", "line_record: no
+ *     p0 since the line row was set", n_times (0), t.  field, run and line_record may be interleaved: the record touches
+ *     neither "p" nor the aggregates and the record of run.  A value's bits do not depend on F, on the other times of the call
+ *     or on the passes.
+ *   line_plan: the checks of row, chunk_times and n_times without a device; out: the times of one pass, the passes of
+ *     n_times, the complex values of Q.
+ * Not built: several rows, columns, arbitrary sensor points, the plane-sensor record of the 3-D propagator, the order "yt",
+ * frames over several GPUs. */
+KWH_API int      kwh_second_order_frames_line_plan(const kwh_second_order_frames_config* config, const kwh_options* options,
+                                                   int64_t row, uint64_t chunk_times, uint64_t n_times, uint64_t out[3]);
+KWH_API int      kwh_second_order_frames_set_line_row(kwh_second_order_frames* s, int64_t row);
+KWH_API int      kwh_second_order_frames_set_line_chunk_times(kwh_second_order_frames* s, uint64_t times);
+KWH_API int      kwh_second_order_frames_line_record(kwh_second_order_frames* s, const double* times, uint64_t n_times,
+                                                     float* dst);
 
 #ifdef __cplusplus
 }

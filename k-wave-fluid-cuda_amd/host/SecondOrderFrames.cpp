@@ -1,7 +1,9 @@
 // SecondOrderFrames.cpp — the host side of the batched 2-D exact k-space propagator around the device library's
-// kw_second_order_frames_mix and kw_fused_second_order_frames_* entry points.
+// kw_second_order_frames_mix, kw_fused_second_order_frames_* and kw_second_order_line_* entry points.
 #include "SecondOrderFrames.h"
 
+#include <algorithm>
+#include <memory>
 #include <vector>
 
 #include "SecondOrderParameters.h"
@@ -45,9 +47,10 @@ void SecondOrderFrames::setP0(const float* p0)
   else mGrid.check(kw_fft_r2c_frames(context(), mVol, mKept));
   mHaveInput = true;
   mHaveField = false;
+  if (mLineRow >= 0) prepareLine(); // (after the fused forward has read mVol)
 }
 
-void SecondOrderFrames::propagate(double t)
+kw_second_order_op SecondOrderFrames::op(double t) const
 {
   kw_second_order_op op{};
   op.dx = mPar.dx; op.dy = mPar.dy; op.c0 = mPar.c0;
@@ -56,6 +59,12 @@ void SecondOrderFrames::propagate(double t)
   op.a  = mPar.a;
   op.alpha_power = mPar.alphaPower;
   op.absorbing   = mPar.a > 0.0 ? 1 : 0;
+  return op;
+}
+
+void SecondOrderFrames::propagate(double t)
+{
+  const kw_second_order_op op = this->op(t);
   if (mGrid.fused()) mGrid.check(kw_fused_second_order_frames_time(context(), mKept, &op, mVol));
   else
   {
@@ -114,6 +123,117 @@ void SecondOrderFrames::run(const double* times, size_t nTimes)
   if (mRms != nullptr) mGrid.check(kw_post_processing_rms(context(), mRms, 1.0f / static_cast<float>(nTimes), nd));
   mTimes = nTimes;
   mRuns++;
+}
+
+// ---- the line-sensor record ---------------------------------------------------------------------------------------------
+void SecondOrderFrames::freeLine()
+{
+  mLinePass.reset(); // its context, plans and arrays (after a sync of its own)
+  mLinePassTimes = 0;
+  mLineG = mLineRows = mLineOut = nullptr;
+  for (void* p : { static_cast<void*>(mLineQ), static_cast<void*>(mLineSpec), static_cast<void*>(mLineTimes) })
+    if (p != nullptr) mGrid.release(p);
+  mLineQ = mLineSpec = nullptr;
+  mLineTimes = nullptr;
+  mLineTimesCapacity = 0;
+  mLineReady = false;
+}
+
+void SecondOrderFrames::setLineRow(int64_t row)
+{
+  mPar.checkLineRow(row);
+  mLineRow   = row;
+  mLineReady = false; // the next setP0 prepares the row
+  if (row < 0)
+  {
+    mGrid.check(kw_sync(context()));
+    freeLine();
+  }
+}
+
+void SecondOrderFrames::setLineChunkTimes(uint64_t times)
+{
+  mPar.lineChunkTimes(times); // refuses what one pass cannot take
+  mLineChunkGiven = times;
+}
+
+void SecondOrderFrames::prepareLine()
+{
+  mLineReady = false;
+  if (mLineQ == nullptr) mLineQ = mGrid.array(2 * mPar.lineElems());
+  const float* spectra = mKept; // rocFFT path: the kept spectra are the natural (kx, ky) ones
+  if (mGrid.fused())
+  {
+    // the pipeline keeps (kx, y, frame) in its own layout: one batched 2-D transform of the embedded batch, which the
+    // fused forward has left as it was
+    if (!mLinePlans) mGrid.check(kw_fft_create_plans_frames(context()));
+    mLinePlans = true;
+    if (mLineSpec == nullptr) mLineSpec = mGrid.array(2 * mPar.nReduced());
+    mGrid.check(kw_fft_r2c_frames(context(), mVol, mLineSpec));
+    spectra = mLineSpec;
+  }
+  mGrid.check(kw_second_order_line_prepare(context(), mLineQ, spectra, static_cast<uint32_t>(mLineRow)));
+  mLineReady = true;
+}
+
+void SecondOrderFrames::makeLinePass(size_t times)
+{
+  if (mLinePass && mLinePassTimes == times) return;
+  mLinePass.reset();
+  mLinePassTimes = 0;
+  mLineG = mLineRows = mLineOut = nullptr;
+  const size_t rows = mPar.frames * times;
+  std::unique_ptr<DeviceGrid> pass(new DeviceGrid(mPar.options.deviceIdx));
+  pass->setConstants(gridConstants(mPar.ex, 1, rows));
+  pass->check(kw_fft_create_plans_frames(pass->ctx())); // ny == 1: batched 1-D plans of length Ex
+  float* g       = pass->array(2 * mPar.lineSpectrumElems(times));
+  float* rowsOut = pass->array(mPar.ex * rows);
+  float* cropped = pass->array(mPar.nx * rows);
+  // a last pass of fewer times transforms the whole batch: the rows past its own hold what an earlier pass left there
+  pass->check(kw_memset(pass->ctx(), g, 0, 2 * mPar.lineSpectrumElems(times) * sizeof(float)));
+  pass->check(kw_sync(pass->ctx()));
+  mLinePass = std::move(pass);
+  mLineG = g; mLineRows = rowsOut; mLineOut = cropped;
+  mLinePassTimes = times;
+}
+
+void SecondOrderFrames::lineRecord(const double* times, size_t nTimes, float* dst)
+{
+  if (mLineRow < 0) throw std::invalid_argument("line_record: no line row set");
+  if (!mLineReady) throw std::invalid_argument("line_record: no p0 since the line row was set");
+  const size_t chunkTimes = std::min(lineChunkTimes(), std::max<size_t>(nTimes, 1));
+  const std::vector<SecondOrderFramesParameters::LineChunk> chunks = SecondOrderFramesParameters::lineChunks(nTimes, chunkTimes);
+  for (size_t i = 0; i < nTimes; i++) SecondOrderParameters::checkTime(times[i]);
+
+  if (nTimes > mLineTimesCapacity)
+  {
+    if (mLineTimes != nullptr) mGrid.release(mLineTimes);
+    mLineTimes = nullptr;
+    mLineTimesCapacity = 0;
+    mLineTimes = static_cast<double*>(mGrid.bytes(nTimes * sizeof(double)));
+    mLineTimesCapacity = nTimes;
+  }
+  mGrid.check(kw_memcpy_h2d(context(), mLineTimes, times, nTimes * sizeof(double)));
+  makeLinePass(chunkTimes);
+
+  const kw_second_order_op op = this->op(0.0);
+  kw_ctx* pass = mLinePass->ctx();
+  const size_t F = mPar.frames;
+  for (const auto& c : chunks)
+  {
+    const size_t rows = F * c.count;
+    mGrid.check(kw_second_order_line_record(context(), mLineG, mLineQ, &op, mLineTimes + c.first, static_cast<uint32_t>(c.count)));
+    mGrid.check(kw_sync(context())); // the second context has a stream of its own
+    mLinePass->check(kw_fft_c2r_frames(pass, mLineG, mLineRows));
+    mLinePass->check(kw_plane_recon_crop(pass, mLineOut, mLineRows, static_cast<uint32_t>(mPar.ex), static_cast<uint32_t>(rows), 1,
+                                         static_cast<uint32_t>(mPar.nx), static_cast<uint32_t>(rows), 1, 0));
+    if (dst == nullptr) mLinePass->check(kw_sync(pass));
+    else if (c.count == nTimes) mLinePass->check(kw_memcpy_d2h(pass, dst, mLineOut, rows * mPar.nx * sizeof(float)));
+    else
+      for (size_t f = 0; f < F; f++) // the pass holds [F][count][Nx], the record [F][n_times][Nx]
+        mLinePass->check(kw_memcpy_d2h(pass, dst + mPar.lineOffset(f, c.first, nTimes), mLineOut + f * c.count * mPar.nx,
+                                       c.count * mPar.nx * sizeof(float)));
+  }
 }
 
 void SecondOrderFrames::get(const std::string& name, float* dst, size_t n)

@@ -11,12 +11,21 @@
 //   run(times): SecondOrder's loop: per time the passes, the sample at the sensor points of every frame into row i of the
 //         record [n_times][F][n_sensor] (kw_sample_index on the expanded batch, indices translated once) and, where asked
 //         for, the crop and kw_sample_all into the running max, min, sum of squares and the final field.
+//   lineRecord(times): the record of one row of every frame (csrc/kw_second_order_line.hip): setLineRow, then at every
+//         setP0 the natural (kx, ky) spectra (rocFFT path: the kept ones; fast path: one kw_fft_r2c_frames of the embedded
+//         batch into an array of its own, after the fused forward has read it) go through kw_second_order_line_prepare
+//         into Q; per pass of at most lineChunkTimes() output times kw_second_order_line_record into G, a batched 1-D C2R
+//         of length Ex over its F times rows on a second context (Ex, 1, F times) and the crop of Ex to Nx.  Neither the
+//         field state nor the aggregates of run are touched.
 //
 // Device memory, E = Ex Ey F points, R = (Ex/2 + 1) Ey F bins, N = Nx Ny F: the batch 4 E, the kept spectrum (8 R; a scratch
 // array on the fast path) and the pipeline's scratch arrays (fast path) or one more spectrum 8 R (rocFFT); the crop 4 N and
-// 4 N per aggregate; the record 4 n_times F n_sensor.
+// 4 N per aggregate; the record 4 n_times F n_sensor.  With a line row: Q 8 (Ex/2 + 1) (Ey/2 + 1) F, on the fast path the
+// natural spectra 8 R as well, the times 8 n_times, and per pass of T times G 8 (Ex/2 + 1) F T, its rows 4 Ex F T and their
+// crop 4 Nx F T.
 #ifndef KW_HOST_SECOND_ORDER_FRAMES_H
 #define KW_HOST_SECOND_ORDER_FRAMES_H
+#include <memory>
 #include <string>
 
 #include "DeviceGrid.h"
@@ -37,6 +46,14 @@ class SecondOrderFrames
   void run(const double* times, size_t nTimes);
   /// "p_raw" [n_times][F][n_sensor], "p_max", "p_min", "p_rms", "p_final" of the last run, "p" (the last field computed)
   void get(const std::string& name, float* dst, size_t n);
+  /// the row of every plane that lineRecord records, 0 ... Ny - 1, from the next setP0 on; -1: none, its arrays are freed
+  void setLineRow(int64_t row);
+  /// how many output times one pass of lineRecord takes; 0: the default (SecondOrderFramesParameters::lineChunkTimes)
+  void setLineChunkTimes(uint64_t times);
+  /// the row's pressure in every frame at every time, in the given order; dst: [F][nTimes][Nx] floats on the host, or NULL
+  void lineRecord(const double* times, size_t nTimes, float* dst);
+  int64_t lineRow() const { return mLineRow; }
+  size_t  lineChunkTimes() const { return mPar.lineChunkTimes(mLineChunkGiven); }
   bool    usesFusedPipeline() const { return mGrid.fused(); }
   size_t  runs() const { return mRuns; }
   kw_ctx* context() const { return mGrid.ctx(); }
@@ -45,6 +62,10 @@ class SecondOrderFrames
  private:
   void propagate(double t); // mVol <- the expanded fields at time t
   void crop();              // mP <- the domain corner of every plane of mVol
+  kw_second_order_op op(double t) const;
+  void prepareLine();                // mLineQ <- the spectra of the p0 just set
+  void makeLinePass(size_t times);   // the second context and the arrays of a pass of `times` output times
+  void freeLine();
 
   SecondOrderFramesParameters mPar;
   DeviceGrid mGrid; // the context, the pipeline and every device array below
@@ -57,5 +78,17 @@ class SecondOrderFrames
   uint64_t*  mIndex = nullptr;  // the sensor points of every frame in the expanded batch
   float*     mRaw = nullptr;    // [n_times][F][n_sensor]
   float     *mMax = nullptr, *mMin = nullptr, *mRms = nullptr, *mFinal = nullptr; // the domain each, where asked for
+  // the line-sensor record
+  int64_t    mLineRow = -1;          // the row wanted
+  uint64_t   mLineChunkGiven = 0;    // 0: the default
+  bool       mLineReady = false;     // mLineQ holds the current p0 at mLineRow
+  bool       mLinePlans = false;     // fast path: the batched 2-D rocFFT plans exist on the main context
+  float*     mLineQ = nullptr;       // Q [Ex/2 + 1][Ey/2 + 1][F]
+  float*     mLineSpec = nullptr;    // fast path: the natural spectra of p0
+  double*    mLineTimes = nullptr;   // the output times of a call
+  size_t     mLineTimesCapacity = 0;
+  std::unique_ptr<DeviceGrid> mLinePass; // constants (Ex, 1, F mLinePassTimes): the 1-D plans and the three arrays below
+  size_t     mLinePassTimes = 0;
+  float     *mLineG = nullptr, *mLineRows = nullptr, *mLineOut = nullptr;
 };
 #endif

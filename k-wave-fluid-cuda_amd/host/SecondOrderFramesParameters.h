@@ -11,6 +11,9 @@
 //   the largest |k| of the 2-D grid.
 //   frames: 1 ... 65535 (the frame is a block index of the fused pass; no chunks of frames in this version), and
 //   Ex Ey frames < 2^32.  sensor_index: flat indices into one plane [Ny][Nx], applied to every frame.
+//   The line-sensor record (SecondOrderFrames::lineRecord): line_row: -1 (off) or a row 0 ... Ny - 1 of the plane;
+//   line_chunk_times: how many output times one pass of the record takes — 0: as many as keep G [F][times][Ex/2 + 1] within
+//   kLineBudgetBytes, one at the least; given: Ex F times < 2^32 (the rows' 32-bit indices) and at most kLineTimesMost.
 // A refusal names the parameter.
 #ifndef KW_HOST_SECOND_ORDER_FRAMES_PARAMETERS_H
 #define KW_HOST_SECOND_ORDER_FRAMES_PARAMETERS_H
@@ -50,5 +53,21 @@ class SecondOrderFramesParameters
   double damping(double k) const { return GridRule::powerLawDamping(a, c0, alphaPower, k); }
   /// the sensor points of every frame as indices into the expanded batch [F][Ey][Ex], frame by frame
   std::vector<uint64_t> expandedSensorIndex() const;
+
+  // ---- the line-sensor record: its sizes and the order of its chunks, after init() ----
+  static constexpr size_t kLineBudgetBytes = size_t(256) << 20;     ///< of G in the default chunk
+  static constexpr size_t kLineTimesMost   = size_t(65535) * 256;  ///< the record kernel's time tiles are a block index
+  struct LineChunk { size_t first, count; };                        ///< output times first ... first + count - 1
+  /// -1 or 0 ... Ny - 1; refuses "line_row"
+  void   checkLineRow(int64_t row) const;
+  /// the times of one pass: the default for 0, the given number otherwise; refuses "line_chunk_times"
+  size_t lineChunkTimes(uint64_t given) const;
+  /// n_times in passes of at most chunkTimes, in order; refuses "n_times" for 0
+  static std::vector<LineChunk> lineChunks(size_t nTimes, size_t chunkTimes);
+  /// complex values of Q [Ex/2 + 1][Ey/2 + 1][F] and of G [F][times][Ex/2 + 1]
+  size_t lineElems() const { return (ex / 2 + 1) * (ey / 2 + 1) * frames; }
+  size_t lineSpectrumElems(size_t times) const { return (ex / 2 + 1) * frames * times; }
+  /// where time t of frame f stands in the record [F][n_times][Nx], in floats
+  size_t lineOffset(size_t f, size_t t, size_t nTimes) const { return (f * nTimes + t) * nx; }
 };
 #endif

@@ -1165,9 +1165,48 @@ int kwh_second_order_frames_get_scalar(kwh_second_order_frames* s, const char* n
   else if (n == "frames") *out = static_cast<double>(p.frames);
   else if (n == "t_free") *out = p.tFree;
   else if (n == "runs") *out = static_cast<double>(s->propagator->runs());
+  else if (n == "line_row") *out = static_cast<double>(s->propagator->lineRow());
+  else if (n == "line_chunk_times") *out = static_cast<double>(s->propagator->lineChunkTimes());
   else throw std::invalid_argument(std::string("unknown scalar ") + name);
   KWH_CATCH
 }
 
 void* kwh_second_order_frames_context(kwh_second_order_frames* s) { return s ? s->propagator->context() : nullptr; }
+
+int kwh_second_order_frames_line_plan(const kwh_second_order_frames_config* config, const kwh_options* o, int64_t row,
+                                      uint64_t chunk_times, uint64_t n_times, uint64_t out[3])
+{
+  KWH_TRY
+  if (!config || !o) throw std::invalid_argument("kwh_second_order_frames_line_plan: NULL argument");
+  const SecondOrderFramesParameters p = kwh_second_order_frames_parameters(config, o);
+  p.checkLineRow(row);
+  const size_t chunk = p.lineChunkTimes(chunk_times);
+  const size_t passes = SecondOrderFramesParameters::lineChunks(n_times, chunk).size();
+  if (out) { out[0] = chunk; out[1] = passes; out[2] = p.lineElems(); }
+  KWH_CATCH
+}
+
+int kwh_second_order_frames_set_line_row(kwh_second_order_frames* s, int64_t row)
+{
+  KWH_TRY
+  if (!s) throw std::invalid_argument("kwh_second_order_frames_set_line_row: NULL propagator");
+  s->propagator->setLineRow(row);
+  KWH_CATCH
+}
+
+int kwh_second_order_frames_set_line_chunk_times(kwh_second_order_frames* s, uint64_t times)
+{
+  KWH_TRY
+  if (!s) throw std::invalid_argument("kwh_second_order_frames_set_line_chunk_times: NULL propagator");
+  s->propagator->setLineChunkTimes(times);
+  KWH_CATCH
+}
+
+int kwh_second_order_frames_line_record(kwh_second_order_frames* s, const double* times, uint64_t n_times, float* dst)
+{
+  KWH_TRY
+  if (!s || (!times && n_times != 0)) throw std::invalid_argument("kwh_second_order_frames_line_record: NULL argument");
+  s->propagator->lineRecord(times, n_times, dst);
+  KWH_CATCH
+}
 }

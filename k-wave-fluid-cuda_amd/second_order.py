@@ -9,11 +9,14 @@ library or device raises.
 
 `SecondOrderFrames` is its batched 2-D form (kwave_host.h "Exact k-space propagator on frames"): F independent images
 p0(x, y) that share the medium, the expanded plane, the output times and the sensor points, each carried to any time by one
-2-D round trip — what a linear array records for many phantoms, the forward side of `recon.LineRecon`.
+2-D round trip — what a linear array records for many phantoms, the forward side of `recon.LineRecon`.  With `line_row`
+set, `line_record(times)` gives that record for one row of the plane, (F, n_times, Nx), in one call: per time and kx one sum
+over the ky bins and one 1-D inverse over the record itself, no 2-D round trip per time.
 
 Not built: dp0/dt as a second initial condition and time-varying sources, heterogeneous media, Z-slabs, chunks of frames and
-frames over several GPUs, HDF5 files and the command line, graphs, several output times per pass, inverse passes restricted
-to the crop, to the sensor points or to the rows that hold sensors, particle velocity outputs.
+frames over several GPUs, HDF5 files and the command line, graphs, several output times per pass and inverse passes
+restricted to the crop, to the sensor points or to the rows that hold sensors (but for the one row of `line_record`),
+several rows, columns or arbitrary points in `line_record`, particle velocity outputs.
 """
 from __future__ import annotations
 
@@ -61,6 +64,11 @@ def _lib() -> C.CDLL:
             fn("get_scalar").argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_double)]
             fn("context").restype = C.c_void_p
             fn("context").argtypes = [C.c_void_p]
+        L.kwh_second_order_frames_line_plan.argtypes = [C.POINTER(FramesConfig), C.POINTER(Options), C.c_int64, C.c_uint64,
+                                                        C.c_uint64, C.POINTER(C.c_uint64)]
+        L.kwh_second_order_frames_set_line_row.argtypes = [C.c_void_p, C.c_int64]
+        L.kwh_second_order_frames_set_line_chunk_times.argtypes = [C.c_void_p, C.c_uint64]
+        L.kwh_second_order_frames_line_record.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_uint64, C.c_void_p]
         _bound = True
     return L
 
@@ -256,15 +264,28 @@ class SecondOrderFrames(SecondOrder):
     sampled in every frame by run() — a row of the plane is a linear array.
 
     set_p0(p0) takes (F, Ny, Nx), or (Ny, Nx) when frames == 1; field(t) -> (F, Ny, Nx); run(times) -> the record
-    (n_times, F, n_sensor), times in any order; p_max() / p_min() / p_rms() / p_final() -> (F, Ny, Nx)."""
+    (n_times, F, n_sensor), times in any order; p_max() / p_min() / p_rms() / p_final() -> (F, Ny, Nx).
+
+    line_row: a row 0 ... Ny - 1 of the plane (None: none) whose record line_record(times) -> (F, n_times, Nx) gives without
+    a 2-D round trip per time — `recon.LineRecon`'s order "ty" with x as the array axis.  It is prepared by set_p0;
+    line_chunk_times bounds the output times of one pass (None: by a byte budget).  field, run and line_record may be
+    interleaved."""
 
     _ENTRY = "kwh_second_order_frames"
 
     def __init__(self, n, d, c0, frames, alpha_coeff=0.0, alpha_power=1.5, t_max=None, expanded=None, sensor_index=None,
-                 record=("p_raw",), fused_kernels=True, device_idx=-1):
+                 record=("p_raw",), fused_kernels=True, device_idx=-1, line_row=None, line_chunk_times=None):
         c, idx = _config(n, d, c0, alpha_coeff, alpha_power, t_max, expanded, sensor_index, record, frames=frames)
         self._create(c, idx, fused_kernels, device_idx)
         self.nx, self.ny, self.frames = int(c.nx), int(c.ny), int(c.frames)
+        try:
+            if line_row is not None:
+                self.line_row = line_row
+            if line_chunk_times is not None:
+                self.line_chunk_times = line_chunk_times
+        except Exception:
+            self.close()
+            raise
 
     @staticmethod
     def plan(n, d, c0, frames, alpha_coeff=0.0, alpha_power=1.5, t_max=None, expanded=None, sensor_index=None,
@@ -297,3 +318,48 @@ class SecondOrderFrames(SecondOrder):
 
     def _record_shape(self):
         return (self.n_times, self.frames, self.n_sensor)
+
+    @staticmethod
+    def line_plan(n, d, c0, frames, line_row, n_times, line_chunk_times=None, **kw) -> Tuple[int, int, int]:
+        """(output times of one pass, passes for n_times, complex values of Q), checked as set_line_row, the chunk setter and
+        line_record would, without a device; kw: the constructor's other arguments"""
+        o = Options()
+        o.fused_kernels = int(bool(kw.pop("fused_kernels", True)))
+        c, _idx = _config(n, d, c0, kw.pop("alpha_coeff", 0.0), kw.pop("alpha_power", 1.5), kw.pop("t_max", None),
+                          kw.pop("expanded", None), kw.pop("sensor_index", None), kw.pop("record", ("p_raw",)), frames=frames)
+        if kw:
+            raise TypeError(f"unknown arguments {sorted(kw)}")
+        out = (C.c_uint64 * 3)()
+        _check(_lib().kwh_second_order_frames_line_plan(C.byref(c), C.byref(o), -1 if line_row is None else int(line_row),
+                                                        int(line_chunk_times or 0), int(n_times), out))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    @property
+    def line_row(self):
+        """the row that line_record records (None: none); setting it takes effect at the next set_p0"""
+        r = int(self._scalar("line_row"))
+        return None if r < 0 else r
+
+    @line_row.setter
+    def line_row(self, row):
+        _check(_lib().kwh_second_order_frames_set_line_row(self._h, -1 if row is None else int(row)))
+
+    @property
+    def line_chunk_times(self) -> int:
+        """output times per pass of line_record; set None or 0 for the default"""
+        return int(self._scalar("line_chunk_times"))
+
+    @line_chunk_times.setter
+    def line_chunk_times(self, times):
+        if times is not None and int(times) < 0:
+            raise ValueError(f"line_chunk_times must not be negative, got {times}")
+        _check(_lib().kwh_second_order_frames_set_line_chunk_times(self._h, int(times or 0)))
+
+    def line_record(self, times) -> np.ndarray:
+        """the pressure on row line_row of every frame at every time of `times` [s], in the given order: float32
+        (F, n_times, Nx)"""
+        ta = np.ascontiguousarray(np.asarray(times, dtype=np.float64).reshape(-1))
+        out = np.empty((self.frames, int(ta.size), self.nx), dtype=np.float32)
+        _check(_lib().kwh_second_order_frames_line_record(self._h, ta.ctypes.data_as(C.POINTER(C.c_double)), ta.size,
+                                                          out.ctypes.data))
+        return out

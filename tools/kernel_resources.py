@@ -34,6 +34,9 @@ def main():
                                                                           os.path.join(CSRC, "kw_angular.hip"),
                                                                           os.path.join(CSRC, "kw_angular_time.hip"),
                                                                           os.path.join(CSRC, "kw_second_order.hip"),
+                                                                          # (no kernel of the pipeline: k_line_record<FT>
+                                                                          # and k_line_prepare, the same at every length)
+                                                                          os.path.join(CSRC, "kw_second_order_line.hip"),
                                                                           os.path.join(CSRC, "kw_plane_recon.hip"),
                                                                           os.path.join(CSRC, "kw_line_recon.hip")]
         texts = list(pool.map(compile_one, [(length, src, tmp, extra) for src in srcs]))
