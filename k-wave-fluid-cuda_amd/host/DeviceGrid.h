@@ -1,6 +1,7 @@
 // DeviceGrid.h — the one owner of a kw_ctx for the operators that bring their own context (ThermalSolver, CwPropagator,
-// AngularSpectrum, AngularSpectrumTime, PlaneRecon, LineRecon, SecondOrder, SecondOrderFrames): the context, its FFT pipeline and every device allocation, released
-// by the destructor.  Held as a member: when the enclosing constructor throws, what was built so far goes the same way.
+// AngularSpectrum, AngularSpectrumTime, PlaneRecon, LineRecon, and SecondOrderCore for SecondOrder and SecondOrderFrames):
+// the context, its FFT pipeline and every device allocation, released by the destructor.  Held as a member: when the
+// enclosing constructor throws, what was built so far goes the same way.
 #ifndef KW_HOST_DEVICE_GRID_H
 #define KW_HOST_DEVICE_GRID_H
 #include <cstddef>

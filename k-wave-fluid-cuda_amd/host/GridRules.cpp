@@ -89,3 +89,49 @@ double powerLawDamping(double a, double c0, double y, double k)
   return 1.0 - 2.0 * g * T - g * g;
 }
 } // namespace GridRule
+
+using namespace GridRule;
+
+void SecondOrderRules::checkTime(double t)
+{
+  if (!(t >= 0.0) || !std::isfinite(t)) refuse("t", std::to_string(t) + " is not a time >= 0");
+}
+
+void SecondOrderRules::checkMedium() const
+{
+  checkPositive(c0, "c0", "sound speed");
+  if (!(alphaCoeff >= 0.0) || !std::isfinite(alphaCoeff))
+    refuse("alpha_coeff", std::to_string(alphaCoeff) + " is not an absorption >= 0 in dB/(MHz^y cm)");
+  if (!(alphaPower >= 0.0) || !(alphaPower < 3.0) || alphaPower == 1.0)
+    refuse("alpha_power", std::to_string(alphaPower) + " is outside the power law's range 0 <= y < 3, y != 1");
+}
+
+void SecondOrderRules::checkSensors(size_t points, const char* where) const
+{
+  for (size_t i = 0; i < sensorIndex.size(); i++)
+    if (sensorIndex[i] >= points)
+      refuse("sensor_index", "sensor_index[" + std::to_string(i) + "] = " + std::to_string(sensorIndex[i]) + " is outside the " +
+                               where + " of " + std::to_string(points) + " points");
+}
+
+void SecondOrderRules::completeAbsorption(const size_t* e, const double* d, int axes)
+{
+  a = powerLawNepers(alphaCoeff, alphaPower);
+  bSmallest = bLargest = 1.0;
+  if (!(a > 0.0)) return;
+  double kSmallest = 0.0, k2Largest = 0.0;
+  for (int i = 0; i < axes; i++)
+  {
+    const double dk = 2.0 * kPi / (static_cast<double>(e[i]) * d[i]);
+    if (e[i] > 1 && (kSmallest == 0.0 || dk < kSmallest)) kSmallest = dk;
+    const double kn = dk * static_cast<double>(e[i] / 2);
+    k2Largest += kn * kn;
+  }
+  bSmallest = damping(kSmallest);
+  bLargest  = damping(std::sqrt(k2Largest));
+  const bool low = !(bSmallest >= 0.25);
+  if (low || !(bLargest >= 0.25))
+    refuse("alpha_coeff", std::to_string(alphaCoeff) + ": a mode of this grid is damped beyond B = 1/4 (B = " +
+                            std::to_string(low ? bSmallest : bLargest) + " at the " + (low ? "smallest non-zero" : "largest") +
+                            " |k|)");
+}

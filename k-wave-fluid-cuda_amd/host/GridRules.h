@@ -1,10 +1,13 @@
 // GridRules.h — the parameter rules that the operators with their own context share (CwParameters, AngularParameters,
-// AngularTimeParameters, PlaneReconParameters, LineReconParameters, SecondOrderParameters, SecondOrderFramesParameters): the refusal that names the parameter, the size and sign checks, the fused
-// pipeline's line lengths and the checks of an expanded grid.  No device call.
+// AngularTimeParameters, PlaneReconParameters, LineReconParameters, SecondOrderParameters, SecondOrderFramesParameters):
+// the refusal that names the parameter, the size and sign checks, the fused pipeline's line lengths and the checks of an
+// expanded grid; and SecondOrderRules, the base of the last two.  No device call.
 #ifndef KW_HOST_GRID_RULES_H
 #define KW_HOST_GRID_RULES_H
 #include <cstddef>
+#include <cstdint>
 #include <string>
+#include <vector>
 
 /// what every such operator takes besides its own parameters
 struct DeviceOptions
@@ -44,4 +47,36 @@ size_t reachSide(size_t n, double d, double reach, bool fusedKernels);
 double powerLawNepers(double alphaCoeff, double y);
 double powerLawDamping(double a, double c0, double y, double k);
 } // namespace GridRule
+
+/// what the exact propagators' parameters have in common (the base of SecondOrderParameters and
+/// SecondOrderFramesParameters): the medium, the sensor points, the aggregates wanted and what init() completes.  The
+/// checks are protected: each init() calls them at its own place among the checks of its sizes.
+struct SecondOrderRules
+{
+  /// throws unless t is finite and >= 0
+  static void checkTime(double t);
+
+  DeviceOptions options;
+  double c0 = 0;                  ///< [m/s]
+  double alphaCoeff = 0;          ///< [dB / (MHz^y cm)]; 0: lossless
+  double alphaPower = 1.5;        ///< y
+  double tMax = 0;                ///< [s]; read for the default sides only
+  std::vector<uint64_t> sensorIndex; ///< 0-based flat indices into the domain (3-D) or into one plane (frames)
+  bool   pMax = false, pMin = false, pRms = false, pFinal = false; ///< aggregates over the output times of a run
+
+  bool   fastPath = false;        ///< every side is a fast-path length (and fusedKernels is on)
+  double a = 0;                   ///< [Np (rad/s)^-y m^-1]
+  double tFree = 0;               ///< [s]
+  double bSmallest = 1, bLargest = 1; ///< B at the smallest non-zero and at the largest |k| of the grid
+  /// B(|k|) of the completed parameters
+  double damping(double k) const { return GridRule::powerLawDamping(a, c0, alphaPower, k); }
+
+ protected:
+  /// refuses "c0", "alpha_coeff", "alpha_power", in this order
+  void checkMedium() const;
+  /// refuses "sensor_index" at the first index not below `points`; `where`: "domain" or "plane"
+  void checkSensors(size_t points, const char* where) const;
+  /// a, bSmallest and bLargest over the `axes` sides e of spacings d; refuses "alpha_coeff" when B is below 1/4 at either
+  void completeAbsorption(const size_t* e, const double* d, int axes);
+};
 #endif

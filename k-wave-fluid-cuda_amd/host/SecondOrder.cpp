@@ -1,132 +1,29 @@
-// SecondOrder.cpp — the host side of the exact k-space propagator around the device library's kw_second_order_mix and
-// kw_fused_second_order_* entry points.
+// SecondOrder.cpp — the 3-D form of the exact k-space propagator: the device library's kw_second_order_mix and
+// kw_fused_second_order_* entry points under SecondOrderCore.
 #include "SecondOrder.h"
 
-#include <vector>
-
-SecondOrder::SecondOrder(const SecondOrderParameters& parameters) : mPar(parameters), mGrid(mPar.options.deviceIdx)
+namespace
 {
-  const size_t ne = mPar.nExpanded(), nr = mPar.nReduced(), nd = mPar.nDomain();
-  mGrid.setConstants(gridConstants(mPar.ex, mPar.ey, mPar.ez));
-  const bool fused = mGrid.choosePipeline(mPar.fastPath);
+const SecondOrderEntries kEntries = { false,
+                                      kw_fused_second_order_elems,
+                                      kw_fused_second_order_forward,
+                                      kw_fused_second_order_time,
+                                      kw_second_order_mix,
+                                      kw_fft_r2c_3d,
+                                      kw_fft_c2r_3d };
 
-  mVol = mGrid.array(ne);
-  size_t kept = nr;
-  if (fused) mGrid.check(kw_fused_second_order_elems(context(), &kept));
-  else mSpec = mGrid.array(2 * nr);
-  mKept = mGrid.array(2 * kept);
-  mP    = mGrid.array(nd);
-  if (mPar.pMax) mMax = mGrid.array(nd);
-  if (mPar.pMin) mMin = mGrid.array(nd);
-  if (mPar.pRms) mRms = mGrid.array(nd);
-  if (mPar.pFinal) mFinal = mGrid.array(nd);
-  if (!mPar.sensorIndex.empty())
-  {
-    const std::vector<uint64_t> index = mPar.expandedSensorIndex();
-    mIndex = static_cast<uint64_t*>(mGrid.bytes(index.size() * sizeof(uint64_t)));
-    mGrid.check(kw_memcpy_h2d(context(), mIndex, index.data(), index.size() * sizeof(uint64_t)));
-  }
-  mGrid.check(kw_sync(context()));
-}
-
-void SecondOrder::setP0(const float* p0)
-{
-  const uint32_t ex = static_cast<uint32_t>(mPar.ex), ey = static_cast<uint32_t>(mPar.ey), ez = static_cast<uint32_t>(mPar.ez);
-  mGrid.check(kw_memcpy_h2d(context(), mP, p0, mPar.nDomain() * sizeof(float)));
-  mGrid.check(kw_angular_time_embed(context(), mVol, mP, ex, ey, ez, static_cast<uint32_t>(mPar.nx), static_cast<uint32_t>(mPar.ny),
-                                    static_cast<uint32_t>(mPar.nz)));
-  if (mGrid.fused()) mGrid.check(kw_fused_second_order_forward(context(), mVol, mKept));
-  else mGrid.check(kw_fft_r2c_3d(context(), mVol, mKept));
-  mHaveInput = true;
-  mHaveField = false;
-}
-
-void SecondOrder::propagate(double t)
+SecondOrderForm form(const SecondOrderParameters& p)
 {
   kw_second_order_op op{};
-  op.dx = mPar.dx; op.dy = mPar.dy; op.dz = mPar.dz; op.c0 = mPar.c0;
-  op.t  = t;
-  op.a  = mPar.a;
-  op.alpha_power = mPar.alphaPower;
-  op.absorbing   = mPar.a > 0.0 ? 1 : 0;
-  if (mGrid.fused()) mGrid.check(kw_fused_second_order_time(context(), mKept, &op, mVol));
-  else
-  {
-    mGrid.check(kw_second_order_mix(context(), mSpec, mKept, &op, 1.0f / static_cast<float>(mPar.nExpanded())));
-    mGrid.check(kw_fft_c2r_3d(context(), mSpec, mVol));
-  }
+  op.dx = p.dx; op.dy = p.dy; op.dz = p.dz; op.c0 = p.c0;
+  op.a  = p.a;
+  op.alpha_power = p.alphaPower;
+  op.absorbing   = p.a > 0.0 ? 1 : 0;
+  return { p.ex, p.ey, p.ez, p.nx, p.ny, p.nz, 1.0f / static_cast<float>(p.nExpanded()), op, &kEntries };
 }
+} // namespace
 
-void SecondOrder::crop()
+SecondOrder::SecondOrder(const SecondOrderParameters& parameters)
+  : mPar(parameters), mCore(mPar, form(mPar), mPar.expandedSensorIndex())
 {
-  mGrid.check(kw_plane_recon_crop(context(), mP, mVol, static_cast<uint32_t>(mPar.ex), static_cast<uint32_t>(mPar.ey),
-                                  static_cast<uint32_t>(mPar.ez), static_cast<uint32_t>(mPar.nx), static_cast<uint32_t>(mPar.ny),
-                                  static_cast<uint32_t>(mPar.nz), 0));
-  mHaveField = true;
-}
-
-void SecondOrder::field(double t, float* dst)
-{
-  SecondOrderParameters::checkTime(t);
-  if (!mHaveInput) throw std::invalid_argument("field: no p0 yet");
-  propagate(t);
-  crop();
-  if (dst != nullptr) mGrid.check(kw_memcpy_d2h(context(), dst, mP, mPar.nDomain() * sizeof(float)));
-}
-
-void SecondOrder::run(const double* times, size_t nTimes)
-{
-  if (nTimes == 0) GridRule::refuse("n_times", "0 is not a number of output times");
-  for (size_t i = 0; i < nTimes; i++) SecondOrderParameters::checkTime(times[i]);
-  if (!mHaveInput) throw std::invalid_argument("run: no p0 yet");
-  const size_t ns = mPar.sensorIndex.size(), nd = mPar.nDomain();
-  if (ns * nTimes > mRawCapacity)
-  {
-    if (mRaw != nullptr) mGrid.release(mRaw);
-    mRaw = nullptr;
-    mRawCapacity = 0;
-    mRaw = mGrid.array(ns * nTimes);
-    mRawCapacity = ns * nTimes;
-  }
-  const bool aggregates = mMax || mMin || mRms || mFinal;
-  if (mRms != nullptr) mGrid.check(kw_memset(context(), mRms, 0, nd * sizeof(float)));
-  for (size_t i = 0; i < nTimes; i++)
-  {
-    propagate(times[i]);
-    if (ns != 0) mGrid.check(kw_sample_index(context(), KW_OP_NONE, mRaw + i * ns, mVol, mIndex, ns));
-    if (!aggregates) continue;
-    crop();
-    // the first time initialises max and min by a copy: no fill with infinities is needed
-    if (mMax != nullptr) mGrid.check(kw_sample_all(context(), i == 0 ? KW_OP_NONE : KW_OP_MAX, mMax, mP, nd));
-    if (mMin != nullptr) mGrid.check(kw_sample_all(context(), i == 0 ? KW_OP_NONE : KW_OP_MIN, mMin, mP, nd));
-    if (mRms != nullptr) mGrid.check(kw_sample_all(context(), KW_OP_RMS, mRms, mP, nd));
-    if (mFinal != nullptr && i + 1 == nTimes) mGrid.check(kw_sample_all(context(), KW_OP_NONE, mFinal, mP, nd));
-  }
-  if (mRms != nullptr) mGrid.check(kw_post_processing_rms(context(), mRms, 1.0f / static_cast<float>(nTimes), nd));
-  mTimes = nTimes;
-  mRuns++;
-}
-
-void SecondOrder::get(const std::string& name, float* dst, size_t n)
-{
-  const float* src = nullptr;
-  size_t want = mPar.nDomain();
-  if (name == "p")
-  {
-    if (!mHaveField) throw std::invalid_argument("p: no field yet");
-    src = mP;
-  }
-  else
-  {
-    if (name == "p_raw") { src = mRaw; want = mTimes * mPar.sensorIndex.size(); }
-    else if (name == "p_max") src = mMax;
-    else if (name == "p_min") src = mMin;
-    else if (name == "p_rms") src = mRms;
-    else if (name == "p_final") src = mFinal;
-    else throw std::invalid_argument("no propagator output named " + name + " (p_raw, p_max, p_min, p_rms, p_final, p)");
-    if (mRuns == 0) throw std::invalid_argument(name + ": no run yet");
-    if (name == "p_raw" ? mPar.sensorIndex.empty() : src == nullptr) throw std::invalid_argument(name + ": not recorded");
-  }
-  if (n != want) throw std::invalid_argument("size mismatch for " + name);
-  if (n != 0) mGrid.check(kw_memcpy_d2h(context(), dst, src, n * sizeof(float)));
 }

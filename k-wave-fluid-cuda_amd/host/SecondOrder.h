@@ -1,6 +1,7 @@
 // SecondOrder.h — exact k-space propagator: an initial pressure p0[z][y][x] in a homogeneous medium, lossless or power-law
 // absorbing, to the pressure at any time with no time loop (DESIGN.md "Exact k-space propagator"; what k-Wave's
-// kspaceSecondOrder computes).  Owns its context through a DeviceGrid.
+// kspaceSecondOrder computes).  Its parameters and a SecondOrderCore in the 3-D form: the core owns the context through a
+// DeviceGrid and holds the bodies of everything below, which SecondOrderFrames runs in its own form.
 //
 //   setP0: embed p0 into the zero-filled volume Ez x Ey x Ex (kw_angular_time_embed), transform it once and keep the
 //         result — fast path: kw_fused_second_order_forward (the (kx, ky, z) half-spectrum); others: kw_fft_r2c_3d
@@ -17,7 +18,7 @@
 #define KW_HOST_SECOND_ORDER_H
 #include <string>
 
-#include "DeviceGrid.h"
+#include "SecondOrderCore.h"
 #include "SecondOrderParameters.h"
 
 class SecondOrder
@@ -28,32 +29,20 @@ class SecondOrder
   SecondOrder& operator=(const SecondOrder&) = delete;
 
   /// p0: Nx Ny Nz floats on the host, [Nz][Ny][Nx]; may be called again
-  void setP0(const float* p0);
+  void setP0(const float* p0) { mCore.setP0(p0); }
   /// the pressure at time t on the domain; dst: Nx Ny Nz floats on the host or NULL (the crop stays on the device)
-  void field(double t, float* dst);
+  void field(double t, float* dst) { mCore.field(t, dst); }
   /// every time in the given order: the record's row, the aggregates
-  void run(const double* times, size_t nTimes);
+  void run(const double* times, size_t nTimes) { mCore.run(times, nTimes); }
   /// "p_raw" [n_times][n_sensor], "p_max", "p_min", "p_rms", "p_final" of the last run, "p" (the last field computed)
-  void get(const std::string& name, float* dst, size_t n);
-  bool    usesFusedPipeline() const { return mGrid.fused(); }
-  size_t  runs() const { return mRuns; }
-  kw_ctx* context() const { return mGrid.ctx(); }
+  void get(const std::string& name, float* dst, size_t n) { mCore.get(name, dst, n); }
+  bool    usesFusedPipeline() const { return mCore.grid().fused(); }
+  size_t  runs() const { return mCore.runs(); }
+  kw_ctx* context() const { return mCore.ctx(); }
   const SecondOrderParameters& parameters() const { return mPar; }
 
  private:
-  void propagate(double t); // mVol <- the expanded field at time t
-  void crop();              // mP <- the domain corner of mVol
-
   SecondOrderParameters mPar;
-  DeviceGrid mGrid; // the context, the pipeline and every device array below
-  bool       mHaveInput = false, mHaveField = false;
-  size_t     mRuns = 0, mTimes = 0, mRawCapacity = 0;
-  float*     mVol = nullptr;    // Ez Ey Ex: the embedded p0, then each time's field
-  float*     mKept = nullptr;   // the kept spectrum
-  float*     mSpec = nullptr;   // rocFFT path: the spectrum of one time
-  float*     mP = nullptr;      // the domain: p0 as handed in, then the crop
-  uint64_t*  mIndex = nullptr;  // the sensor points in the expanded volume
-  float*     mRaw = nullptr;    // [n_times][n_sensor]
-  float     *mMax = nullptr, *mMin = nullptr, *mRms = nullptr, *mFinal = nullptr; // the domain each, where asked for
+  SecondOrderCore mCore;
 };
 #endif

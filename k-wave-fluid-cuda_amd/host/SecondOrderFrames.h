@@ -1,15 +1,16 @@
 // SecondOrderFrames.h — batched 2-D exact k-space propagator: F independent initial pressures p0[f][y][x] in a homogeneous
 // medium, lossless or power-law absorbing, to the pressure of each at any time with no time loop (DESIGN.md "Exact k-space
-// propagator on frames") — SecondOrder with the z axis removed and the frame count in its place.  Owns its context through
-// a DeviceGrid: the fused pipeline in frames mode (the z axis of the constants is the batch) where wanted and supported,
-// the batched 2-D rocFFT plans otherwise.
+// propagator on frames") — SecondOrder with the z axis removed and the frame count in its place.  Its parameters, a
+// SecondOrderCore in the frames form and the line-sensor record.  The core owns the context through a DeviceGrid: the
+// fused pipeline in frames mode (the z axis of the constants is the batch) where wanted and supported, the batched 2-D
+// rocFFT plans otherwise.
 //
 //   setP0: embed every p0 into its zero-filled plane Ey x Ex (kw_angular_time_embed, the frame in the slowest position),
 //         transform once and keep — fast path: kw_fused_second_order_frames_forward; others: kw_fft_r2c_frames
 //   field(t): fast path: kw_fused_second_order_frames_time; others: kw_second_order_frames_mix and kw_fft_c2r_frames — then
 //         the crop to the domain (kw_plane_recon_crop), which stays on the device
-//   run(times): SecondOrder's loop: per time the passes, the sample at the sensor points of every frame into row i of the
-//         record [n_times][F][n_sensor] (kw_sample_index on the expanded batch, indices translated once) and, where asked
+//   run(times): the core's loop, SecondOrder's too: per time the passes, the sample at the sensor points of every frame
+//         into row i of the record [n_times][F][n_sensor] (kw_sample_index on the expanded batch, indices translated once) and, where asked
 //         for, the crop and kw_sample_all into the running max, min, sum of squares and the final field.
 //   lineRecord(times): the record of one row of every frame (csrc/kw_second_order_line.hip): setLineRow, then at every
 //         setP0 the natural (kx, ky) spectra (rocFFT path: the kept ones; fast path: one kw_fft_r2c_frames of the embedded
@@ -28,7 +29,7 @@
 #include <memory>
 #include <string>
 
-#include "DeviceGrid.h"
+#include "SecondOrderCore.h"
 #include "SecondOrderFramesParameters.h"
 
 class SecondOrderFrames
@@ -41,11 +42,11 @@ class SecondOrderFrames
   /// p0: Nx Ny F floats on the host, [F][Ny][Nx]; may be called again
   void setP0(const float* p0);
   /// every frame's pressure at time t on the domain; dst: Nx Ny F floats on the host or NULL (the crop stays on the device)
-  void field(double t, float* dst);
+  void field(double t, float* dst) { mCore.field(t, dst); }
   /// every time in the given order: the record's row, the aggregates
-  void run(const double* times, size_t nTimes);
+  void run(const double* times, size_t nTimes) { mCore.run(times, nTimes); }
   /// "p_raw" [n_times][F][n_sensor], "p_max", "p_min", "p_rms", "p_final" of the last run, "p" (the last field computed)
-  void get(const std::string& name, float* dst, size_t n);
+  void get(const std::string& name, float* dst, size_t n) { mCore.get(name, dst, n); }
   /// the row of every plane that lineRecord records, 0 ... Ny - 1, from the next setP0 on; -1: none, its arrays are freed
   void setLineRow(int64_t row);
   /// how many output times one pass of lineRecord takes; 0: the default (SecondOrderFramesParameters::lineChunkTimes)
@@ -54,41 +55,39 @@ class SecondOrderFrames
   void lineRecord(const double* times, size_t nTimes, float* dst);
   int64_t lineRow() const { return mLineRow; }
   size_t  lineChunkTimes() const { return mPar.lineChunkTimes(mLineChunkGiven); }
-  bool    usesFusedPipeline() const { return mGrid.fused(); }
-  size_t  runs() const { return mRuns; }
-  kw_ctx* context() const { return mGrid.ctx(); }
+  bool    usesFusedPipeline() const { return mCore.grid().fused(); }
+  size_t  runs() const { return mCore.runs(); }
+  kw_ctx* context() const { return mCore.ctx(); }
   const SecondOrderFramesParameters& parameters() const { return mPar; }
 
  private:
-  void propagate(double t); // mVol <- the expanded fields at time t
-  void crop();              // mP <- the domain corner of every plane of mVol
-  kw_second_order_op op(double t) const;
-  void prepareLine();                // mLineQ <- the spectra of the p0 just set
-  void makeLinePass(size_t times);   // the second context and the arrays of a pass of `times` output times
+  /// what the main context holds of the line record
+  struct Line
+  {
+    bool    ready = false;     // q holds the current p0 at mLineRow
+    float*  q = nullptr;       // Q [Ex/2 + 1][Ey/2 + 1][F]
+    float*  spec = nullptr;    // fast path: the natural spectra of p0
+    double* times = nullptr;   // the output times of a call
+    size_t  timesCapacity = 0;
+  };
+  /// a second context with constants (Ex, 1, F times): the batched 1-D plans and the arrays of a pass of `times` output times
+  struct LinePass
+  {
+    LinePass(const SecondOrderFramesParameters& par, size_t times);
+    DeviceGrid grid;
+    size_t     times;
+    float     *g = nullptr, *rows = nullptr, *out = nullptr; // G, its F times rows of Ex, their crop to Nx
+  };
+  void prepareLine();              // mLine.q <- the spectra of the p0 just set
+  void makeLinePass(size_t times); // mLinePass <- a pass of `times` output times, unless it is one already
   void freeLine();
 
   SecondOrderFramesParameters mPar;
-  DeviceGrid mGrid; // the context, the pipeline and every device array below
-  bool       mHaveInput = false, mHaveField = false;
-  size_t     mRuns = 0, mTimes = 0, mRawCapacity = 0;
-  float*     mVol = nullptr;    // F Ey Ex: the embedded p0, then each time's fields
-  float*     mKept = nullptr;   // the kept spectra
-  float*     mSpec = nullptr;   // rocFFT path: the spectra of one time
-  float*     mP = nullptr;      // the domain: p0 as handed in, then the crop
-  uint64_t*  mIndex = nullptr;  // the sensor points of every frame in the expanded batch
-  float*     mRaw = nullptr;    // [n_times][F][n_sensor]
-  float     *mMax = nullptr, *mMin = nullptr, *mRms = nullptr, *mFinal = nullptr; // the domain each, where asked for
-  // the line-sensor record
+  SecondOrderCore mCore;
   int64_t    mLineRow = -1;          // the row wanted
   uint64_t   mLineChunkGiven = 0;    // 0: the default
-  bool       mLineReady = false;     // mLineQ holds the current p0 at mLineRow
   bool       mLinePlans = false;     // fast path: the batched 2-D rocFFT plans exist on the main context
-  float*     mLineQ = nullptr;       // Q [Ex/2 + 1][Ey/2 + 1][F]
-  float*     mLineSpec = nullptr;    // fast path: the natural spectra of p0
-  double*    mLineTimes = nullptr;   // the output times of a call
-  size_t     mLineTimesCapacity = 0;
-  std::unique_ptr<DeviceGrid> mLinePass; // constants (Ex, 1, F mLinePassTimes): the 1-D plans and the three arrays below
-  size_t     mLinePassTimes = 0;
-  float     *mLineG = nullptr, *mLineRows = nullptr, *mLineOut = nullptr;
+  Line       mLine;
+  std::unique_ptr<LinePass> mLinePass;
 };
 #endif

@@ -10,7 +10,6 @@ using namespace GridRule;
 
 namespace
 {
-const double kPi = 3.14159265358979323846;
 const size_t kFramesMax = 65535; // the frame is a block index of the fused pass (csrc/kw_fused_main.hip kw_fused_supported)
 } // namespace
 
@@ -24,11 +23,7 @@ void SecondOrderFramesParameters::init(const DeviceOptions& opt)
     refuse("frames", std::to_string(frames) + " is above " + std::to_string(kFramesMax) + ", the most one batch takes");
   checkPositive(dx, "dx", "spacing");
   checkPositive(dy, "dy", "spacing");
-  checkPositive(c0, "c0", "sound speed");
-  if (!(alphaCoeff >= 0.0) || !std::isfinite(alphaCoeff))
-    refuse("alpha_coeff", std::to_string(alphaCoeff) + " is not an absorption >= 0 in dB/(MHz^y cm)");
-  if (!(alphaPower >= 0.0) || !(alphaPower < 3.0) || alphaPower == 1.0)
-    refuse("alpha_power", std::to_string(alphaPower) + " is outside the power law's range 0 <= y < 3, y != 1");
+  checkMedium();
 
   if (ex == 0 && ey == 0)
   {
@@ -42,34 +37,10 @@ void SecondOrderFramesParameters::init(const DeviceOptions& opt)
   fastPath = options.fusedKernels && isFastLength(ex) && isFastLength(ey);
   tFree = std::min(static_cast<double>(ex - nx) * dx, static_cast<double>(ey - ny) * dy) / c0;
 
-  const size_t n = nPlane();
-  for (size_t i = 0; i < sensorIndex.size(); i++)
-    if (sensorIndex[i] >= n)
-      refuse("sensor_index", "sensor_index[" + std::to_string(i) + "] = " + std::to_string(sensorIndex[i]) +
-                               " is outside the plane of " + std::to_string(n) + " points");
-
-  a = powerLawNepers(alphaCoeff, alphaPower);
-  bSmallest = bLargest = 1.0;
-  if (a > 0.0)
-  {
-    const size_t e[2] = { ex, ey };
-    const double d[2] = { dx, dy };
-    double kSmallest = 0.0, k2Largest = 0.0;
-    for (int i = 0; i < 2; i++)
-    {
-      const double dk = 2.0 * kPi / (static_cast<double>(e[i]) * d[i]);
-      if (e[i] > 1 && (kSmallest == 0.0 || dk < kSmallest)) kSmallest = dk;
-      const double kn = dk * static_cast<double>(e[i] / 2);
-      k2Largest += kn * kn;
-    }
-    bSmallest = damping(kSmallest);
-    bLargest  = damping(std::sqrt(k2Largest));
-    const bool low = !(bSmallest >= 0.25);
-    if (low || !(bLargest >= 0.25))
-      refuse("alpha_coeff", std::to_string(alphaCoeff) + ": a mode of this grid is damped beyond B = 1/4 (B = " +
-                              std::to_string(low ? bSmallest : bLargest) + " at the " + (low ? "smallest non-zero" : "largest") +
-                              " |k|)");
-  }
+  checkSensors(nPlane(), "plane");
+  const size_t e[2] = { ex, ey };
+  const double d[2] = { dx, dy };
+  completeAbsorption(e, d, 2);
 }
 
 std::vector<uint64_t> SecondOrderFramesParameters::expandedSensorIndex() const

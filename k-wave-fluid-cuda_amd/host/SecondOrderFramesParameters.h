@@ -1,7 +1,7 @@
 // SecondOrderFramesParameters.h — input of the batched 2-D exact k-space propagator (SecondOrderFrames): F independent
 // initial pressures p0[f][y][x] on a domain Nx x Ny that share the homogeneous medium, the expanded periodic plane, the
 // sensor points and the aggregates wanted, validated and completed without touching a device (DESIGN.md "Exact k-space
-// propagator on frames").  SecondOrderParameters' rules with the z axis removed:
+// propagator on frames").  SecondOrderParameters' rules with the z axis removed, on the same base (SecondOrderRules):
 //
 //   default E_a (both given sides 0): needs t_max > 0 — the smallest fast-path line length of the fused pipeline at or above
 //   M_a = N_a + ceil(c0 t_max / d_a); where an axis has none (above 1024) or with fusedKernels off, M_a itself.
@@ -23,34 +23,21 @@
 
 #include "GridRules.h"
 
-class SecondOrderFramesParameters
+class SecondOrderFramesParameters : public SecondOrderRules
 {
  public:
   /// checks every parameter and fills in ex / ey where they are 0; throws std::invalid_argument naming the parameter
   void init(const DeviceOptions& options);
 
-  DeviceOptions options;
-  size_t nx = 0, ny = 0;          ///< the domain of one frame
+  size_t nx = 0, ny = 0;          ///< the domain of one frame; sensorIndex: flat indices into one plane [Ny][Nx]
   size_t frames = 0;              ///< F
   double dx = 0, dy = 0;          ///< [m]
-  double c0 = 0;                  ///< [m/s]
-  double alphaCoeff = 0;          ///< [dB / (MHz^y cm)]; 0: lossless
-  double alphaPower = 1.5;        ///< y
-  double tMax = 0;                ///< [s]; read for the default sides only
   size_t ex = 0, ey = 0;          ///< expanded sides; both 0: by the rule
-  std::vector<uint64_t> sensorIndex; ///< 0-based flat indices into one plane [Ny][Nx]
-  bool   pMax = false, pMin = false, pRms = false, pFinal = false; ///< aggregates over the output times of a run
 
-  bool   fastPath = false;        ///< both sides are fast-path lengths (and fusedKernels is on)
-  double a = 0;                   ///< [Np (rad/s)^-y m^-1]
-  double tFree = 0;               ///< [s]
-  double bSmallest = 1, bLargest = 1; ///< B at the smallest non-zero and at the largest |k| of the 2-D grid
   size_t nPlane() const { return nx * ny; }
   size_t nDomain() const { return nx * ny * frames; }
   size_t nExpanded() const { return ex * ey * frames; }
   size_t nReduced() const { return (ex / 2 + 1) * ey * frames; }
-  /// B(|k|) of the completed parameters
-  double damping(double k) const { return GridRule::powerLawDamping(a, c0, alphaPower, k); }
   /// the sensor points of every frame as indices into the expanded batch [F][Ey][Ex], frame by frame
   std::vector<uint64_t> expandedSensorIndex() const;
 

@@ -8,19 +8,6 @@
 
 using namespace GridRule;
 
-namespace
-{
-const double kPi = 3.14159265358979323846;
-
-} // namespace
-
-void SecondOrderParameters::checkTime(double t)
-{
-  if (!(t >= 0.0) || !std::isfinite(t)) refuse("t", std::to_string(t) + " is not a time >= 0");
-}
-
-double SecondOrderParameters::damping(double k) const { return powerLawDamping(a, c0, alphaPower, k); }
-
 void SecondOrderParameters::init(const DeviceOptions& opt)
 {
   options = opt;
@@ -30,11 +17,7 @@ void SecondOrderParameters::init(const DeviceOptions& opt)
   checkPositive(dx, "dx", "spacing");
   checkPositive(dy, "dy", "spacing");
   checkPositive(dz, "dz", "spacing");
-  checkPositive(c0, "c0", "sound speed");
-  if (!(alphaCoeff >= 0.0) || !std::isfinite(alphaCoeff))
-    refuse("alpha_coeff", std::to_string(alphaCoeff) + " is not an absorption >= 0 in dB/(MHz^y cm)");
-  if (!(alphaPower >= 0.0) || !(alphaPower < 3.0) || alphaPower == 1.0)
-    refuse("alpha_power", std::to_string(alphaPower) + " is outside the power law's range 0 <= y < 3, y != 1");
+  checkMedium();
 
   if (ex == 0 && ey == 0 && ez == 0)
   {
@@ -55,34 +38,10 @@ void SecondOrderParameters::init(const DeviceOptions& opt)
   fastPath = options.fusedKernels && isFastLength(ex) && isFastLength(ey) && isFastLength(ez);
   tFree = std::min({ static_cast<double>(ex - nx) * dx, static_cast<double>(ey - ny) * dy, static_cast<double>(ez - nz) * dz }) / c0;
 
-  const size_t n = nDomain();
-  for (size_t i = 0; i < sensorIndex.size(); i++)
-    if (sensorIndex[i] >= n)
-      refuse("sensor_index", "sensor_index[" + std::to_string(i) + "] = " + std::to_string(sensorIndex[i]) +
-                               " is outside the domain of " + std::to_string(n) + " points");
-
-  a = powerLawNepers(alphaCoeff, alphaPower);
-  bSmallest = bLargest = 1.0;
-  if (a > 0.0)
-  {
-    const size_t e[3] = { ex, ey, ez };
-    const double d[3] = { dx, dy, dz };
-    double kSmallest = 0.0, k2Largest = 0.0;
-    for (int i = 0; i < 3; i++)
-    {
-      const double dk = 2.0 * kPi / (static_cast<double>(e[i]) * d[i]);
-      if (e[i] > 1 && (kSmallest == 0.0 || dk < kSmallest)) kSmallest = dk;
-      const double kn = dk * static_cast<double>(e[i] / 2);
-      k2Largest += kn * kn;
-    }
-    bSmallest = damping(kSmallest);
-    bLargest  = damping(std::sqrt(k2Largest));
-    const bool low = !(bSmallest >= 0.25);
-    if (low || !(bLargest >= 0.25))
-      refuse("alpha_coeff", std::to_string(alphaCoeff) + ": a mode of this grid is damped beyond B = 1/4 (B = " +
-                              std::to_string(low ? bSmallest : bLargest) + " at the " + (low ? "smallest non-zero" : "largest") +
-                              " |k|)");
-  }
+  checkSensors(nDomain(), "domain");
+  const size_t e[3] = { ex, ey, ez };
+  const double d[3] = { dx, dy, dz };
+  completeAbsorption(e, d, 3);
 }
 
 std::vector<uint64_t> SecondOrderParameters::expandedSensorIndex() const

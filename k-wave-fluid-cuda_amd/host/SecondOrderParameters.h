@@ -12,7 +12,8 @@
 //   float64; 0 <= y < 3, y != 1.  B = 1 - 2 g T - g^2 with g = a c0^y |k|^(y-1), T = tan(pi y / 2) (0 for y = 2) is concave
 //   in |k|^(y-1), so its minimum over the grid's bins is at the smallest non-zero or at the largest |k|: alpha_coeff is
 //   refused when B is below 1/4 at either.
-// A refusal names the parameter.
+// A refusal names the parameter.  The medium, the sensor points, the aggregates and the completed a, tFree, B, with
+// checkTime, are SecondOrderRules (GridRules.h), shared with SecondOrderFramesParameters.
 #ifndef KW_HOST_SECOND_ORDER_PARAMETERS_H
 #define KW_HOST_SECOND_ORDER_PARAMETERS_H
 #include <cstddef>
@@ -21,34 +22,19 @@
 
 #include "GridRules.h"
 
-class SecondOrderParameters
+class SecondOrderParameters : public SecondOrderRules
 {
  public:
   /// checks every parameter and fills in ex / ey / ez where they are 0; throws std::invalid_argument naming the parameter
   void init(const DeviceOptions& options);
-  /// throws unless t is finite and >= 0
-  static void checkTime(double t);
 
-  DeviceOptions options;
-  size_t nx = 0, ny = 0, nz = 0;  ///< the domain
+  size_t nx = 0, ny = 0, nz = 0;  ///< the domain; sensorIndex: flat indices into [Nz][Ny][Nx]
   double dx = 0, dy = 0, dz = 0;  ///< [m]
-  double c0 = 0;                  ///< [m/s]
-  double alphaCoeff = 0;          ///< [dB / (MHz^y cm)]; 0: lossless
-  double alphaPower = 1.5;        ///< y
-  double tMax = 0;                ///< [s]; read for the default sides only
   size_t ex = 0, ey = 0, ez = 0;  ///< expanded sides; all 0: by the rule
-  std::vector<uint64_t> sensorIndex; ///< 0-based flat indices into the domain [Nz][Ny][Nx]
-  bool   pMax = false, pMin = false, pRms = false, pFinal = false; ///< aggregates over the output times of a run
 
-  bool   fastPath = false;        ///< all three sides are fast-path lengths (and fusedKernels is on)
-  double a = 0;                   ///< [Np (rad/s)^-y m^-1]
-  double tFree = 0;               ///< [s]
-  double bSmallest = 1, bLargest = 1; ///< B at the smallest non-zero and at the largest |k| of the grid
   size_t nDomain() const { return nx * ny * nz; }
   size_t nExpanded() const { return ex * ey * ez; }
   size_t nReduced() const { return (ex / 2 + 1) * ey * ez; }
-  /// B(|k|) of the completed parameters
-  double damping(double k) const;
   /// the sensor points as indices into the expanded volume [Ez][Ey][Ex]
   std::vector<uint64_t> expandedSensorIndex() const;
 };

@@ -246,26 +246,6 @@ struct kwh_second_order
   std::unique_ptr<SecondOrder> propagator;
 };
 
-static SecondOrderParameters kwh_second_order_parameters(const kwh_second_order_config* c, const kwh_options* o)
-{
-  SecondOrderParameters p;
-  p.nx = c->nx; p.ny = c->ny; p.nz = c->nz;
-  p.dx = c->dx; p.dy = c->dy; p.dz = c->dz;
-  p.c0 = c->c0;
-  p.alphaCoeff = c->alpha_coeff;
-  p.alphaPower = c->alpha_power;
-  p.tMax = c->t_max;
-  p.ex = c->ex; p.ey = c->ey; p.ez = c->ez;
-  if (c->n_sensor != 0 && c->sensor_index == nullptr) throw std::invalid_argument("sensor_index: NULL with n_sensor > 0");
-  if (c->n_sensor != 0) p.sensorIndex.assign(c->sensor_index, c->sensor_index + c->n_sensor);
-  p.pMax   = (c->flags & KWH_SECOND_ORDER_P_MAX) != 0;
-  p.pMin   = (c->flags & KWH_SECOND_ORDER_P_MIN) != 0;
-  p.pRms   = (c->flags & KWH_SECOND_ORDER_P_RMS) != 0;
-  p.pFinal = (c->flags & KWH_SECOND_ORDER_P_FINAL) != 0;
-  p.init(kwh_device_options(o));
-  return p;
-}
-
 /// a batched 2-D exact k-space propagator with its completed parameters
 struct kwh_second_order_frames
 {
@@ -273,25 +253,91 @@ struct kwh_second_order_frames
   std::unique_ptr<SecondOrderFrames> propagator;
 };
 
-static SecondOrderFramesParameters kwh_second_order_frames_parameters(const kwh_second_order_frames_config* c, const kwh_options* o)
+/// what the two configs of the exact propagators share: the medium, t_max, the sensor points and the flags
+template <class Config>
+static void kwh_second_order_rules(SecondOrderRules& p, const Config* c)
 {
-  SecondOrderFramesParameters p;
-  p.nx = c->nx; p.ny = c->ny; p.frames = c->frames;
-  p.dx = c->dx; p.dy = c->dy;
   p.c0 = c->c0;
   p.alphaCoeff = c->alpha_coeff;
   p.alphaPower = c->alpha_power;
   p.tMax = c->t_max;
-  p.ex = c->ex; p.ey = c->ey;
   if (c->n_sensor != 0 && c->sensor_index == nullptr) throw std::invalid_argument("sensor_index: NULL with n_sensor > 0");
   if (c->n_sensor != 0) p.sensorIndex.assign(c->sensor_index, c->sensor_index + c->n_sensor);
   p.pMax   = (c->flags & KWH_SECOND_ORDER_P_MAX) != 0;
   p.pMin   = (c->flags & KWH_SECOND_ORDER_P_MIN) != 0;
   p.pRms   = (c->flags & KWH_SECOND_ORDER_P_RMS) != 0;
   p.pFinal = (c->flags & KWH_SECOND_ORDER_P_FINAL) != 0;
+}
+
+static SecondOrderParameters kwh_second_order_parameters(const kwh_second_order_config* c, const kwh_options* o)
+{
+  SecondOrderParameters p;
+  p.nx = c->nx; p.ny = c->ny; p.nz = c->nz;
+  p.dx = c->dx; p.dy = c->dy; p.dz = c->dz;
+  p.ex = c->ex; p.ey = c->ey; p.ez = c->ez;
+  kwh_second_order_rules(p, c);
   p.init(kwh_device_options(o));
   return p;
 }
+
+static SecondOrderFramesParameters kwh_second_order_frames_parameters(const kwh_second_order_frames_config* c, const kwh_options* o)
+{
+  SecondOrderFramesParameters p;
+  p.nx = c->nx; p.ny = c->ny; p.frames = c->frames;
+  p.dx = c->dx; p.dy = c->dy;
+  p.ex = c->ex; p.ey = c->ey;
+  kwh_second_order_rules(p, c);
+  p.init(kwh_device_options(o));
+  return p;
+}
+
+// the entries that kwh_second_order_* and kwh_second_order_frames_* have alike; `who`: the entry's own name
+template <class Handle>
+static int kwh_propagator_destroy(Handle* s)
+{
+  KWH_TRY
+  delete s;
+  KWH_CATCH
+}
+
+template <class Handle>
+static int kwh_propagator_set_p0(const char* who, Handle* s, const float* p0)
+{
+  KWH_TRY
+  if (!s || !p0) throw std::invalid_argument(std::string(who) + ": NULL argument");
+  s->propagator->setP0(p0);
+  KWH_CATCH
+}
+
+template <class Handle>
+static int kwh_propagator_field(const char* who, Handle* s, double t, float* dst)
+{
+  KWH_TRY
+  if (!s) throw std::invalid_argument(std::string(who) + ": NULL propagator");
+  s->propagator->field(t, dst);
+  KWH_CATCH
+}
+
+template <class Handle>
+static int kwh_propagator_run(const char* who, Handle* s, const double* times, uint64_t n_times)
+{
+  KWH_TRY
+  if (!s || (!times && n_times != 0)) throw std::invalid_argument(std::string(who) + ": NULL argument");
+  s->propagator->run(times, n_times);
+  KWH_CATCH
+}
+
+template <class Handle>
+static int kwh_propagator_get(const char* who, Handle* s, const char* name, float* dst, uint64_t n)
+{
+  KWH_TRY
+  if (!s || !name || (!dst && n != 0)) throw std::invalid_argument(std::string(who) + ": NULL argument");
+  s->propagator->get(name, dst, n);
+  KWH_CATCH
+}
+
+template <class Handle>
+static void* kwh_propagator_context(Handle* s) { return s ? s->propagator->context() : nullptr; }
 
 extern "C" {
 
@@ -1037,43 +1083,26 @@ int kwh_second_order_create(const kwh_second_order_config* config, const kwh_opt
   });
 }
 
-int kwh_second_order_destroy(kwh_second_order* s)
-{
-  KWH_TRY
-  delete s;
-  KWH_CATCH
-}
+int kwh_second_order_destroy(kwh_second_order* s) { return kwh_propagator_destroy(s); }
 
 int kwh_second_order_set_p0(kwh_second_order* s, const float* p0)
 {
-  KWH_TRY
-  if (!s || !p0) throw std::invalid_argument("kwh_second_order_set_p0: NULL argument");
-  s->propagator->setP0(p0);
-  KWH_CATCH
+  return kwh_propagator_set_p0("kwh_second_order_set_p0", s, p0);
 }
 
 int kwh_second_order_field(kwh_second_order* s, double t, float* dst)
 {
-  KWH_TRY
-  if (!s) throw std::invalid_argument("kwh_second_order_field: NULL propagator");
-  s->propagator->field(t, dst);
-  KWH_CATCH
+  return kwh_propagator_field("kwh_second_order_field", s, t, dst);
 }
 
 int kwh_second_order_run(kwh_second_order* s, const double* times, uint64_t n_times)
 {
-  KWH_TRY
-  if (!s || (!times && n_times != 0)) throw std::invalid_argument("kwh_second_order_run: NULL argument");
-  s->propagator->run(times, n_times);
-  KWH_CATCH
+  return kwh_propagator_run("kwh_second_order_run", s, times, n_times);
 }
 
 int kwh_second_order_get(kwh_second_order* s, const char* name, float* dst, uint64_t n)
 {
-  KWH_TRY
-  if (!s || !name || (!dst && n != 0)) throw std::invalid_argument("kwh_second_order_get: NULL argument");
-  s->propagator->get(name, dst, n);
-  KWH_CATCH
+  return kwh_propagator_get("kwh_second_order_get", s, name, dst, n);
 }
 
 int kwh_second_order_get_scalar(kwh_second_order* s, const char* name, double* out)
@@ -1092,7 +1121,7 @@ int kwh_second_order_get_scalar(kwh_second_order* s, const char* name, double* o
   KWH_CATCH
 }
 
-void* kwh_second_order_context(kwh_second_order* s) { return s ? s->propagator->context() : nullptr; }
+void* kwh_second_order_context(kwh_second_order* s) { return kwh_propagator_context(s); }
 
 // ---- batched 2-D exact k-space propagator -----------------------------------------------------------------------------
 int kwh_second_order_frames_plan(const kwh_second_order_frames_config* config, const kwh_options* o, uint64_t out_expanded[2],
@@ -1114,43 +1143,26 @@ int kwh_second_order_frames_create(const kwh_second_order_frames_config* config,
   });
 }
 
-int kwh_second_order_frames_destroy(kwh_second_order_frames* s)
-{
-  KWH_TRY
-  delete s;
-  KWH_CATCH
-}
+int kwh_second_order_frames_destroy(kwh_second_order_frames* s) { return kwh_propagator_destroy(s); }
 
 int kwh_second_order_frames_set_p0(kwh_second_order_frames* s, const float* p0)
 {
-  KWH_TRY
-  if (!s || !p0) throw std::invalid_argument("kwh_second_order_frames_set_p0: NULL argument");
-  s->propagator->setP0(p0);
-  KWH_CATCH
+  return kwh_propagator_set_p0("kwh_second_order_frames_set_p0", s, p0);
 }
 
 int kwh_second_order_frames_field(kwh_second_order_frames* s, double t, float* dst)
 {
-  KWH_TRY
-  if (!s) throw std::invalid_argument("kwh_second_order_frames_field: NULL propagator");
-  s->propagator->field(t, dst);
-  KWH_CATCH
+  return kwh_propagator_field("kwh_second_order_frames_field", s, t, dst);
 }
 
 int kwh_second_order_frames_run(kwh_second_order_frames* s, const double* times, uint64_t n_times)
 {
-  KWH_TRY
-  if (!s || (!times && n_times != 0)) throw std::invalid_argument("kwh_second_order_frames_run: NULL argument");
-  s->propagator->run(times, n_times);
-  KWH_CATCH
+  return kwh_propagator_run("kwh_second_order_frames_run", s, times, n_times);
 }
 
 int kwh_second_order_frames_get(kwh_second_order_frames* s, const char* name, float* dst, uint64_t n)
 {
-  KWH_TRY
-  if (!s || !name || (!dst && n != 0)) throw std::invalid_argument("kwh_second_order_frames_get: NULL argument");
-  s->propagator->get(name, dst, n);
-  KWH_CATCH
+  return kwh_propagator_get("kwh_second_order_frames_get", s, name, dst, n);
 }
 
 int kwh_second_order_frames_get_scalar(kwh_second_order_frames* s, const char* name, double* out)
@@ -1171,7 +1183,7 @@ int kwh_second_order_frames_get_scalar(kwh_second_order_frames* s, const char* n
   KWH_CATCH
 }
 
-void* kwh_second_order_frames_context(kwh_second_order_frames* s) { return s ? s->propagator->context() : nullptr; }
+void* kwh_second_order_frames_context(kwh_second_order_frames* s) { return kwh_propagator_context(s); }
 
 int kwh_second_order_frames_line_plan(const kwh_second_order_frames_config* config, const kwh_options* o, int64_t row,
                                       uint64_t chunk_times, uint64_t n_times, uint64_t out[3])

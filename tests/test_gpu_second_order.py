@@ -314,6 +314,37 @@ def test_second_order_against_the_restatement(second_order, coeff, n, fused):
         p.close()
 
 
+@pytest.mark.parametrize("n,fused", [((24, 20, 18), True), ((23, 19, 17), False)], ids=["fused", "rocfft"])
+def test_run_again_regrows_reuses_and_resets(second_order, n, fused):
+    """run three times on one object: three times, five others (the record grows), the three again (the larger record is
+    kept).  Every run's record and aggregates are those of its own times alone: the bits of field(t), p_rms within the
+    parity bound of the float64 root mean square of those float32 fields."""
+    sensors = e2e_sensors(n)
+    t1, t2 = E2E_TIMES[[5, 3, 10]], E2E_TIMES[[2, 7, 0, 4, 9]]
+    p = second_order.SecondOrder(n, E2E_D, C0, alpha_coeff=E2E_COEFF, alpha_power=1.5, t_max=E2E_TMAX, sensor_index=sensors,
+                                 record=("p_raw", "p_max", "p_min", "p_rms", "p_final"), fused_kernels=fused)
+    try:
+        assert p.fused == fused
+        p.set_p0(e2e_p0(n, 5))
+        fields = np.array([p.field(t) for t in t2])
+        first = p.run(t1)
+        assert first.shape == (3, 7)
+        rec = p.run(t2)
+        assert rec.shape == (5, 7) and np.array_equal(rec, fields.reshape(5, -1)[:, sensors])
+        assert np.array_equal(p.p_max(), fields.max(axis=0)) and np.array_equal(p.p_min(), fields.min(axis=0))
+        assert np.array_equal(p.p_final(), fields[-1])
+        e_rms = sr.rel_l2(p.p_rms(), np.sqrt(np.mean(fields.astype(np.float64) ** 2, axis=0)))
+        print(f"SecondOrder {n} fused {fused}: p_rms of a second run against its own fields {e_rms:.3e}")
+        assert e_rms < PARITY
+        again = p.run(t1)
+        assert again.shape == (3, 7) and np.array_equal(again, first)
+        p_max = p.p_max()
+        assert np.array_equal(p_max, np.array([p.field(t) for t in t1]).max(axis=0))
+        assert p.runs == 3
+    finally:
+        p.close()
+
+
 def test_two_interleaved_propagators_do_not_disturb_each_other(second_order):
     n = (24, 20, 18)
     pa, pb = e2e_p0(n, 2), e2e_p0(n, 3)
