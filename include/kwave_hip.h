@@ -992,7 +992,26 @@ KW_API kw_status kw_line_recon_crop(kw_ctx* ctx, float* out, const float* vol, u
  *   KW_OK, nothing launched.
  * Embedding and crop: kw_angular_time_embed and kw_plane_recon_crop (a 3-D corner either way).  Sensor records and the
  * aggregates over the output times: kw_sample_index and kw_sample_all on the volume and on the crop.
- * Not built: dp0/dt as a second initial condition and time-varying sources, heterogeneous media, Z-slabs, several output
+ *
+ * dp0/dt as a second initial condition (csrc/kw_second_order_pair.hip; k-Wave's source.dp0dt): p(0) = P0, p'(0) = V0 with
+ * V0 = F{dp0dt embedded} [Pa/s], the same per-mode equation:
+ *     p^(t) = Hc(|k|; t) P0 + Hs(|k|; t) V0          Hc = the H above
+ *     lossless:  Hs = sin(c0 |k| t) / (c0 |k|)       absorbing: Hs = exp(-gamma t) sin(w_d t) / w_d       |k| = 0: Hs = t
+ * Hs [s] is real and depends on |k| only.  (Hc, Hs) per bin is ONE device function (second_h_pair) for the fused passes and
+ * the twins: second_h's float64 expressions in its order up to the phase word, ONE sincosf of the word's angle for both,
+ *   float64: w = c0 * k (lossless), (c0 * k) * r (absorbing)
+ *   float32: Hc = (E * (cos + (q * sin))) * divider;  Hs = ((E * sin) * float(1.0 / w)) * divider;  E = 1, q = 0 lossless
+ *            k2 == 0: (divider, float(t) * divider);   out = ((Hc * x.x) + (Hs * y.x), (Hc * x.y) + (Hs * y.y))
+ * kw_fused_second_order_time_pair: vol_out <- the pressure at op->t from kept_p and kept_v, each a kept spectrum of
+ *   kw_fused_second_order_forward in an array of kw_fused_second_order_elems values: one launch
+ *   k_zfused_second_order_pair (lines of both forward along z, the second one's requested while the first is transformed,
+ *   the mix in registers, ONE inverse along z into scratch array 0), then the y-inverse and the storing x-inverse of
+ *   kw_fused_second_order_time.  Neither kept array is written.  Its refusals are kw_fused_second_order_time's.
+ * kw_second_order_mix_pair: the twin: out_spec <- Hc spec_p + Hs spec_v on the natural half-spectra, out of place
+ *   (out_spec is neither input), any sizes.  A context without bins: KW_OK, nothing launched.
+ * kw_fused_second_order_time and kw_second_order_mix are what they were: without dp0dt nothing else is launched.
+ *
+ * Not built: time-varying sources, heterogeneous media, Z-slabs, several output
  * times per z-pass, inverse passes restricted to the crop or to the sensor points, particle velocity.  (2-D: the batched
  * form on a frames context, below.)
  * ---------------------------------------------------------------------------------------------------------------- */
@@ -1007,6 +1026,10 @@ KW_API kw_status kw_fused_second_order_forward(kw_ctx* ctx, const float* vol, fl
 KW_API kw_status kw_fused_second_order_time(kw_ctx* ctx, const float* kept, const kw_second_order_op* op, float* vol_out);
 KW_API kw_status kw_second_order_mix(kw_ctx* ctx, float* out_spec, const float* spec, const kw_second_order_op* op,
                                      float divider);
+KW_API kw_status kw_fused_second_order_time_pair(kw_ctx* ctx, const float* kept_p, const float* kept_v,
+                                                 const kw_second_order_op* op, float* vol_out);
+KW_API kw_status kw_second_order_mix_pair(kw_ctx* ctx, float* out_spec, const float* spec_p, const float* spec_v,
+                                          const kw_second_order_op* op, float divider);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Exact k-space propagator on frames: the batched 2-D form of the operator above (csrc/kw_second_order.hip,
@@ -1038,7 +1061,16 @@ KW_API kw_status kw_second_order_mix(kw_ctx* ctx, float* out_spec, const float* 
  *   nothing launched.
  * Embedding and crop: kw_angular_time_embed and kw_plane_recon_crop with the frame count in the slowest position.  The
  * record: kw_sample_index on the expanded batch; the aggregates: kw_sample_all on the crop.
- * Not built: dp0/dt as a second initial condition and time-varying sources, heterogeneous media, chunks of frames and
+ * dp0/dt as a second initial condition: the 3-D section's operator and device function (second_h_pair), the bin along y
+ * where the z bin stands.
+ * kw_fused_second_order_frames_time_pair: vol_out <- every frame's pressure at op->t from kept_p and kept_v (each from
+ *   kw_fused_second_order_frames_forward, kw_fused_second_order_frames_elems values): ONE launch k_yfused_second_order_pair
+ *   (k_yfused_second_order's tiles and side blocks; both spectra forward along y, the mix in registers, ONE inverse) and the
+ *   storing x-inverse.  Neither kept array is written.  KW_ERR_STATE before kw_fused_create, KW_ERR_INVALID outside frames
+ *   mode, as kw_fused_second_order_frames_time.
+ * kw_second_order_frames_mix_pair: the twin on the natural spectra [F][Ey][Ex/2 + 1], out of place, any sizes.  A context
+ *   without bins: KW_OK, nothing launched.
+ * Not built: dp0/dt in the line-sensor record below, time-varying sources, heterogeneous media, chunks of frames and
  * frames over several GPUs, particle velocity.  Several output times per pass and an x-inverse restricted to the rows that
  * hold sensors: served for a single row by the line-sensor record below, not otherwise.
  * ---------------------------------------------------------------------------------------------------------------- */
@@ -1048,6 +1080,10 @@ KW_API kw_status kw_fused_second_order_frames_time(kw_ctx* ctx, const float* kep
                                                    float* vol_out);
 KW_API kw_status kw_second_order_frames_mix(kw_ctx* ctx, float* out_spec, const float* spec, const kw_second_order_op* op,
                                             float divider);
+KW_API kw_status kw_fused_second_order_frames_time_pair(kw_ctx* ctx, const float* kept_p, const float* kept_v,
+                                                        const kw_second_order_op* op, float* vol_out);
+KW_API kw_status kw_second_order_frames_mix_pair(kw_ctx* ctx, float* out_spec, const float* spec_p, const float* spec_v,
+                                                 const kw_second_order_op* op, float divider);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Line-sensor record of the propagator on frames: what the row y = r dy of every frame records at many output times, with

@@ -487,7 +487,14 @@ KWH_API void*    kwh_line_recon_context(kwh_line_recon* s);
  * default), alpha_coeff (< 0, the B rule), alpha_power (outside 0 <= y < 3, y = 1), Ex Ey Ez (missing, below N), E (2^32 points
  * or more), sensor_index (NULL, an entry outside the domain), t (negative or not finite), n_times (0).
  * Of kwh_options the calls read device_idx and fused_kernels.  kwh_second_order_plan validates and completes (Ex, Ey, Ez)
- * and the fast-path flag without a device.  Not built: dp0/dt as a second initial condition and time-varying sources,
+ * and the fast-path flag without a device.
+ *   dp0/dt (k-Wave's source.dp0dt): kwh_second_order_set_dp0dt gives dp/dt at t = 0 [Pa/s] as a second initial condition,
+ *   p^(t) = Hc P0 + Hs V0 per mode (kwave_hip.h); with dp0dt = -c0 df/dx beside p0 = f(x) it launches a one-way
+ *   wave, and (p, dp/dt) of a snapshot continue a field.  It is independent of set_p0 — either may be called again in any
+ *   order, neither resets the other; set_p0 stays required before field / run and may be all zeros —, NULL clears it and
+ *   the propagator then launches what one without it launches.  The second kept spectrum is allocated at the first call.
+ *   The scalar "has_dp0dt" reports 0 / 1.
+ * Not built: time-varying sources,
  * heterogeneous media, Z-slabs, HDF5 files and the command line, graphs, several output times per z-pass, inverse passes restricted to the crop or to the sensor points, particle velocity outputs.
  * ---------------------------------------------------------------------------------------------------------------- */
 #define KWH_SECOND_ORDER_P_MAX   1
@@ -516,13 +523,15 @@ KWH_API int      kwh_second_order_create(const kwh_second_order_config* config, 
 KWH_API int      kwh_second_order_destroy(kwh_second_order* s);
 /* p0: Nx * Ny * Nz floats on the host ([Nz][Ny][Nx]): embed, transform, keep; may be called again */
 KWH_API int      kwh_second_order_set_p0(kwh_second_order* s, const float* p0);
+/* dp0dt: Nx * Ny * Nz floats on the host ([Nz][Ny][Nx]), dp/dt at t = 0 [Pa/s]: embed, transform, keep; NULL clears it */
+KWH_API int      kwh_second_order_set_dp0dt(kwh_second_order* s, const float* dp0dt);
 /* the pressure at time t; the crop [Nz][Ny][Nx] stays on the device ("p") and goes to dst where dst is not NULL */
 KWH_API int      kwh_second_order_field(kwh_second_order* s, double t, float* dst);
 /* every time in the given order: row i of the record, the aggregates */
 KWH_API int      kwh_second_order_run(kwh_second_order* s, const double* times, uint64_t n_times);
 /* "p_raw" [n_times][n_sensor], "p_max", "p_min", "p_rms", "p_final" of the last run, "p" (the last field); n checked */
 KWH_API int      kwh_second_order_get(kwh_second_order* s, const char* name, float* dst, uint64_t n);
-/* "fused_pipeline", "Ex", "Ey", "Ez", "t_free", "runs" */
+/* "fused_pipeline", "Ex", "Ey", "Ez", "t_free", "runs", "has_dp0dt" */
 KWH_API int      kwh_second_order_get_scalar(kwh_second_order* s, const char* name, double* out);
 /* the underlying kw_ctx* (include/kwave_hip.h) */
 KWH_API void*    kwh_second_order_context(kwh_second_order* s);
@@ -543,7 +552,9 @@ KWH_API void*    kwh_second_order_context(kwh_second_order* s);
  * the sides are by default), alpha_coeff (< 0, the B rule), alpha_power (outside 0 <= y < 3, y = 1), Ex Ey (missing, below N),
  * E (2^32 points or more), sensor_index (NULL, an entry outside the plane), t (negative or not finite), n_times (0).
  * flags: KWH_SECOND_ORDER_P_*.  kwh_second_order_frames_plan validates and completes (Ex, Ey) and the fast-path flag
- * without a device.  Not built: dp0/dt as a second initial condition and time-varying sources, heterogeneous media,
+ * without a device.  kwh_second_order_frames_set_dp0dt: dp/dt at t = 0 of every frame as a second initial condition, with
+ * the rules of kwh_second_order_set_dp0dt; the scalar "has_dp0dt".  Not built: dp0/dt in the line-sensor record,
+ * time-varying sources, heterogeneous media,
  * chunks of frames and frames over several GPUs, particle velocity outputs, HDF5 files and the command line, graphs.
  * Several output times per pass and an x-inverse restricted to the rows that hold sensors: for one row, the line-sensor
  * record below.
@@ -571,13 +582,15 @@ KWH_API int      kwh_second_order_frames_create(const kwh_second_order_frames_co
 KWH_API int      kwh_second_order_frames_destroy(kwh_second_order_frames* s);
 /* p0: Nx * Ny * F floats on the host ([F][Ny][Nx]): embed, transform, keep; may be called again */
 KWH_API int      kwh_second_order_frames_set_p0(kwh_second_order_frames* s, const float* p0);
+/* dp0dt: Nx * Ny * F floats on the host ([F][Ny][Nx]), dp/dt at t = 0 [Pa/s]: embed, transform, keep; NULL clears it */
+KWH_API int      kwh_second_order_frames_set_dp0dt(kwh_second_order_frames* s, const float* dp0dt);
 /* every frame's pressure at time t; the crop [F][Ny][Nx] stays on the device ("p") and goes to dst where dst is not NULL */
 KWH_API int      kwh_second_order_frames_field(kwh_second_order_frames* s, double t, float* dst);
 /* every time in the given order: row i of the record, the aggregates */
 KWH_API int      kwh_second_order_frames_run(kwh_second_order_frames* s, const double* times, uint64_t n_times);
 /* "p_raw" [n_times][F][n_sensor], "p_max", "p_min", "p_rms", "p_final" of the last run ([F][Ny][Nx]), "p"; n checked */
 KWH_API int      kwh_second_order_frames_get(kwh_second_order_frames* s, const char* name, float* dst, uint64_t n);
-/* "fused_pipeline", "Ex", "Ey", "frames", "t_free", "runs" */
+/* "fused_pipeline", "Ex", "Ey", "frames", "t_free", "runs", "has_dp0dt", "line_row", "line_chunk_times" */
 KWH_API int      kwh_second_order_frames_get_scalar(kwh_second_order_frames* s, const char* name, double* out);
 /* the underlying kw_ctx* (include/kwave_hip.h) */
 KWH_API void*    kwh_second_order_frames_context(kwh_second_order_frames* s);
@@ -593,7 +606,8 @@ KWH_API void*    kwh_second_order_frames_context(kwh_second_order_frames* s);
  *     "line_row" and "line_chunk_times" report what is in effect.
  *   line_record: dst [F][n_times][Nx] floats on the host, x fastest, or NULL (the passes run, nothing is copied); times in
  *     any order, each >= 0 and finite; t = 0 gives the row of p0.  Refused: "line_record: no line row set", "line_record: no
- *     p0 since the line row was set", n_times (0), t.  field, run and line_record may be interleaved: the record touches
+ *     p0 since the line row was set", n_times (0), t, and while a dp0dt is set (the message names dp0dt and points to
+ *     run(times); the record takes p0 alone).  field, run and line_record may be interleaved: the record touches
  *     neither "p" nor the aggregates and the record of run.  A value's bits do not depend on F, on the other times of the call
  *     or on the passes.
  *   line_plan: the checks of row, chunk_times and n_times without a device; out: the times of one pass, the passes of

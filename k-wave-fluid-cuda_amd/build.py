@@ -24,7 +24,7 @@ HIPCC = os.path.join(ROCM, "bin", "hipcc")
 # measured from scratch, 8 jobs side by side: 185 s down to 65 s in this order, every other object at most 11 s)
 SLOWEST_FIRST = ("kw_fused_xinv_other.hip", "kw_fused_main.hip", "kw_fused_xinv_density_plain_tail.hip",
                  "kw_fused_xinv_density_chain_tail.hip", "kw_fused_xinv_other_tail.hip", "kw_fused_xinv_density_plain_long.hip",
-                 "kw_fused_xinv_density_chain_long.hip", "kw_cw.hip", "kw_angular_time.hip", "kw_second_order.hip", "kw_plane_recon.hip", "kw_line_recon.hip",
+                 "kw_fused_xinv_density_chain_long.hip", "kw_cw.hip", "kw_angular_time.hip", "kw_second_order.hip", "kw_second_order_pair.hip", "kw_plane_recon.hip", "kw_line_recon.hip",
                  "kw_angular.hip",
                  "kw_fused_xinv_density_stokes_tail.hip",
                  "kw_fused_xinv_density_chain_short.hip", "kw_fused_xinv_density_plain_short.hip",

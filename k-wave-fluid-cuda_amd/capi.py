@@ -212,10 +212,14 @@ _SIG: Dict[str, list] = {
     "kw_fused_second_order_forward": [_P, _P, _P],
     "kw_fused_second_order_time": [_P, _P, _P, _P],
     "kw_second_order_mix": [_P, _P, _P, _P, C.c_float],
+    "kw_fused_second_order_time_pair": [_P, _P, _P, _P, _P],
+    "kw_second_order_mix_pair": [_P, _P, _P, _P, _P, C.c_float],
     "kw_fused_second_order_frames_elems": [_P, C.POINTER(C.c_size_t)],
     "kw_fused_second_order_frames_forward": [_P, _P, _P],
     "kw_fused_second_order_frames_time": [_P, _P, _P, _P],
     "kw_second_order_frames_mix": [_P, _P, _P, _P, C.c_float],
+    "kw_fused_second_order_frames_time_pair": [_P, _P, _P, _P, _P],
+    "kw_second_order_frames_mix_pair": [_P, _P, _P, _P, _P, C.c_float],
     "kw_second_order_line_elems": [_P, C.POINTER(C.c_size_t)],
     "kw_second_order_line_prepare": [_P, _P, _P, C.c_uint32],
     "kw_second_order_line_record": [_P, _P, _P, _P, _P, C.c_uint32],

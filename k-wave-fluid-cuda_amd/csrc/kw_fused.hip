@@ -209,6 +209,10 @@ kw_status yfused_line_recon(kw_ctx* ctx, float2* s, const kw_plane_recon_op* op)
 // the pass along y of kw_fused_second_order_frames_time (frames context): lines of `in` (the kept spectrum of the frames)
 // forward along y, the real H(|k|; t) of the plane formed in registers, the inverse, to `out` (kw_second_order.hip)
 kw_status yfused_second_order(kw_ctx* ctx, const float2* in, float2* out, const kw_second_order_op* op);
+// the same two passes with dp0/dt as a second initial condition (kw_second_order_pair.hip): lines of both kept spectra
+// forward, Hc in_p + Hs in_v in registers, ONE inverse, to `out`
+kw_status zfused_second_order_pair(kw_ctx* ctx, const float2* in_p, const float2* in_v, float2* out, const kw_second_order_op* op);
+kw_status yfused_second_order_pair(kw_ctx* ctx, const float2* in_p, const float2* in_v, float2* out, const kw_second_order_op* op);
 // the tuning probes of kw_fused_probe that launch no pipeline kernel (kw_fused_probe.hip)
 kw_status probe_patterns(kw_ctx* ctx, int which, const float* op);
 
@@ -489,7 +493,7 @@ template<int L, int DIR> __device__ __forceinline__ void step_a(float2 (&v)[Fac<
 // four-step transform through the block's buffer lds[G::LDSB].  A kernel's body keeps what is its own — which arrays,
 // what happens to a bin between the transforms — and the order of loads, barriers and stores.
 // On the steps: k_zfused_split, k_zfused_pair_split (kw_cw.hip), k_zfused_time (kw_angular_time.hip), k_zfused_second_order
-// and k_yfused_second_order (kw_second_order.hip), k_zfused_recon (kw_plane_recon.hip), k_yfused_line_recon (kw_line_recon.hip); k_ypass and k_ypass_split take the tile and keep their
+// and k_yfused_second_order (kw_second_order.hip), their pair forms (kw_second_order_pair.hip), k_zfused_recon (kw_plane_recon.hip), k_yfused_line_recon (kw_line_recon.hip); k_ypass and k_ypass_split take the tile and keep their
 // RowAddr loads and stores.  k_zfused, k_zfused_pair (kw_cw.hip) and k_yinv_angular (kw_angular.hip) spell the same steps out in their bodies: assembled from
 // the functions below the compiler allocates their guarded (non-whole-wave) and spilling instantiations differently — an
 // occupancy step lost at some lengths, scratch bytes gained at others — so they stay as they were written.  A change to

@@ -1538,6 +1538,23 @@ kw_status kw_fused_second_order_time(kw_ctx* ctx, const float* kept, const kw_se
   return store_scratch0(ctx, vol_out);
 }
 
+// The same stage with dp0/dt as a second initial condition (kw_second_order_pair.hip): `kept_v` is the kept spectrum of the
+// embedded dp0dt (kw_fused_second_order_forward into an array of its own); k_zfused_second_order_pair carries both forward,
+// mixes them in registers and runs one inverse, so the y-inverse and the x-inverse are the single stage's.
+kw_status kw_fused_second_order_time_pair(kw_ctx* ctx, const float* kept_p, const float* kept_v, const kw_second_order_op* op,
+                                          float* vol_out)
+{
+  KW_FUSED_READY(ctx);
+  KW_PROF(ctx, "fused_second_order_time_pair");
+  KW_REQUIRE(kept_p && kept_v && op && vol_out);
+  KW_TRY(single_gpu_only(ctx, __func__));
+  KW_REQUIRE(op->dx > 0.0 && op->dy > 0.0 && op->dz > 0.0 && op->c0 > 0.0 && op->t >= 0.0);
+  KW_REQUIRE(op->absorbing == 0 || (op->a >= 0.0 && op->alpha_power >= 0.0 && op->alpha_power != 1.0));
+  KW_TRY(zfused_second_order_pair(ctx, reinterpret_cast<const float2*>(kept_p), reinterpret_cast<const float2*>(kept_v),
+                                  ctx->fused.s[0], op));
+  return store_scratch0(ctx, vol_out);
+}
+
 // k-space plane reconstruction (kw_plane_recon.hip): kw_fused_scale_source's round trip with k_zfused_recon as its z-pass —
 // the weight and the gather from w to kz happen along the line the z-pass holds in LDS.
 kw_status kw_fused_plane_recon(kw_ctx* ctx, const float* vol_even, const kw_plane_recon_op* op, float* vol_out)
@@ -1615,6 +1632,20 @@ kw_status kw_fused_second_order_frames_time(kw_ctx* ctx, const float* kept, cons
   KW_REQUIRE(op->dx > 0.0 && op->dy > 0.0 && op->c0 > 0.0 && op->t >= 0.0); // (dz is not looked at)
   KW_REQUIRE(op->absorbing == 0 || (op->a >= 0.0 && op->alpha_power >= 0.0 && op->alpha_power != 1.0));
   KW_TRY(yfused_second_order(ctx, reinterpret_cast<const float2*>(kept), ctx->fused.s[0], op));
+  return store_scratch0(ctx, vol_out, false);
+}
+
+// with dp0/dt: ONE launch of k_yfused_second_order_pair over both kept spectra and the storing x-inverse
+kw_status kw_fused_second_order_frames_time_pair(kw_ctx* ctx, const float* kept_p, const float* kept_v,
+                                                 const kw_second_order_op* op, float* vol_out)
+{
+  KW_FRAMES_STAGE_READY(ctx);
+  KW_PROF(ctx, "fused_second_order_frames_time_pair");
+  KW_REQUIRE(kept_p && kept_v && op && vol_out);
+  KW_REQUIRE(op->dx > 0.0 && op->dy > 0.0 && op->c0 > 0.0 && op->t >= 0.0); // (dz is not looked at)
+  KW_REQUIRE(op->absorbing == 0 || (op->a >= 0.0 && op->alpha_power >= 0.0 && op->alpha_power != 1.0));
+  KW_TRY(yfused_second_order_pair(ctx, reinterpret_cast<const float2*>(kept_p), reinterpret_cast<const float2*>(kept_v),
+                                  ctx->fused.s[0], op));
   return store_scratch0(ctx, vol_out, false);
 }
 

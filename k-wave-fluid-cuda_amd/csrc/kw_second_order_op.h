@@ -1,5 +1,5 @@
 // kw_second_order_op.h — what the code objects of the exact k-space propagator share (kw_second_order.hip: the passes and
-// their rocFFT twins; kw_second_order_line.hip: the line-sensor record): the constants that H needs besides the bin, how
+// their rocFFT twins; kw_second_order_pair.hip: the same with dp0/dt; kw_second_order_line.hip: the line-sensor record): the constants that H needs besides the bin, how
 // |k|^(y-1) is formed, their float64 derivation from a kw_second_order_op on the host, and the validation of that struct.
 #ifndef KW_SECOND_ORDER_OP_H
 #define KW_SECOND_ORDER_OP_H
@@ -15,6 +15,7 @@ struct SecondH
 {
   double   dkx, dky, dkz;   // 2 pi / (E? d?)
   double   ct;              // c0 t
+  double   c0, t;           // for Hs (kw_second_order_pair.hip): w = c0 k, and Hs = t at |k| = 0
   double   ac, twoT, ym1;   // a c0^y, 2 tan(pi y / 2) (0 for y = 2), y - 1
   float    divider;
   uint32_t ex, ey, ez;
@@ -32,6 +33,8 @@ enum : uint32_t { kPowGeneral = 0, kPowStokes = 1, kPowHalf = 2 };
   g.dky = kTwoPi / (static_cast<double>(c.ny) * op->dy);
   g.dkz = frames ? g.dky : kTwoPi / (static_cast<double>(c.nz) * op->dz);
   g.ct  = op->c0 * op->t;
+  g.c0  = op->c0;
+  g.t   = op->t;
   g.divider = divider;
   g.ex = c.nx; g.ey = c.ny; g.ez = frames ? c.ny : c.nz;
   g.absorbing = (op->absorbing != 0 && op->a > 0.0) ? 1u : 0u;

@@ -9,6 +9,8 @@ const SecondOrderEntries kEntries = { false,
                                       kw_fused_second_order_forward,
                                       kw_fused_second_order_time,
                                       kw_second_order_mix,
+                                      kw_fused_second_order_time_pair,
+                                      kw_second_order_mix_pair,
                                       kw_fft_r2c_3d,
                                       kw_fft_c2r_3d };
 

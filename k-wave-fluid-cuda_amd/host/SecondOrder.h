@@ -13,7 +13,7 @@
 //
 // Device memory, E = Ex Ey Ez points, R = (Ex/2 + 1) Ey Ez bins, N the domain: the volume 4 E, the kept spectrum (8 R; a
 // scratch array on the fast path) and the pipeline's three scratch arrays (fast path) or one more spectrum 8 R (rocFFT);
-// the crop 4 N and 4 N per aggregate; the record 4 n_times n_sensor.
+// the crop 4 N and 4 N per aggregate; the record 4 n_times n_sensor.  From the first setDp0dt on: a second kept spectrum.
 #ifndef KW_HOST_SECOND_ORDER_H
 #define KW_HOST_SECOND_ORDER_H
 #include <string>
@@ -30,6 +30,11 @@ class SecondOrder
 
   /// p0: Nx Ny Nz floats on the host, [Nz][Ny][Nx]; may be called again
   void setP0(const float* p0) { mCore.setP0(p0); }
+  /// dp/dt at t = 0 [Pa/s], Nx Ny Nz floats on the host, [Nz][Ny][Nx]; NULL clears it.  Independent of setP0.  field and
+  /// run then take both conditions (kw_fused_second_order_time_pair / kw_second_order_mix_pair); the second kept spectrum
+  /// (8 R more) exists from the first call on.
+  void setDp0dt(const float* dp0dt) { mCore.setDp0dt(dp0dt); }
+  bool hasDp0dt() const { return mCore.hasDp0dt(); }
   /// the pressure at time t on the domain; dst: Nx Ny Nz floats on the host or NULL (the crop stays on the device)
   void field(double t, float* dst) { mCore.field(t, dst); }
   /// every time in the given order: the record's row, the aggregates

@@ -18,7 +18,8 @@ SecondOrderCore::SecondOrderCore(const SecondOrderRules& rules, const SecondOrde
   size_t kept = nr;
   if (fused) mGrid.check(mForm.entries->elems(ctx(), &kept));
   else mSpec = mGrid.array(2 * nr);
-  mKept = mGrid.array(2 * kept);
+  mKeptFloats = 2 * kept;
+  mKept = mGrid.array(mKeptFloats);
   mP    = mGrid.array(nd);
   if (rules.pMax) mMax = mGrid.array(nd);
   if (rules.pMin) mMin = mGrid.array(nd);
@@ -32,17 +33,35 @@ SecondOrderCore::SecondOrderCore(const SecondOrderRules& rules, const SecondOrde
   mGrid.check(kw_sync(ctx()));
 }
 
-void SecondOrderCore::setP0(const float* p0)
+void SecondOrderCore::keep(const float* src, float* kept)
 {
   const SecondOrderForm& f = mForm;
-  mGrid.check(kw_memcpy_h2d(ctx(), mP, p0, f.nDomain() * sizeof(float)));
+  mGrid.check(kw_memcpy_h2d(ctx(), mP, src, f.nDomain() * sizeof(float)));
   mGrid.check(kw_angular_time_embed(ctx(), mVol, mP, static_cast<uint32_t>(f.ex), static_cast<uint32_t>(f.ey),
                                     static_cast<uint32_t>(f.ez), static_cast<uint32_t>(f.nx), static_cast<uint32_t>(f.ny),
                                     static_cast<uint32_t>(f.nz)));
-  if (mGrid.fused()) mGrid.check(f.entries->forward(ctx(), mVol, mKept));
-  else mGrid.check(f.entries->r2c(ctx(), mVol, mKept));
+  if (mGrid.fused()) mGrid.check(f.entries->forward(ctx(), mVol, kept));
+  else mGrid.check(f.entries->r2c(ctx(), mVol, kept));
+  mHaveField = false; // (mP has been the staging array)
+}
+
+void SecondOrderCore::setP0(const float* p0)
+{
+  keep(p0, mKept);
   mHaveInput = true;
-  mHaveField = false;
+}
+
+void SecondOrderCore::setDp0dt(const float* dp0dt)
+{
+  if (dp0dt == nullptr)
+  {
+    mHaveDp0dt = false; // (the array stays: the next setDp0dt finds it)
+    return;
+  }
+  if (mKeptV == nullptr) mKeptV = mGrid.array(mKeptFloats);
+  mHaveDp0dt = false;
+  keep(dp0dt, mKeptV);
+  mHaveDp0dt = true;
 }
 
 kw_second_order_op SecondOrderCore::op(double t) const
@@ -55,10 +74,12 @@ kw_second_order_op SecondOrderCore::op(double t) const
 void SecondOrderCore::propagate(double t)
 {
   const kw_second_order_op op = this->op(t);
-  if (mGrid.fused()) mGrid.check(mForm.entries->time(ctx(), mKept, &op, mVol));
+  if (mGrid.fused())
+    mGrid.check(mHaveDp0dt ? mForm.entries->timePair(ctx(), mKept, mKeptV, &op, mVol) : mForm.entries->time(ctx(), mKept, &op, mVol));
   else
   {
-    mGrid.check(mForm.entries->mix(ctx(), mSpec, mKept, &op, mForm.divider));
+    if (mHaveDp0dt) mGrid.check(mForm.entries->mixPair(ctx(), mSpec, mKept, mKeptV, &op, mForm.divider));
+    else mGrid.check(mForm.entries->mix(ctx(), mSpec, mKept, &op, mForm.divider));
     mGrid.check(mForm.entries->c2r(ctx(), mSpec, mVol));
   }
 }

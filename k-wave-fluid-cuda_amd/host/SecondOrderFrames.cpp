@@ -13,6 +13,8 @@ const SecondOrderEntries kEntries = { true,
                                       kw_fused_second_order_frames_forward,
                                       kw_fused_second_order_frames_time,
                                       kw_second_order_frames_mix,
+                                      kw_fused_second_order_frames_time_pair,
+                                      kw_second_order_frames_mix_pair,
                                       kw_fft_r2c_frames,
                                       kw_fft_c2r_frames };
 
@@ -112,6 +114,9 @@ void SecondOrderFrames::lineRecord(const double* times, size_t nTimes, float* ds
 {
   if (mLineRow < 0) throw std::invalid_argument("line_record: no line row set");
   if (!mLine.ready) throw std::invalid_argument("line_record: no p0 since the line row was set");
+  if (mCore.hasDp0dt())
+    throw std::invalid_argument("line_record: a dp0dt is set and the line record takes p0 alone (not built: dp0dt in "
+                                "line_record); clear it with set_dp0dt(NULL), or sample the row with run(times)");
   const size_t chunkTimes = std::min(lineChunkTimes(), std::max<size_t>(nTimes, 1));
   const std::vector<SecondOrderFramesParameters::LineChunk> chunks = SecondOrderFramesParameters::lineChunks(nTimes, chunkTimes);
   for (size_t i = 0; i < nTimes; i++) SecondOrderRules::checkTime(times[i]);

@@ -21,7 +21,7 @@
 //
 // Device memory, E = Ex Ey F points, R = (Ex/2 + 1) Ey F bins, N = Nx Ny F: the batch 4 E, the kept spectrum (8 R; a scratch
 // array on the fast path) and the pipeline's scratch arrays (fast path) or one more spectrum 8 R (rocFFT); the crop 4 N and
-// 4 N per aggregate; the record 4 n_times F n_sensor.  With a line row: Q 8 (Ex/2 + 1) (Ey/2 + 1) F, on the fast path the
+// 4 N per aggregate; the record 4 n_times F n_sensor.  From the first setDp0dt on: a second kept spectrum.  With a line row: Q 8 (Ex/2 + 1) (Ey/2 + 1) F, on the fast path the
 // natural spectra 8 R as well, the times 8 n_times, and per pass of T times G 8 (Ex/2 + 1) F T, its rows 4 Ex F T and their
 // crop 4 Nx F T.
 #ifndef KW_HOST_SECOND_ORDER_FRAMES_H
@@ -41,6 +41,11 @@ class SecondOrderFrames
 
   /// p0: Nx Ny F floats on the host, [F][Ny][Nx]; may be called again
   void setP0(const float* p0);
+  /// dp/dt at t = 0 of every frame [Pa/s], Nx Ny F floats on the host, [F][Ny][Nx]; NULL clears it.  Independent of setP0.
+  /// field and run then take both conditions (kw_fused_second_order_frames_time_pair / kw_second_order_frames_mix_pair);
+  /// lineRecord refuses while one is set.
+  void setDp0dt(const float* dp0dt) { mCore.setDp0dt(dp0dt); }
+  bool hasDp0dt() const { return mCore.hasDp0dt(); }
   /// every frame's pressure at time t on the domain; dst: Nx Ny F floats on the host or NULL (the crop stays on the device)
   void field(double t, float* dst) { mCore.field(t, dst); }
   /// every time in the given order: the record's row, the aggregates

@@ -310,6 +310,15 @@ static int kwh_propagator_set_p0(const char* who, Handle* s, const float* p0)
 }
 
 template <class Handle>
+static int kwh_propagator_set_dp0dt(const char* who, Handle* s, const float* dp0dt)
+{
+  KWH_TRY
+  if (!s) throw std::invalid_argument(std::string(who) + ": NULL propagator");
+  s->propagator->setDp0dt(dp0dt); // (NULL clears)
+  KWH_CATCH
+}
+
+template <class Handle>
 static int kwh_propagator_field(const char* who, Handle* s, double t, float* dst)
 {
   KWH_TRY
@@ -1090,6 +1099,11 @@ int kwh_second_order_set_p0(kwh_second_order* s, const float* p0)
   return kwh_propagator_set_p0("kwh_second_order_set_p0", s, p0);
 }
 
+int kwh_second_order_set_dp0dt(kwh_second_order* s, const float* dp0dt)
+{
+  return kwh_propagator_set_dp0dt("kwh_second_order_set_dp0dt", s, dp0dt);
+}
+
 int kwh_second_order_field(kwh_second_order* s, double t, float* dst)
 {
   return kwh_propagator_field("kwh_second_order_field", s, t, dst);
@@ -1117,6 +1131,7 @@ int kwh_second_order_get_scalar(kwh_second_order* s, const char* name, double* o
   else if (n == "Ez") *out = static_cast<double>(p.ez);
   else if (n == "t_free") *out = p.tFree;
   else if (n == "runs") *out = static_cast<double>(s->propagator->runs());
+  else if (n == "has_dp0dt") *out = s->propagator->hasDp0dt() ? 1.0 : 0.0;
   else throw std::invalid_argument(std::string("unknown scalar ") + name);
   KWH_CATCH
 }
@@ -1150,6 +1165,11 @@ int kwh_second_order_frames_set_p0(kwh_second_order_frames* s, const float* p0)
   return kwh_propagator_set_p0("kwh_second_order_frames_set_p0", s, p0);
 }
 
+int kwh_second_order_frames_set_dp0dt(kwh_second_order_frames* s, const float* dp0dt)
+{
+  return kwh_propagator_set_dp0dt("kwh_second_order_frames_set_dp0dt", s, dp0dt);
+}
+
 int kwh_second_order_frames_field(kwh_second_order_frames* s, double t, float* dst)
 {
   return kwh_propagator_field("kwh_second_order_frames_field", s, t, dst);
@@ -1177,6 +1197,7 @@ int kwh_second_order_frames_get_scalar(kwh_second_order_frames* s, const char* n
   else if (n == "frames") *out = static_cast<double>(p.frames);
   else if (n == "t_free") *out = p.tFree;
   else if (n == "runs") *out = static_cast<double>(s->propagator->runs());
+  else if (n == "has_dp0dt") *out = s->propagator->hasDp0dt() ? 1.0 : 0.0;
   else if (n == "line_row") *out = static_cast<double>(s->propagator->lineRow());
   else if (n == "line_chunk_times") *out = static_cast<double>(s->propagator->lineChunkTimes());
   else throw std::invalid_argument(std::string("unknown scalar ") + name);

@@ -13,7 +13,11 @@ p0(x, y) that share the medium, the expanded plane, the output times and the sen
 set, `line_record(times)` gives that record for one row of the plane, (F, n_times, Nx), in one call: per time and kx one sum
 over the ky bins and one 1-D inverse over the record itself, no 2-D round trip per time.
 
-Not built: dp0/dt as a second initial condition and time-varying sources, heterogeneous media, Z-slabs, chunks of frames and
+`set_dp0dt(v)` on either gives dp/dt at t = 0 [Pa/s] as a second initial condition (k-Wave's source.dp0dt): per mode
+p^(t) = Hc P0 + Hs V0, so dp0dt = -c0 df/dx with p0 = f(x) launches a one-way wave, and a snapshot (p, dp/dt) continues a
+field.  It is independent of `set_p0`; `None` clears it.
+
+Not built: dp0/dt in `line_record`, time-varying sources, heterogeneous media, Z-slabs, chunks of frames and
 frames over several GPUs, HDF5 files and the command line, graphs, several output times per pass and inverse passes
 restricted to the crop, to the sensor points or to the rows that hold sensors (but for the one row of `line_record`),
 several rows, columns or arbitrary points in `line_record`, particle velocity outputs.
@@ -58,6 +62,7 @@ def _lib() -> C.CDLL:
             fn("create").argtypes = [C.POINTER(cfg), C.POINTER(Options), C.POINTER(C.c_void_p)]
             fn("destroy").argtypes = [C.c_void_p]
             fn("set_p0").argtypes = [C.c_void_p, C.c_void_p]
+            fn("set_dp0dt").argtypes = [C.c_void_p, C.c_void_p]
             fn("field").argtypes = [C.c_void_p, C.c_double, C.c_void_p]
             fn("run").argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_uint64]
             fn("get").argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint64]
@@ -129,7 +134,8 @@ class SecondOrder:
     expanded = (Ex, Ey, Ez) gives the sides instead (expanded = n: the periodic box).  sensor_index: 0-based flat indices
     into the (Nz, Ny, Nx) array, sampled by run(); record: which of "p_raw", "p_max", "p_min", "p_rms", "p_final" run() keeps.
 
-    set_p0(p0), then field(t) -> (Nz, Ny, Nx) or run(times) -> the record (n_times, n_sensor); times in any order."""
+    set_p0(p0), then field(t) -> (Nz, Ny, Nx) or run(times) -> the record (n_times, n_sensor); times in any order.
+    set_dp0dt(v) adds dp/dt at t = 0 (Nz, Ny, Nx) [Pa/s]; None clears it (has_dp0dt)."""
 
     _ENTRY = "kwh_second_order"   # the C entry points' common name (SecondOrderFrames: its own)
 
@@ -209,6 +215,25 @@ class SecondOrder:
         a = np.ascontiguousarray(a)
         _check(self._fn("set_p0")(self._h, a.ctypes.data))
 
+    def _set_dp0dt(self, v, name):
+        if v is None:
+            _check(self._fn("set_dp0dt")(self._h, None))
+            return
+        a = np.asarray(v, dtype=np.float32)
+        if a.shape != self.shape:
+            raise ValueError(f"dp0dt must be {name} = {self.shape}, got {a.shape}")
+        a = np.ascontiguousarray(a)
+        _check(self._fn("set_dp0dt")(self._h, a.ctypes.data))
+
+    def set_dp0dt(self, v):
+        """dp/dt at t = 0 [Pa/s], (Nz, Ny, Nx), as a second initial condition; None clears it.  Independent of set_p0
+        (which stays required, and may be all zeros): either may be called again in any order."""
+        self._set_dp0dt(v, "(Nz, Ny, Nx)")
+
+    @property
+    def has_dp0dt(self) -> bool:
+        return self._scalar("has_dp0dt") != 0.0
+
     def field(self, t: float) -> np.ndarray:
         """the pressure at time t [s] on the domain: float32 (Nz, Ny, Nx)"""
         out = np.empty(self.shape, dtype=np.float32)
@@ -264,7 +289,8 @@ class SecondOrderFrames(SecondOrder):
     sampled in every frame by run() — a row of the plane is a linear array.
 
     set_p0(p0) takes (F, Ny, Nx), or (Ny, Nx) when frames == 1; field(t) -> (F, Ny, Nx); run(times) -> the record
-    (n_times, F, n_sensor), times in any order; p_max() / p_min() / p_rms() / p_final() -> (F, Ny, Nx).
+    (n_times, F, n_sensor), times in any order; p_max() / p_min() / p_rms() / p_final() -> (F, Ny, Nx).  set_dp0dt(v) adds
+    dp/dt at t = 0 of every frame (F, Ny, Nx) [Pa/s]; None clears it.
 
     line_row: a row 0 ... Ny - 1 of the plane (None: none) whose record line_record(times) -> (F, n_times, Nx) gives without
     a 2-D round trip per time — `recon.LineRecon`'s order "ty" with x as the array axis.  It is prepared by set_p0;
@@ -315,6 +341,11 @@ class SecondOrderFrames(SecondOrder):
             raise ValueError(f"p0 must be (F, Ny, Nx) = {self.shape}, got {a.shape}")
         a = np.ascontiguousarray(a)
         _check(self._fn("set_p0")(self._h, a.ctypes.data))
+
+    def set_dp0dt(self, v):
+        """dp/dt at t = 0 of every frame [Pa/s], (F, Ny, Nx), as a second initial condition; None clears it.  Independent
+        of set_p0.  line_record is refused while one is set."""
+        self._set_dp0dt(v, "(F, Ny, Nx)")
 
     def _record_shape(self):
         return (self.n_times, self.frames, self.n_sensor)

@@ -3,7 +3,7 @@
 twin, the stage's z-pass k_zfused_second_order against k_zfused_time at the same length, and the time loop's step on the
 same grid beside them:
 
-    python tools/bench_second_order.py [--grids 256x256x256] [--reps 20] [--warmup 3] [--loop-steps 50]
+    python tools/bench_second_order.py [--grids 256x256x256] [--reps 20] [--warmup 3] [--loop-steps 50] [--dp0dt]
 
 One JSON line per grid (Ex x Ey x Ez).  The forms alternate rep by rep; figures are medians.
 
@@ -17,6 +17,14 @@ One JSON line per grid (Ex x Ey x Ez).  The forms alternate rep by rep; figures 
            H costs.  From the library's per-kernel timing.
   loop     ms per step of the time loop (HostSolver, heterogeneous, nonlinear, absorbing, p0 source: the flagship
            workload of bench.py) on a cube of the grid's x side, wall clock over --loop-steps steps after a warm-up.
+
+--dp0dt: instead of the above, the stage with dp0/dt as a second initial condition on the same context, the forms
+alternating rep by rep, absorbing medium (y = 1.5):
+  single   one kw_fused_second_order_time (as `stage` above)
+  pair     one kw_fused_second_order_time_pair: k_zfused_second_order_pair over both kept spectra, the y-inverse and the
+           storing x-inverse.  The comparison that matters is pair against twice single: what two propagators and an
+           addition cost.
+  pass     k_zfused_second_order_pair and k_zfused_second_order alone, from the library's per-kernel timing
 """
 import argparse
 import ctypes as C
@@ -86,6 +94,68 @@ def loop_ms_per_step(n, steps, warmup):
         return (time.perf_counter() - t0) * 1e3 / steps
     finally:
         sim.close()
+
+
+def dp0dt_case(ex, ey, n3, reps, warmup, frames=False):
+    """single stage, pair stage and the pair pass alone on one context (Ex, Ey, Ez), or with `frames` a frames context
+    (Ex, Ey, F); shared with tools/bench_second_order_frames.py"""
+    rng = np.random.default_rng(ex + ey + n3)
+    shape = (n3, ey, ex)
+    nr = (ex // 2 + 1) * ey * n3
+    entry = "fused_second_order_frames_" if frames else "fused_second_order_"
+    kernel = "k_yfused_second_order" if frames else "k_zfused_second_order"
+    dev = capi.Device()
+    dev.set_constants(constants(ex, ey, n3))
+    if frames:
+        dev.call("fused_set_frames", 1)
+    ok = C.c_int()
+    dev.call("fused_supported", C.byref(ok))
+    if ok.value != 1:
+        raise SystemExit(f"the fused pipeline does not take a context of {ex} x {ey} x {n3}")
+    dev.call("fused_create")
+    ne = C.c_size_t()
+    dev.call(entry + "elems", C.byref(ne))
+    vol, kept_p, kept_v = dev.array(rng.standard_normal(shape).astype(F32)), dev.empty(2 * ne.value), dev.empty(2 * ne.value)
+    dev.call(entry + "forward", vol, kept_p)
+    vol_v = dev.array((rng.standard_normal(shape) * C0 / DX).astype(F32))
+    dev.call(entry + "forward", vol_v, kept_v)
+    op = make_op(True)
+    forms = {"single": lambda: dev.call(entry + "time", kept_p, C.byref(op), vol),
+             "pair": lambda: dev.call(entry + "time_pair", kept_p, kept_v, C.byref(op), vol)}
+    for _ in range(warmup):
+        for fn in forms.values():
+            fn()
+    dev.sync()
+    e0, e1 = dev.event(), dev.event()
+    times = {name: [] for name in forms}
+    for _ in range(reps):
+        for name, fn in forms.items():
+            dev.record(e0)
+            fn()
+            dev.record(e1)
+            times[name].append(dev.elapsed_ms(e0, e1))
+    capi.check(dev.L.kw_profile_enable(dev.ctx, 1))
+    capi.profile_collect(dev.ctx)
+    passes = {name: [] for name in forms}
+    for _ in range(reps):
+        for name, fn in forms.items():
+            fn()
+            passes[name].append(kernel_ms(dev, kernel + ("_pair" if name == "pair" else "")))
+    capi.check(dev.L.kw_profile_enable(dev.ctx, 0))
+    copy = C.c_double()
+    capi.check(dev.L.kw_measure_copy_bandwidth(dev.ctx, C.c_size_t(8 * nr), 20, C.byref(copy)))
+    dev.call("fused_destroy")
+    dev.close()
+    med = lambda v: float(np.median(v))   # noqa: E731
+    rng_of = lambda v: [round(min(v), 4), round(max(v), 4)]   # noqa: E731
+    si, pa, ps, pp = med(times["single"]), med(times["pair"]), med(passes["single"]), med(passes["pair"])
+    return {("batch" if frames else "grid"): ([n3, ey, ex] if frames else [ex, ey, n3]), "dp0dt": True, "reps": reps,
+            "single_stage_ms": round(si, 4), "single_stage_ms_min_max": rng_of(times["single"]),
+            "pair_stage_ms": round(pa, 4), "pair_stage_ms_min_max": rng_of(times["pair"]),
+            "pair_over_twice_single": round(pa / (2.0 * si), 3), "single_pass_ms": round(ps, 4),
+            "pair_pass_ms": round(pp, 4), "pair_pass_ms_min_max": rng_of(passes["pair"]), "pair_pass_over_single_pass": round(pp / ps, 3),
+            "pair_pass_bytes": 24 * nr, "pair_pass_gbs": round(24 * nr / pp / 1e6, 1), "single_pass_gbs": round(16 * nr / ps / 1e6, 1),
+            "copy_gbs": round(copy.value, 1)}
 
 
 def grid_case(ex, ey, ez, reps, warmup, loop_steps):
@@ -163,9 +233,13 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--loop-steps", type=int, default=50)
+    ap.add_argument("--dp0dt", action="store_true", help="time the single stage, the pair stage and the pair pass instead")
     args = ap.parse_args()
     for g in args.grids:
         ex, ey, ez = (int(v) for v in g.split("x"))
+        if args.dp0dt:
+            print(json.dumps(dp0dt_case(ex, ey, ez, args.reps, args.warmup)), flush=True)
+            continue
         print(json.dumps(grid_case(ex, ey, ez, args.reps, args.warmup, args.loop_steps)), flush=True)
 
 

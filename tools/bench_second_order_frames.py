@@ -3,7 +3,7 @@
 kw_fused_second_order_frames_time against its rocFFT twin, and the stage's pass along y k_yfused_second_order beside the 3-D
 propagator's z-pass k_zfused_second_order on a 3-D context of the same number of bins:
 
-    python tools/bench_second_order_frames.py [--batches 64x512x512] [--reps 20] [--warmup 3]
+    python tools/bench_second_order_frames.py [--batches 64x512x512] [--reps 20] [--warmup 3] [--dp0dt]
 
 One JSON line per batch (F x Ey x Ex, the expanded planes).  The forms alternate rep by rep; figures are medians with
 their range.
@@ -15,6 +15,11 @@ their range.
   ypass    k_yfused_second_order alone, absorbing, beside k_zfused_second_order on the 3-D context (Ex, Ey, F) — the same
            bins, the same H, lines of Ey along y against lines of F along z.  From the library's per-kernel timing.
            (F must be a fast-path line length for the 3-D context; otherwise the figure is left out.)
+
+--dp0dt: instead of the above, on one frames context and alternating rep by rep, one kw_fused_second_order_frames_time
+(single), one kw_fused_second_order_frames_time_pair (pair: both kept spectra through k_yfused_second_order_pair, one
+x-inverse) and the two passes alone from the library's per-kernel timing (bench_second_order.dp0dt_case).  The comparison
+that matters is pair against twice single.
 """
 import argparse
 import ctypes as C
@@ -25,7 +30,7 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from bench_second_order import F32, capi, constants, kernel_ms, make_op  # noqa: E402
+from bench_second_order import F32, capi, constants, dp0dt_case, kernel_ms, make_op  # noqa: E402
 
 
 def batch_case(nf, ey, ex, reps, warmup):
@@ -123,9 +128,13 @@ def main():
     ap.add_argument("--batches", nargs="*", default=["64x512x512"])
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--dp0dt", action="store_true", help="time the single stage, the pair stage and the pair pass instead")
     args = ap.parse_args()
     for b in args.batches:
         nf, ey, ex = (int(v) for v in b.split("x"))
+        if args.dp0dt:
+            print(json.dumps(dp0dt_case(ex, ey, nf, args.reps, args.warmup, frames=True)), flush=True)
+            continue
         print(json.dumps(batch_case(nf, ey, ex, args.reps, args.warmup)), flush=True)
 
 

@@ -34,6 +34,8 @@ def main():
                                                                           os.path.join(CSRC, "kw_angular.hip"),
                                                                           os.path.join(CSRC, "kw_angular_time.hip"),
                                                                           os.path.join(CSRC, "kw_second_order.hip"),
+                                                                          # (the same two passes with dp0/dt)
+                                                                          os.path.join(CSRC, "kw_second_order_pair.hip"),
                                                                           # (no kernel of the pipeline: k_line_record<FT>
                                                                           # and k_line_prepare, the same at every length)
                                                                           os.path.join(CSRC, "kw_second_order_line.hip"),
