@@ -1261,11 +1261,39 @@ template<int L, bool TAIL = false> __global__ __launch_bounds__(GeoX<L>::THREADS
 // =====================================================================================================================
 enum Epi { EPI_STORE = 0, EPI_VELOCITY = 1, EPI_INITVEL = 2, EPI_DENSITY = 3, EPI_PSUM = 4, EPI_PSUM1 = 5 };
 
+// Line lengths whose density and pressure-sum epilogues let values wait in the real tile in LDS instead of in registers
+// (see k_xinv: LAST_IN_LDS, FW0_IN_LDS, FRESH_XT): the pressure sum's chained row, the density epilogue's last inverse,
+// the pressure sum's last inverse.  On where it buys an occupancy step at no scratch AND measures faster (DESIGN.md
+// §3b, §6: 256 so far; the register table of the other lengths is there); a length left off compiles to the kernels it
+// had before.  (tuning builds: -DKW_TUNE_XLDS=<bits> overrides the three tables for every length: 1, 2, 4 in that
+// order; -DKW_TUNE_XWAVES=<n> the waves per SIMD asked for the two epilogues)
+#ifdef KW_TUNE_XLDS
+constexpr bool psum_row_in_lds(int) { return (KW_TUNE_XLDS & 1) != 0; }
+constexpr bool last_inverse_in_lds(int) { return (KW_TUNE_XLDS & 2) != 0; }
+constexpr bool psum_last_in_lds(int) { return (KW_TUNE_XLDS & 4) != 0; }
+#else
+constexpr bool psum_row_in_lds(int L) { return L == 256; }
+constexpr bool last_inverse_in_lds(int L) { return L == 256; }
+constexpr bool psum_last_in_lds(int) { return false; }
+#endif
+// waves per SIMD asked of the allocator.  256 points: the LDS forms of the two epilogues fit the 128 registers of four
+// waves with no scratch, but the allocator only aims for them when asked; the register form of the density epilogue sits
+// two registers above the three-wave step
+constexpr int xinv_waves(int L, int EPI)
+{
+#ifdef KW_TUNE_XWAVES
+  if (EPI == EPI_DENSITY || EPI == EPI_PSUM) return KW_TUNE_XWAVES;
+#endif
+  if (L == 256 && EPI == EPI_DENSITY) return last_inverse_in_lds(L) ? 4 : 3;
+  if (L == 256 && EPI == EPI_PSUM && psum_row_in_lds(L)) return 4;
+  return big_line_waves(L);
+}
+
 
 // standalone inverse of one array for this block's 32 rows; the thread of role sb = XRole<G, R1> ends with
 // x[sb.f + R1*k2] of rows (2 sb.c, 2 sb.c + 1)
 // PLANE: the rows come from the block's plane buffer in LDS ([row][L / 2 + 1], `src`), where the y-inverse left them
-template<int L, int NGRP = 1, bool TAIL = false, int NLX = nl_x(L), bool PLANE = false>
+template<int L, int NGRP = 1, bool TAIL = false, int NLX = nl_x(L), bool PLANE = false, bool FRESH = false>
 __device__ __forceinline__ void xinv_lines(const float2* __restrict__ src, uint32_t P, float2* lds,
                                            const float2* tw, float2 (&w)[Fac<L>::R2], uint32_t tile,
                                            const float2* __restrict__ mulx = nullptr, uint32_t nrows = 0,
@@ -1278,6 +1306,9 @@ __device__ __forceinline__ void xinv_lines(const float2* __restrict__ src, uint3
   // latency once per iteration); the last, partial iteration re-reads the final element instead of being predicated
   constexpr int NE = (G::NL * HALF + G::THREADS - 1) / G::THREADS;
   constexpr int NG = (NE + NGRP - 1) / NGRP; // iterations per group (NGRP > 1: fewer loads in flight, fewer registers)
+  // FRESH: the row offsets are worked out again for every array of a multi-array kernel instead of waiting in registers
+  int tx = static_cast<int>(threadIdx.x);
+  if (FRESH) asm volatile("" : "+v"(tx));
 #pragma unroll
   for (int g0 = 0; g0 < NE; g0 += NG)
   {
@@ -1285,7 +1316,7 @@ __device__ __forceinline__ void xinv_lines(const float2* __restrict__ src, uint3
 #pragma unroll
     for (int it = 0; it < NG; it++)
     {
-      const int e  = min(static_cast<int>(threadIdx.x) + (g0 + it) * G::THREADS, G::NL * HALF - 1);
+      const int e  = min(tx + (g0 + it) * G::THREADS, G::NL * HALF - 1);
       const int cc = e / HALF;
       const int k  = e - cc * HALF;
       const uint32_t r = tile_row0 + 2 * cc;
@@ -1457,11 +1488,11 @@ constexpr bool plane_len(int L) { return L == 32 || L == 64; }
 // The inverse leaves each thread with x = f + R1*k2 of two rows — a 64-B-segment pattern.  The results are restaged
 // through LDS as a plain real tile [32 rows][L] and re-read as float4 in a row-contiguous mapping, so that every
 // epilogue access to the state / medium arrays is a 16-B-per-lane coalesced access.
-// (the 256-point density epilogue sits two registers above the 3-waves-per-SIMD step: ask the allocator for that step)
+// (waves per SIMD asked of the allocator: xinv_waves)
 // TERMS: compile-time value of a.terms for the density epilogue (one specialised kernel per pressure-term mode)
 // PLANE: the tile is a whole z-plane (L / 2 line pairs) and the kernel does the plane's y transforms too — see above.
 template<int L, int EPI, bool CHAIN, int TERMS = 0, bool TAIL = false, bool PLANE = false>
-__global__ __launch_bounds__((Geo<L, PLANE ? L / 2 : nl_x(L)>::THREADS), (EPI == EPI_DENSITY && L == 256) ? 3 : big_line_waves(L)) void k_xinv(XinvArgs a)
+__global__ __launch_bounds__((Geo<L, PLANE ? L / 2 : nl_x(L)>::THREADS), xinv_waves(L, EPI)) void k_xinv(XinvArgs a)
 {
   constexpr int terms = TERMS;
   constexpr int NLX = PLANE ? L / 2 : nl_x(L); // (the registers a thread needs follow from L / TPL, not from the lines per block)
@@ -1475,8 +1506,11 @@ __global__ __launch_bounds__((Geo<L, PLANE ? L / 2 : nl_x(L)>::THREADS), (EPI ==
   // L / 2 not a multiple of the threads per line (25 x 28, 27 x 28, 25 x 32, 27 x 32): the tile does not divide by the block;
   // the surplus lanes of the last round read the tile's last float4 (XE) and store nothing (XE_OK)
   constexpr bool QPART = (TOT4 % G::THREADS) != 0;
-#define XE(q) (QPART ? min(static_cast<int>(threadIdx.x) + (q) * G::THREADS, TOT4 - 1) : static_cast<int>(threadIdx.x) + (q) * G::THREADS)
-#define XE_OK(q) (!QPART || static_cast<int>(threadIdx.x) + (q) * G::THREADS < TOT4)
+#define XE(q) (QPART ? min(xt + (q) * G::THREADS, TOT4 - 1) : xt + (q) * G::THREADS)
+#define XE_OK(q) (!QPART || xt + (q) * G::THREADS < TOT4)
+  // xt: the thread's index in the block as the float4 mapping sees it.  FRESH_XT: every read-out loop and every operand
+  // group derives its cells from a fresh copy, so that no row index or LDS address waits in a register across a transform
+#define XT_FRESH() do { xt = static_cast<int>(threadIdx.x); if (FRESH_XT) asm volatile("" : "+v"(xt)); } while (0)
   __shared__ float2 lds[G::LDSX];
   __shared__ float2 twl[G::TWN];
   __shared__ float2 Yp[PLANE ? L * (L / 2 + 1) : 1]; // PLANE: the plane's half-spectrum between its y and x transforms
@@ -1486,11 +1520,18 @@ __global__ __launch_bounds__((Geo<L, PLANE ? L / 2 : nl_x(L)>::THREADS), (EPI ==
   const XRole<G, R1> sb;
   const uint32_t comp = (NA == 1) ? blockIdx.y + a.comp0 : 0; // component / array index for single-array epilogues
   const uint32_t tile = blockIdx.x + a.tile0;
-  float4 res[NA][NQ];
+  // the last inverse (the density epilogue's duz, the pressure sum's eta term) stays in the real tile: each float4 is
+  // read where the epilogue uses it, just before the same thread overwrites the cell with a chained row (no read-out
+  // loop and no barrier after it; a surplus lane of a QPART tile may read a cell its owner has rewritten: it stores nothing)
+  constexpr bool LAST_IN_LDS = !PLANE && ((EPI == EPI_DENSITY && last_inverse_in_lds(L)) || (EPI == EPI_PSUM && psum_last_in_lds(L)));
+  float4 res[LAST_IN_LDS ? NA - 1 : NA][NQ];
+  constexpr bool FRESH_XT = LAST_IN_LDS || (EPI == EPI_PSUM && !PLANE && psum_row_in_lds(L));
+  int xt = static_cast<int>(threadIdx.x);
   constexpr int NF = CHAIN ? ((EPI == EPI_DENSITY) ? 2 : 1) : 1; // chained forward transforms
-  // rows to chain: kept in registers, except the first of the density epilogue's two, which goes straight into the
-  // real tile in LDS (free once the last inverse has been read out) — 32 registers less at the kernel's widest point
-  constexpr bool FW0_IN_LDS = CHAIN && (EPI == EPI_DENSITY);
+  // rows to chain: kept in registers, except the first of the density epilogue's two (and, where psum_row_in_lds, the
+  // pressure sum's one), which goes straight into the real tile in LDS (free once the last inverse has been read out)
+  // — 32 registers less at the kernel's widest point
+  constexpr bool FW0_IN_LDS = CHAIN && ((EPI == EPI_DENSITY) || (EPI == EPI_PSUM && !PLANE && psum_row_in_lds(L)));
   float4 fw[FW0_IN_LDS ? 1 : NF][NQ];
 #pragma unroll
   for (int i = 0; i < NA; i++)
@@ -1505,7 +1546,7 @@ __global__ __launch_bounds__((Geo<L, PLANE ? L / 2 : nl_x(L)>::THREADS), (EPI ==
       xinv_lines<L, 1, false, NLX, true>(Yp, a.P, lds, twl, w, tile, (NA == 1) ? a.mulx[comp] : nullptr);
     }
     else
-    xinv_lines<L, (EPI == EPI_DENSITY) ? 2 : 1, TAIL, NLX>(a.in[(NA == 1) ? comp : i], a.P, lds, twl, w, tile,
+    xinv_lines<L, (EPI == EPI_DENSITY) ? 2 : 1, TAIL, NLX, false, LAST_IN_LDS>(a.in[(NA == 1) ? comp : i], a.P, lds, twl, w, tile,
                                                             (NA == 1) ? a.mulx[comp] : nullptr, a.nrows, a.side_off); // ends with a barrier
     if (sb.on)
     {
@@ -1517,13 +1558,15 @@ __global__ __launch_bounds__((Geo<L, PLANE ? L / 2 : nl_x(L)>::THREADS), (EPI ==
       }
     }
     lds_barrier();
+    if (LAST_IN_LDS && i == NA - 1) break;
+    XT_FRESH();
 #pragma unroll
     for (int q = 0; q < NQ; q++)
     {
       const int e   = XE(q);
       const int row = e / Q4;
       const int x4  = e - row * Q4;
-      res[i][q]     = *reinterpret_cast<const float4*>(&ldsr[row * RP + 4 * x4]);
+      res[LAST_IN_LDS ? min(i, NA - 2) : i][q] = *reinterpret_cast<const float4*>(&ldsr[row * RP + 4 * x4]);
     }
     lds_barrier();
   }
@@ -1539,7 +1582,8 @@ __global__ __launch_bounds__((Geo<L, PLANE ? L / 2 : nl_x(L)>::THREADS), (EPI ==
   // power-of-two rows: x is the same for every float4 of a thread (one PML-x load per thread); the 3 * 2^m rows whose
   // float4 count does not divide the block take x (and the PML-x operand) per float4
   constexpr bool XFIX = (G::THREADS % Q4 == 0);
-  const uint32_t xfix = 4u * (threadIdx.x % Q4);
+  XT_FRESH();
+  const uint32_t xfix = 4u * (static_cast<uint32_t>(xt) % Q4);
   float4 pmlx4 = make_float4(1.f, 1.f, 1.f, 1.f);
   if (XFIX && ((EPI == EPI_VELOCITY && comp == 0) || EPI == EPI_DENSITY)) pmlx4 = ld4(a.m1[0] + xfix);
   const bool hetRho0 = (EPI == EPI_DENSITY) && (a.m0[0] != nullptr);
@@ -1550,6 +1594,7 @@ __global__ __launch_bounds__((Geo<L, PLANE ? L / 2 : nl_x(L)>::THREADS), (EPI ==
   for (int q0 = 0; q0 < NQ; q0 += GQ)
   {
     float4 op0[GQ], op1[GQ], op2[GQ], op3[GQ], op4[GQ], op5[GQ], opx[GQ];
+    XT_FRESH();
     float  sy[GQ], sz[GQ];
 #pragma unroll
     for (int g = 0; g < GQ; g++)
@@ -1662,7 +1707,8 @@ __global__ __launch_bounds__((Geo<L, PLANE ? L / 2 : nl_x(L)>::THREADS), (EPI ==
       }
       else if (EPI == EPI_DENSITY)
       { // :1368-1392 (nonlinear) / :1480-1496 (linear); du already carries fftDivider (applied in k-space, :1220)
-        const float4 dux = res[0][q], duy = res[1][q], duz = res[2][q];
+        const float4 dux = res[0][q], duy = res[1][q];
+        const float4 duz = LAST_IN_LDS ? *reinterpret_cast<const float4*>(&ldsr[(e / Q4) * RP + x]) : res[LAST_IN_LDS ? 0 : 2][q];
         const float  py = sy[g], pz = sz[g];
         const float4 rx = op0[g], ry = op1[g], rz = op2[g];
         const float4 r04 = hetRho0 ? op3[g] : make_float4(k.rho0, k.rho0, k.rho0, k.rho0);
@@ -1799,7 +1845,8 @@ __global__ __launch_bounds__((Geo<L, PLANE ? L / 2 : nl_x(L)>::THREADS), (EPI ==
       }
       else if (EPI == EPI_PSUM)
       { // :1877 / :1978: p = c2*(first + (fftDivider*((tauTerm*tau) - (etaTerm*eta))))
-        const float4 tt = res[0][q], et = res[1][q];
+        const float4 tt = res[0][q];
+        const float4 et = LAST_IN_LDS ? *reinterpret_cast<const float4*>(&ldsr[(e / Q4) * RP + x]) : res[LAST_IN_LDS ? 0 : 1][q];
         const float4 fi = op0[g];
         const float4 c24  = (a.m0[1] != nullptr) ? op1[g] : make_float4(k.c2, k.c2, k.c2, k.c2);
         const float4 tau4 = (a.m1[0] != nullptr) ? op2[g] : make_float4(k.absorb_tau, k.absorb_tau, k.absorb_tau, k.absorb_tau);
@@ -1809,7 +1856,8 @@ __global__ __launch_bounds__((Geo<L, PLANE ? L / 2 : nl_x(L)>::THREADS), (EPI ==
         for (int t = 0; t < 4; t++)
           f4put(o, t, f4get(c24, t) * (f4get(fi, t) + (k.fft_divider * ((f4get(tt, t) * f4get(tau4, t)) - (f4get(et, t) * f4get(eta4, t))))));
         if (row_ok) st4(a.out[0] + i, o);
-        if constexpr (CHAIN) fw[0][q] = o;
+        if constexpr (FW0_IN_LDS) { if (e_ok) *reinterpret_cast<float4*>(&ldsr[(e / Q4) * RP + x]) = o; }
+        else if constexpr (CHAIN) fw[0][q] = o;
       }
       else if (EPI == EPI_PSUM1)
       { // the power law's sum with one term (kw_one_term_pressure, kw_internal.h): the arithmetic of kw_sum_pressure_terms_one_*
@@ -1839,6 +1887,7 @@ __global__ __launch_bounds__((Geo<L, PLANE ? L / 2 : nl_x(L)>::THREADS), (EPI ==
       if (EPI == EPI_DENSITY && jf == 1 && terms >= 3) break; // lossless / Stokes: only p is chained; one-term power law: one term
       if (!(FW0_IN_LDS && jf == 0))
       {
+        XT_FRESH();
 #pragma unroll
         for (int q = 0; q < NQ; q++)
         {
@@ -1888,6 +1937,7 @@ template<int L, bool TAIL = false> __global__ __launch_bounds__(GeoX<L>::THREADS
   const XRole<G, R2> sa;
   const XRole<G, R1> sb;
   const uint32_t tile_row0 = (blockIdx.x + a.tile0) * G::NL * 2;
+  const int xt = static_cast<int>(threadIdx.x); // (XE / XE_OK)
   float2 v[R1];
   if (sa.on)
   {
