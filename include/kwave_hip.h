@@ -1117,6 +1117,39 @@ KW_API kw_status kw_second_order_line_prepare(kw_ctx* ctx, float* q, const float
 KW_API kw_status kw_second_order_line_record(kw_ctx* ctx, float* g, const float* q, const kw_second_order_op* op,
                                              const double* times, uint32_t n_times);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Plane-sensor record of the 3-D propagator: what the plane z = r dz of the volume records at many output times, with no
+ * inverse along z and no 3-D round trip per time (csrc/kw_second_order_plane.hip, host/SecondOrder.cpp, DESIGN.md
+ * "Plane-sensor record of the propagator").  Any context with constants (nx, ny, nz) = (Ex, Ey, Ez), any sizes, odd ones
+ * included; the fused pipeline plays no part.
+ *     p(x, y, z_r; t) = irfft2_xy[ G(kx, ky; t) ],  kx = 0 ... Ex/2, ky = 0 ... Ey - 1
+ *     G(kx, ky; t)    = sum over m = 0 ... Ez/2 of H(kx, ky, m; t) Q(kx, ky, m)
+ *     Q(kx, ky, m)    = q(kx, ky, m) + q(kx, ky, Ez - m);  bins 0 and (Ez even) Ez/2 pair with themselves: q(kx, ky, m) alone
+ *     q(kx, ky, kz)   = rfftn(p0 embedded)(kx, ky, kz) exp(+2 pi i kz r / Ez) / (Ex Ey Ez)
+ * H is the H of "Exact k-space propagator", which depends on kz through min(kz, Ez - kz) and on ky through min(ky, Ey - ky).
+ *
+ * kw_second_order_plane_elems: complex values of Q: Ey (Ex/2 + 1) (Ez/2 + 1).
+ * kw_second_order_plane_prepare: q [Ey][Ex/2 + 1][Ez/2 + 1] (m fastest) <- the natural [Ez][Ey][Ex/2 + 1] spectrum of
+ *   kw_fft_r2c_3d, which is read only.  The phase of bin kz: the integer (kz r) mod Ez exactly, angle = 2 pi (that / Ez) and
+ *   its cosine and sine in float64, each rounded to float32 once; q = ((X * phase) * divider) in float32 without
+ *   contraction, divider = float(1 / (Ex Ey Ez)); the fold adds the two terms.  plane < Ez; q != spec; Ey <= 65535 and
+ *   (Ez/2 + 1) / 32 <= 65535 (block indices).
+ * kw_second_order_plane_record: g [n_times][Ey][Ex/2 + 1] (float2: the half-spectrum layout of kw_fft_c2r_frames on a context
+ *   (Ex, Ey, n_times)) <- Q, op (op->t is not looked at) and the DEVICE array times [n_times] of float64 seconds, each >= 0
+ *   and finite (the caller checks them; the kernel reads no other memory by them), in any order.  A block of k_plane_record
+ *   owns 4 consecutive kx columns, the rows ky and Ey - ky (0 and, Ey even, Ey/2 stand alone) and 256 times; per bin the
+ *   expressions of kw_second_order_line_record with kr2 = kx^2 + ky^2 as the z-pass forms it, one H for both rows.
+ *   An accumulator takes its bins in ascending m, one fmaf(H, Q, acc) each, from zero: the bits of G(kx, ky; t) do not depend
+ *   on the tile, on the other times of the call or on n_times.  No atomics; nothing of size Ex Ey Ez n_times exists.
+ *   1 <= n_times <= 65535 * 256; g != q.
+ * The inverse over the record: kw_fft_c2r_frames on a context with constants (Ex, Ey, n_times), then kw_plane_recon_crop of
+ * (Ex, Ey) to (Nx, Ny).
+ * ---------------------------------------------------------------------------------------------------------------- */
+KW_API kw_status kw_second_order_plane_elems(kw_ctx* ctx, size_t* out_elems);
+KW_API kw_status kw_second_order_plane_prepare(kw_ctx* ctx, float* q, const float* spec, uint32_t plane);
+KW_API kw_status kw_second_order_plane_record(kw_ctx* ctx, float* g, const float* q, const kw_second_order_op* op,
+                                              const double* times, uint32_t n_times);
+
 #ifdef __cplusplus
 }
 #endif

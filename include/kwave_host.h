@@ -495,7 +495,7 @@ KWH_API void*    kwh_line_recon_context(kwh_line_recon* s);
  *   the propagator then launches what one without it launches.  The second kept spectrum is allocated at the first call.
  *   The scalar "has_dp0dt" reports 0 / 1.
  * Not built: time-varying sources,
- * heterogeneous media, Z-slabs, HDF5 files and the command line, graphs, several output times per z-pass, inverse passes restricted to the crop or to the sensor points, particle velocity outputs.
+ * heterogeneous media, Z-slabs, HDF5 files and the command line, graphs, several output times per z-pass, inverse passes restricted to the crop or to the sensor points (but for one plane z = const: the plane-sensor record below), particle velocity outputs.
  * ---------------------------------------------------------------------------------------------------------------- */
 #define KWH_SECOND_ORDER_P_MAX   1
 #define KWH_SECOND_ORDER_P_MIN   2
@@ -531,10 +531,36 @@ KWH_API int      kwh_second_order_field(kwh_second_order* s, double t, float* ds
 KWH_API int      kwh_second_order_run(kwh_second_order* s, const double* times, uint64_t n_times);
 /* "p_raw" [n_times][n_sensor], "p_max", "p_min", "p_rms", "p_final" of the last run, "p" (the last field); n checked */
 KWH_API int      kwh_second_order_get(kwh_second_order* s, const char* name, float* dst, uint64_t n);
-/* "fused_pipeline", "Ex", "Ey", "Ez", "t_free", "runs", "has_dp0dt" */
+/* "fused_pipeline", "Ex", "Ey", "Ez", "t_free", "runs", "has_dp0dt", "plane", "plane_chunk_times" */
 KWH_API int      kwh_second_order_get_scalar(kwh_second_order* s, const char* name, double* out);
 /* the underlying kw_ctx* (include/kwave_hip.h) */
 KWH_API void*    kwh_second_order_context(kwh_second_order* s);
+
+/* The plane-sensor record: the pressure on ONE plane z = plane dz of the domain at many output times — what a planar sensor
+ * records, the input of kwh_plane_recon when times = n dt — without the inverse along z and without a 3-D round trip per
+ * output time (kwave_hip.h "Plane-sensor record of the 3-D propagator"): per output time and (kx, ky) one sum over the
+ * folded kz bins, then one batched 2-D inverse over the record itself.
+ *   set_plane: 0 <= plane < Nz, in effect from the next set_p0 on; -1 switches the record off and frees its arrays.
+ *     Refused as "plane" otherwise.
+ *   set_plane_chunk_times: how many output times one pass takes (it bounds G [times][Ey][Ex/2 + 1]); 0: the default, as many
+ *     as fit 256 MiB, one at the least.  Refused as "plane_chunk_times" when Ex Ey times reaches 2^32.  The scalars "plane"
+ *     and "plane_chunk_times" report what is in effect.
+ *   plane_record: dst [n_times][Ny][Nx] floats on the host, x fastest, or NULL (the passes run, nothing is copied); times in
+ *     any order, each >= 0 and finite; t = 0 gives the plane of p0.  Refused: "plane_record: no plane set", "plane_record: no
+ *     p0 since the plane was set", n_times (0), t, and while a dp0dt is set (the message names dp0dt and points to
+ *     run(times); the record takes p0 alone).  field, run and plane_record may be interleaved: the record touches neither
+ *     "p" nor the aggregates and the record of run.  A value's bits do not depend on the other times of the call or on the
+ *     passes.  On the fast path set_p0 with a plane set runs one 3-D rocFFT of the embedded volume beside the fused forward
+ *     and holds its spectrum (8 (Ex/2 + 1) Ey Ez bytes) until Q is formed.
+ *   plane_plan: the checks of plane, chunk_times and n_times without a device; out: the times of one pass, the passes of
+ *     n_times, the complex values of Q.
+ * Not built: dp0/dt in the record, planes normal to x or y, several planes per call, equally spaced times by a recurrence
+ * instead of one H per time, the 2-D inverse on the fused kernels, Z-slabs, HDF5 files and the command line. */
+KWH_API int      kwh_second_order_plane_plan(const kwh_second_order_config* config, const kwh_options* options, int64_t plane,
+                                             uint64_t chunk_times, uint64_t n_times, uint64_t out[3]);
+KWH_API int      kwh_second_order_set_plane(kwh_second_order* s, int64_t plane);
+KWH_API int      kwh_second_order_set_plane_chunk_times(kwh_second_order* s, uint64_t times);
+KWH_API int      kwh_second_order_plane_record(kwh_second_order* s, const double* times, uint64_t n_times, float* dst);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Exact k-space propagator on frames: the batched 2-D form of the propagator above — F independent initial pressures
@@ -612,8 +638,8 @@ KWH_API void*    kwh_second_order_frames_context(kwh_second_order_frames* s);
  *     or on the passes.
  *   line_plan: the checks of row, chunk_times and n_times without a device; out: the times of one pass, the passes of
  *     n_times, the complex values of Q.
- * Not built: several rows, columns, arbitrary sensor points, the plane-sensor record of the 3-D propagator, the order "yt",
- * frames over several GPUs. */
+ * Not built: several rows, columns, arbitrary sensor points, the order "yt", frames over several GPUs.  (The plane-sensor
+ * record of the 3-D propagator: kwh_second_order_plane_record above.) */
 KWH_API int      kwh_second_order_frames_line_plan(const kwh_second_order_frames_config* config, const kwh_options* options,
                                                    int64_t row, uint64_t chunk_times, uint64_t n_times, uint64_t out[3]);
 KWH_API int      kwh_second_order_frames_set_line_row(kwh_second_order_frames* s, int64_t row);

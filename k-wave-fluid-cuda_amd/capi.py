@@ -223,6 +223,9 @@ _SIG: Dict[str, list] = {
     "kw_second_order_line_elems": [_P, C.POINTER(C.c_size_t)],
     "kw_second_order_line_prepare": [_P, _P, _P, C.c_uint32],
     "kw_second_order_line_record": [_P, _P, _P, _P, _P, C.c_uint32],
+    "kw_second_order_plane_elems": [_P, C.POINTER(C.c_size_t)],
+    "kw_second_order_plane_prepare": [_P, _P, _P, C.c_uint32],
+    "kw_second_order_plane_record": [_P, _P, _P, _P, _P, C.c_uint32],
     "kw_fused_plane_recon": [_P, _P, _P, _P],
     "kw_plane_recon_mix": [_P, _P, _P, _P, C.c_float],
     "kw_plane_recon_embed": [_P, _P, _P] + [C.c_uint32] * 6,

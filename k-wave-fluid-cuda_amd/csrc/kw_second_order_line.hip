@@ -26,54 +26,6 @@ constexpr int kLineTimes = 256; // threads of a record block: one output time ea
 constexpr int kLineChunk = 64;  // folded bins per LDS slab
 constexpr int kLineTile  = 32;  // the transposition's tile
 
-// the factors of H that do not depend on time (second_h's float64 expressions in its order, up to the products with ct)
-struct LineBin
-{
-  double   kr;   // |k| r   (lossless: |k|)
-  double   kg;   // |k| g
-  float    q;    // g / r
-  uint32_t zero; // |k| = 0: H = 1
-};
-
-// bin m (folded: m <= Ey/2) of the column with kr2 = (kx*kx); g.dkz = 2 pi / (Ey dy) as in every frames pass
-__device__ __forceinline__ LineBin line_bin(const SecondH& g, double kr2, uint32_t m)
-{
-#pragma clang fp contract(off)
-  const double ky = g.dkz * static_cast<double>(m);
-  const double k2 = kr2 + (ky * ky);
-  LineBin b{ 0.0, 0.0, 0.f, 0u };
-  if (k2 == 0.0) { b.zero = 1u; return b; }
-  const double k = sqrt(k2);
-  if (g.absorbing == 0) { b.kr = k; return b; }
-  const uint32_t pw = g.power;
-  const double   s  = pw == kPowStokes ? k : (pw == kPowHalf ? sqrt(k) : pow(k, g.ym1));
-  const double   gg = g.ac * s;
-  const double   B  = (1.0 - (g.twoT * gg)) - (gg * gg);
-  const double   r  = sqrt(B);
-  b.kr = k * r;
-  b.kg = k * gg;
-  b.q  = static_cast<float>(gg / r);
-  return b;
-}
-
-// H of one bin at ct = c0 t: second_h from the phase word on, without the divider (Q carries it)
-__device__ __forceinline__ float line_h(double kr, double kg, float q, uint32_t zero, double ct, bool absorbing)
-{
-#pragma clang fp contract(off)
-  const uint32_t word = kw_phase_word((kr * ct) / kTwoPi);
-  const float    ang  = static_cast<float>(static_cast<int32_t>(word)) * 1.4629180792671596e-9f;
-  float h;
-  if (!absorbing) h = cosf(ang);
-  else
-  {
-    float sn, cs;
-    sincosf(ang, &sn, &cs);
-    const float E = exp2f(-static_cast<float>((kg * ct) * kLog2e));
-    h = E * (cs + (q * sn));
-  }
-  return zero != 0u ? 1.0f : h;
-}
-
 struct LineArgs
 {
   const float2* q;      // [nxc][mf][frames]
@@ -138,14 +90,6 @@ struct PrepareArgs
   uint32_t      nxc, ey, mf, frames, row;
   float         divider;
 };
-
-// exp(+2 pi i m r / Ey): the exact integer m r mod Ey, the angle and its cosine and sine in float64, rounded once
-__device__ __forceinline__ float2 row_phase(uint32_t m, uint32_t row, uint32_t ey)
-{
-  const uint32_t e   = static_cast<uint32_t>((static_cast<uint64_t>(m) * row) % ey);
-  const double   ang = kTwoPi * (static_cast<double>(e) / static_cast<double>(ey));
-  return make_float2(static_cast<float>(cos(ang)), static_cast<float>(sin(ang)));
-}
 
 // block (32, 8); grid (kx tiles, frame tiles, mf): the bins (kx0 ... kx0 + 31, m) of the frames f0 ... f0 + 31
 __global__ __launch_bounds__(kLineTile * 8) void k_line_prepare(PrepareArgs a)

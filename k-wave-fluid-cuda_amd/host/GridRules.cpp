@@ -97,6 +97,25 @@ void SecondOrderRules::checkTime(double t)
   if (!(t >= 0.0) || !std::isfinite(t)) refuse("t", std::to_string(t) + " is not a time >= 0");
 }
 
+size_t SecondOrderRules::passTimes(uint64_t given, size_t bytesPerTime, size_t pointsPerTime, const char* name, const std::string& of)
+{
+  if (given == 0) return std::min(kRecordTimesMost, std::max<size_t>(1, kRecordBudgetBytes / bytesPerTime));
+  const bool rows = given <= (uint64_t(1) << 32) / pointsPerTime && pointsPerTime * given < (uint64_t(1) << 32);
+  if (!rows || given > kRecordTimesMost)
+    refuse(name, std::to_string(given) + " times of " + of + " are too many for one pass (2^32 points, " +
+                   std::to_string(kRecordTimesMost) + " times)");
+  return static_cast<size_t>(given);
+}
+
+std::vector<SecondOrderRules::TimeChunk> SecondOrderRules::timeChunks(size_t nTimes, size_t chunkTimes, const char* name)
+{
+  if (nTimes == 0) refuse("n_times", "0 is not a number of output times");
+  if (chunkTimes == 0) refuse(name, "0 is not a number of output times");
+  std::vector<TimeChunk> out;
+  for (size_t first = 0; first < nTimes; first += chunkTimes) out.push_back({ first, std::min(chunkTimes, nTimes - first) });
+  return out;
+}
+
 void SecondOrderRules::checkMedium() const
 {
   checkPositive(c0, "c0", "sound speed");

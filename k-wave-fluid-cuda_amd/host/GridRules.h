@@ -56,6 +56,17 @@ struct SecondOrderRules
   /// throws unless t is finite and >= 0
   static void checkTime(double t);
 
+  // ---- the records of many output times (SecondOrderFrames::lineRecord, SecondOrder::planeRecord) run in passes ----
+  static constexpr size_t kRecordBudgetBytes = size_t(256) << 20;    ///< of G in the default pass
+  static constexpr size_t kRecordTimesMost   = size_t(65535) * 256;  ///< the record kernels' time tiles are a block index
+  struct TimeChunk { size_t first, count; };                         ///< output times first ... first + count - 1
+  /// the times of one pass.  given == 0: as many as keep G (bytesPerTime each) within kRecordBudgetBytes, one at the least;
+  /// otherwise `given`, refused as `name` ("<given> times of <of> are too many ...") when the pass's rows (pointsPerTime
+  /// each, indexed in 32 bits as every batch here) reach 2^32 points or it is above kRecordTimesMost
+  static size_t passTimes(uint64_t given, size_t bytesPerTime, size_t pointsPerTime, const char* name, const std::string& of);
+  /// nTimes in passes of at most chunkTimes, in order; refuses "n_times" for 0 and `name` for a chunk of 0
+  static std::vector<TimeChunk> timeChunks(size_t nTimes, size_t chunkTimes, const char* name);
+
   DeviceOptions options;
   double c0 = 0;                  ///< [m/s]
   double alphaCoeff = 0;          ///< [dB / (MHz^y cm)]; 0: lossless

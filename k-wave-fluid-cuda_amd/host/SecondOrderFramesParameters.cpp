@@ -64,21 +64,12 @@ void SecondOrderFramesParameters::checkLineRow(int64_t row) const
 
 size_t SecondOrderFramesParameters::lineChunkTimes(uint64_t given) const
 {
-  const size_t perTime = lineSpectrumElems(1) * 2 * sizeof(float); // G of one output time
-  if (given == 0) return std::min(kLineTimesMost, std::max<size_t>(1, kLineBudgetBytes / perTime));
-  // the rows of one pass [F given][Ex] are indexed in 32 bits, as every batch here
-  const bool rows = given <= (uint64_t(1) << 32) / (ex * frames) && ex * frames * given < (uint64_t(1) << 32);
-  if (!rows || given > kLineTimesMost)
-    refuse("line_chunk_times", std::to_string(given) + " times of " + std::to_string(frames) + " rows of " + std::to_string(ex) +
-                                 " points are too many for one pass (2^32 points, " + std::to_string(kLineTimesMost) + " times)");
-  return static_cast<size_t>(given);
+  // G of one output time; the rows of one pass [F given][Ex]
+  return passTimes(given, lineSpectrumElems(1) * 2 * sizeof(float), ex * frames, "line_chunk_times",
+                   std::to_string(frames) + " rows of " + std::to_string(ex) + " points");
 }
 
 std::vector<SecondOrderFramesParameters::LineChunk> SecondOrderFramesParameters::lineChunks(size_t nTimes, size_t chunkTimes)
 {
-  if (nTimes == 0) refuse("n_times", "0 is not a number of output times");
-  if (chunkTimes == 0) refuse("line_chunk_times", "0 is not a number of output times");
-  std::vector<LineChunk> out;
-  for (size_t first = 0; first < nTimes; first += chunkTimes) out.push_back({ first, std::min(chunkTimes, nTimes - first) });
-  return out;
+  return timeChunks(nTimes, chunkTimes, "line_chunk_times");
 }

@@ -42,9 +42,9 @@ class SecondOrderFramesParameters : public SecondOrderRules
   std::vector<uint64_t> expandedSensorIndex() const;
 
   // ---- the line-sensor record: its sizes and the order of its chunks, after init() ----
-  static constexpr size_t kLineBudgetBytes = size_t(256) << 20;     ///< of G in the default chunk
-  static constexpr size_t kLineTimesMost   = size_t(65535) * 256;  ///< the record kernel's time tiles are a block index
-  struct LineChunk { size_t first, count; };                        ///< output times first ... first + count - 1
+  static constexpr size_t kLineBudgetBytes = kRecordBudgetBytes;    ///< of G in the default chunk
+  static constexpr size_t kLineTimesMost   = kRecordTimesMost;      ///< the record kernel's time tiles are a block index
+  using LineChunk = TimeChunk;                                       ///< output times first ... first + count - 1
   /// -1 or 0 ... Ny - 1; refuses "line_row"
   void   checkLineRow(int64_t row) const;
   /// the times of one pass: the default for 0, the given number otherwise; refuses "line_chunk_times"

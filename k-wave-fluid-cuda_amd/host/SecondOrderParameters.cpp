@@ -44,6 +44,19 @@ void SecondOrderParameters::init(const DeviceOptions& opt)
   completeAbsorption(e, d, 3);
 }
 
+void SecondOrderParameters::checkPlane(int64_t plane) const
+{
+  if (plane < -1 || (plane >= 0 && static_cast<uint64_t>(plane) >= nz))
+    refuse("plane", std::to_string(plane) + " is outside the domain's planes 0 ... " + std::to_string(nz - 1) + " (-1: no record)");
+}
+
+size_t SecondOrderParameters::planeChunkTimes(uint64_t given) const
+{
+  // G of one output time; the planes of one pass [given][Ey][Ex]
+  return passTimes(given, planeSpectrumElems(1) * 2 * sizeof(float), ex * ey, "plane_chunk_times",
+                   "planes of " + std::to_string(ex) + " x " + std::to_string(ey) + " points");
+}
+
 std::vector<uint64_t> SecondOrderParameters::expandedSensorIndex() const
 {
   std::vector<uint64_t> out(sensorIndex.size());

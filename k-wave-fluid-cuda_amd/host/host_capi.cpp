@@ -1132,11 +1132,50 @@ int kwh_second_order_get_scalar(kwh_second_order* s, const char* name, double* o
   else if (n == "t_free") *out = p.tFree;
   else if (n == "runs") *out = static_cast<double>(s->propagator->runs());
   else if (n == "has_dp0dt") *out = s->propagator->hasDp0dt() ? 1.0 : 0.0;
+  else if (n == "plane") *out = static_cast<double>(s->propagator->plane());
+  else if (n == "plane_chunk_times") *out = static_cast<double>(s->propagator->planeChunkTimes());
   else throw std::invalid_argument(std::string("unknown scalar ") + name);
   KWH_CATCH
 }
 
 void* kwh_second_order_context(kwh_second_order* s) { return kwh_propagator_context(s); }
+
+int kwh_second_order_plane_plan(const kwh_second_order_config* config, const kwh_options* o, int64_t plane, uint64_t chunk_times,
+                                uint64_t n_times, uint64_t out[3])
+{
+  KWH_TRY
+  if (!config || !o) throw std::invalid_argument("kwh_second_order_plane_plan: NULL argument");
+  const SecondOrderParameters p = kwh_second_order_parameters(config, o);
+  p.checkPlane(plane);
+  const size_t chunk = p.planeChunkTimes(chunk_times);
+  const size_t passes = SecondOrderParameters::planeChunks(n_times, chunk).size();
+  if (out) { out[0] = chunk; out[1] = passes; out[2] = p.planeElems(); }
+  KWH_CATCH
+}
+
+int kwh_second_order_set_plane(kwh_second_order* s, int64_t plane)
+{
+  KWH_TRY
+  if (!s) throw std::invalid_argument("kwh_second_order_set_plane: NULL propagator");
+  s->propagator->setPlane(plane);
+  KWH_CATCH
+}
+
+int kwh_second_order_set_plane_chunk_times(kwh_second_order* s, uint64_t times)
+{
+  KWH_TRY
+  if (!s) throw std::invalid_argument("kwh_second_order_set_plane_chunk_times: NULL propagator");
+  s->propagator->setPlaneChunkTimes(times);
+  KWH_CATCH
+}
+
+int kwh_second_order_plane_record(kwh_second_order* s, const double* times, uint64_t n_times, float* dst)
+{
+  KWH_TRY
+  if (!s || (!times && n_times != 0)) throw std::invalid_argument("kwh_second_order_plane_record: NULL argument");
+  s->propagator->planeRecord(times, n_times, dst);
+  KWH_CATCH
+}
 
 // ---- batched 2-D exact k-space propagator -----------------------------------------------------------------------------
 int kwh_second_order_frames_plan(const kwh_second_order_frames_config* config, const kwh_options* o, uint64_t out_expanded[2],

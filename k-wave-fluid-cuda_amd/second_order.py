@@ -5,7 +5,9 @@ pressure at any time t, what k-Wave's kspaceSecondOrder computes: one 3-D FFT of
 the real H(|k|; t) and one inverse transform.  There is no time loop, so there is no CFL limit and no stepping error: a
 snapshot at t = 40 us costs two transforms, a sensor record three passes per sample at any sampling interval.  The box is
 periodic; `t_free` is the time up to which the result inside the domain is the free-space one.  No CPU fallback: a missing
-library or device raises.
+library or device raises.  With `plane` set, `plane_record(times)` gives what a planar sensor at z = plane dz records,
+(n_times, Ny, Nx) — `recon.PlaneRecon`'s input — in one call: per time and (kx, ky) one sum over the kz bins and one 2-D
+inverse over the record itself, no 3-D round trip per time.
 
 `SecondOrderFrames` is its batched 2-D form (kwave_host.h "Exact k-space propagator on frames"): F independent images
 p0(x, y) that share the medium, the expanded plane, the output times and the sensor points, each carried to any time by one
@@ -17,10 +19,12 @@ over the ky bins and one 1-D inverse over the record itself, no 2-D round trip p
 p^(t) = Hc P0 + Hs V0, so dp0dt = -c0 df/dx with p0 = f(x) launches a one-way wave, and a snapshot (p, dp/dt) continues a
 field.  It is independent of `set_p0`; `None` clears it.
 
-Not built: dp0/dt in `line_record`, time-varying sources, heterogeneous media, Z-slabs, chunks of frames and
+Not built: dp0/dt in `line_record` and `plane_record`, time-varying sources, heterogeneous media, Z-slabs, chunks of frames and
 frames over several GPUs, HDF5 files and the command line, graphs, several output times per pass and inverse passes
-restricted to the crop, to the sensor points or to the rows that hold sensors (but for the one row of `line_record`),
-several rows, columns or arbitrary points in `line_record`, particle velocity outputs.
+restricted to the crop, to the sensor points or to the rows that hold sensors (but for the one row of `line_record` and the
+one plane of `plane_record`),
+several rows, columns or arbitrary points in `line_record`, planes normal to x or y and several planes in `plane_record`,
+particle velocity outputs.
 """
 from __future__ import annotations
 
@@ -69,6 +73,11 @@ def _lib() -> C.CDLL:
             fn("get_scalar").argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_double)]
             fn("context").restype = C.c_void_p
             fn("context").argtypes = [C.c_void_p]
+        L.kwh_second_order_plane_plan.argtypes = [C.POINTER(Config), C.POINTER(Options), C.c_int64, C.c_uint64, C.c_uint64,
+                                                  C.POINTER(C.c_uint64)]
+        L.kwh_second_order_set_plane.argtypes = [C.c_void_p, C.c_int64]
+        L.kwh_second_order_set_plane_chunk_times.argtypes = [C.c_void_p, C.c_uint64]
+        L.kwh_second_order_plane_record.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_uint64, C.c_void_p]
         L.kwh_second_order_frames_line_plan.argtypes = [C.POINTER(FramesConfig), C.POINTER(Options), C.c_int64, C.c_uint64,
                                                         C.c_uint64, C.POINTER(C.c_uint64)]
         L.kwh_second_order_frames_set_line_row.argtypes = [C.c_void_p, C.c_int64]
@@ -125,25 +134,9 @@ def _config(n, d, c0, alpha_coeff, alpha_power, t_max, expanded, sensor_index, r
     return c, idx
 
 
-class SecondOrder:
-    """The pressure at any time from an initial pressure p0 (Nz, Ny, Nx) (x fastest) in a homogeneous medium.
-
-    n = (Nx, Ny, Nz), d = (dx, dy, dz) [m], c0 [m/s].  alpha_coeff [dB / (MHz^y cm)] (0: lossless) and alpha_power y: power-law
-    absorption with its dispersion, underdamped modes only (a coefficient that damps a mode of the grid beyond B = 1/4 is
-    refused).  t_max [s] sizes the default expanded grid: per axis the smallest fast-path length >= N + ceil(c0 t_max / d);
-    expanded = (Ex, Ey, Ez) gives the sides instead (expanded = n: the periodic box).  sensor_index: 0-based flat indices
-    into the (Nz, Ny, Nx) array, sampled by run(); record: which of "p_raw", "p_max", "p_min", "p_rms", "p_final" run() keeps.
-
-    set_p0(p0), then field(t) -> (Nz, Ny, Nx) or run(times) -> the record (n_times, n_sensor); times in any order.
-    set_dp0dt(v) adds dp/dt at t = 0 (Nz, Ny, Nx) [Pa/s]; None clears it (has_dp0dt)."""
-
-    _ENTRY = "kwh_second_order"   # the C entry points' common name (SecondOrderFrames: its own)
-
-    def __init__(self, n, d, c0, alpha_coeff=0.0, alpha_power=1.5, t_max=None, expanded=None, sensor_index=None,
-                 record=("p_raw",), fused_kernels=True, device_idx=-1):
-        c, idx = _config(n, d, c0, alpha_coeff, alpha_power, t_max, expanded, sensor_index, record)
-        self._create(c, idx, fused_kernels, device_idx)
-        self.nx, self.ny, self.nz = int(c.nx), int(c.ny), int(c.nz)
+class _Propagator:
+    """What SecondOrder and SecondOrderFrames share: the handle and its scalars, dp0dt, field, run, the aggregates of a run.
+    `_ENTRY` is the C entry points' common name."""
 
     def _create(self, c, idx, fused_kernels, device_idx):
         self.L, self._h = _lib(), None
@@ -160,30 +153,10 @@ class SecondOrder:
     def _fn(cls, what: str):
         return getattr(_lib(), cls._ENTRY + "_" + what)
 
-    @staticmethod
-    def plan(n, d, c0, alpha_coeff=0.0, alpha_power=1.5, t_max=None, expanded=None, sensor_index=None, record=("p_raw",),
-             fused_kernels=True) -> Tuple[Tuple[int, int, int], bool]:
-        """((Ex, Ey, Ez), fast path), validated as the constructor would, without a device"""
-        L = _lib()
-        c, _idx = _config(n, d, c0, alpha_coeff, alpha_power, t_max, expanded, sensor_index, record)
-        o = Options()
-        o.fused_kernels = int(bool(fused_kernels))
-        e, fast = (C.c_uint64 * 3)(), C.c_int32()
-        _check(L.kwh_second_order_plan(C.byref(c), C.byref(o), e, C.byref(fast)))
-        return (int(e[0]), int(e[1]), int(e[2])), bool(fast.value)
-
     def _scalar(self, name: str) -> float:
         v = C.c_double()
         _check(self._fn("get_scalar")(self._h, name.encode(), C.byref(v)))
         return float(v.value)
-
-    @property
-    def shape(self):
-        return (self.nz, self.ny, self.nx)
-
-    @property
-    def expanded(self) -> Tuple[int, int, int]:
-        return tuple(int(self._scalar(n)) for n in ("Ex", "Ey", "Ez"))
 
     @property
     def t_free(self) -> float:
@@ -207,14 +180,6 @@ class SecondOrder:
         _check(self._fn("get")(self._h, name.encode(), out.ctypes.data, out.size))
         return out
 
-    def set_p0(self, p0):
-        """embed, transform and keep the initial pressure; may be called again"""
-        a = np.asarray(p0, dtype=np.float32)
-        if a.shape != self.shape:
-            raise ValueError(f"p0 must be (Nz, Ny, Nx) = {self.shape}, got {a.shape}")
-        a = np.ascontiguousarray(a)
-        _check(self._fn("set_p0")(self._h, a.ctypes.data))
-
     def _set_dp0dt(self, v, name):
         if v is None:
             _check(self._fn("set_dp0dt")(self._h, None))
@@ -224,11 +189,6 @@ class SecondOrder:
             raise ValueError(f"dp0dt must be {name} = {self.shape}, got {a.shape}")
         a = np.ascontiguousarray(a)
         _check(self._fn("set_dp0dt")(self._h, a.ctypes.data))
-
-    def set_dp0dt(self, v):
-        """dp/dt at t = 0 [Pa/s], (Nz, Ny, Nx), as a second initial condition; None clears it.  Independent of set_p0
-        (which stays required, and may be all zeros): either may be called again in any order."""
-        self._set_dp0dt(v, "(Nz, Ny, Nx)")
 
     @property
     def has_dp0dt(self) -> bool:
@@ -279,7 +239,117 @@ class SecondOrder:
             pass
 
 
-class SecondOrderFrames(SecondOrder):
+class SecondOrder(_Propagator):
+    """The pressure at any time from an initial pressure p0 (Nz, Ny, Nx) (x fastest) in a homogeneous medium.
+
+    n = (Nx, Ny, Nz), d = (dx, dy, dz) [m], c0 [m/s].  alpha_coeff [dB / (MHz^y cm)] (0: lossless) and alpha_power y: power-law
+    absorption with its dispersion, underdamped modes only (a coefficient that damps a mode of the grid beyond B = 1/4 is
+    refused).  t_max [s] sizes the default expanded grid: per axis the smallest fast-path length >= N + ceil(c0 t_max / d);
+    expanded = (Ex, Ey, Ez) gives the sides instead (expanded = n: the periodic box).  sensor_index: 0-based flat indices
+    into the (Nz, Ny, Nx) array, sampled by run(); record: which of "p_raw", "p_max", "p_min", "p_rms", "p_final" run() keeps.
+
+    set_p0(p0), then field(t) -> (Nz, Ny, Nx) or run(times) -> the record (n_times, n_sensor); times in any order.
+    set_dp0dt(v) adds dp/dt at t = 0 (Nz, Ny, Nx) [Pa/s]; None clears it (has_dp0dt).
+
+    plane: a plane 0 ... Nz - 1 of the domain (None: none) whose record plane_record(times) -> (n_times, Ny, Nx) gives without
+    a 3-D round trip per time — `recon.PlaneRecon`'s input when times = n dt.  It is prepared by set_p0; plane_chunk_times
+    bounds the output times of one pass (None: by a byte budget).  field, run and plane_record may be interleaved."""
+
+    _ENTRY = "kwh_second_order"   # the C entry points' common name (SecondOrderFrames: its own)
+
+    def __init__(self, n, d, c0, alpha_coeff=0.0, alpha_power=1.5, t_max=None, expanded=None, sensor_index=None,
+                 record=("p_raw",), fused_kernels=True, device_idx=-1, plane=None, plane_chunk_times=None):
+        c, idx = _config(n, d, c0, alpha_coeff, alpha_power, t_max, expanded, sensor_index, record)
+        self._create(c, idx, fused_kernels, device_idx)
+        self.nx, self.ny, self.nz = int(c.nx), int(c.ny), int(c.nz)
+        try:
+            if plane is not None:
+                self.plane = plane
+            if plane_chunk_times is not None:
+                self.plane_chunk_times = plane_chunk_times
+        except Exception:
+            self.close()
+            raise
+
+    @staticmethod
+    def plan(n, d, c0, alpha_coeff=0.0, alpha_power=1.5, t_max=None, expanded=None, sensor_index=None, record=("p_raw",),
+             fused_kernels=True) -> Tuple[Tuple[int, int, int], bool]:
+        """((Ex, Ey, Ez), fast path), validated as the constructor would, without a device"""
+        L = _lib()
+        c, _idx = _config(n, d, c0, alpha_coeff, alpha_power, t_max, expanded, sensor_index, record)
+        o = Options()
+        o.fused_kernels = int(bool(fused_kernels))
+        e, fast = (C.c_uint64 * 3)(), C.c_int32()
+        _check(L.kwh_second_order_plan(C.byref(c), C.byref(o), e, C.byref(fast)))
+        return (int(e[0]), int(e[1]), int(e[2])), bool(fast.value)
+
+    @property
+    def shape(self):
+        return (self.nz, self.ny, self.nx)
+
+    @property
+    def expanded(self) -> Tuple[int, int, int]:
+        return tuple(int(self._scalar(n)) for n in ("Ex", "Ey", "Ez"))
+
+    def set_p0(self, p0):
+        """embed, transform and keep the initial pressure; may be called again"""
+        a = np.asarray(p0, dtype=np.float32)
+        if a.shape != self.shape:
+            raise ValueError(f"p0 must be (Nz, Ny, Nx) = {self.shape}, got {a.shape}")
+        a = np.ascontiguousarray(a)
+        _check(self._fn("set_p0")(self._h, a.ctypes.data))
+
+    def set_dp0dt(self, v):
+        """dp/dt at t = 0 [Pa/s], (Nz, Ny, Nx), as a second initial condition; None clears it.  Independent of set_p0
+        (which stays required, and may be all zeros): either may be called again in any order."""
+        self._set_dp0dt(v, "(Nz, Ny, Nx)")
+
+    @staticmethod
+    def plane_plan(n, d, c0, plane, n_times, plane_chunk_times=None, **kw) -> Tuple[int, int, int]:
+        """(output times of one pass, passes for n_times, complex values of Q), checked as the plane setter, the chunk setter
+        and plane_record would, without a device; kw: the constructor's other arguments"""
+        o = Options()
+        o.fused_kernels = int(bool(kw.pop("fused_kernels", True)))
+        c, _idx = _config(n, d, c0, kw.pop("alpha_coeff", 0.0), kw.pop("alpha_power", 1.5), kw.pop("t_max", None),
+                          kw.pop("expanded", None), kw.pop("sensor_index", None), kw.pop("record", ("p_raw",)))
+        if kw:
+            raise TypeError(f"unknown arguments {sorted(kw)}")
+        out = (C.c_uint64 * 3)()
+        _check(_lib().kwh_second_order_plane_plan(C.byref(c), C.byref(o), -1 if plane is None else int(plane),
+                                                  int(plane_chunk_times or 0), int(n_times), out))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    @property
+    def plane(self):
+        """the plane that plane_record records (None: none); setting it takes effect at the next set_p0"""
+        r = int(self._scalar("plane"))
+        return None if r < 0 else r
+
+    @plane.setter
+    def plane(self, plane):
+        _check(_lib().kwh_second_order_set_plane(self._h, -1 if plane is None else int(plane)))
+
+    @property
+    def plane_chunk_times(self) -> int:
+        """output times per pass of plane_record; set None or 0 for the default"""
+        return int(self._scalar("plane_chunk_times"))
+
+    @plane_chunk_times.setter
+    def plane_chunk_times(self, times):
+        if times is not None and int(times) < 0:
+            raise ValueError(f"plane_chunk_times must not be negative, got {times}")
+        _check(_lib().kwh_second_order_set_plane_chunk_times(self._h, int(times or 0)))
+
+    def plane_record(self, times) -> np.ndarray:
+        """the pressure on the plane z = plane dz at every time of `times` [s], in the given order: float32 (n_times, Ny, Nx)"""
+        ta = np.ascontiguousarray(np.asarray(times, dtype=np.float64).reshape(-1))
+        out = np.empty((int(ta.size), self.ny, self.nx), dtype=np.float32)
+        _check(_lib().kwh_second_order_plane_record(self._h, ta.ctypes.data_as(C.POINTER(C.c_double)), ta.size,
+                                                    out.ctypes.data))
+        return out
+
+
+class SecondOrderFrames(_Propagator):
     """The pressure at any time from F independent initial pressures p0 (F, Ny, Nx) (x fastest) in one homogeneous medium:
     SecondOrder in 2-D, batched — one pass serves all frames.
 

@@ -39,6 +39,8 @@ def main():
                                                                           # (no kernel of the pipeline: k_line_record<FT>
                                                                           # and k_line_prepare, the same at every length)
                                                                           os.path.join(CSRC, "kw_second_order_line.hip"),
+                                                                          # (likewise: k_plane_record<KX>, k_plane_prepare)
+                                                                          os.path.join(CSRC, "kw_second_order_plane.hip"),
                                                                           os.path.join(CSRC, "kw_plane_recon.hip"),
                                                                           os.path.join(CSRC, "kw_line_recon.hip")]
         texts = list(pool.map(compile_one, [(length, src, tmp, extra) for src in srcs]))
